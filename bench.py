@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""bench.py -- FourQ scalar-mults/sec: BASELINE.json config 2 per GPU as the headline, configs 3-5 beside it.
+"""bench.py -- FourQ scalar-mults/sec: BASELINE.json config 2 per GPU as the headline, configs 3-5 beside it with --full.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 started from a bare shell launches its own N rank processes (python -m
 torch.distributed.run on 127.0.0.1, a free port) BEFORE anything touches a GPU and relays rank 0's line; started
@@ -10,12 +10,14 @@ rank on GPU 0 over gloo (rehearsal of the N > 1 code on a one-GPU box; at most 6
 
 One step = one pass of the hot path over one batch: 2^16 variable-base MUL_endo(m_i, P_i) per GPU (random 256-bit
 scalars; P_i = projective N-torsion points, raw R1 outputs of fixed-base [k_i]G), inputs and outputs resident in
-HBM.  The default run then measures configs 3, 4, 5 at their per-GPU sizes (nested under "configs") and, on one GPU,
-the PCIe-inclusive rate of the host-array API ("pcie_inclusive") and the CPU baseline.  Ranks are independent (weak
-scaling, no data-path collective); the one collective of the path, the gather of results, is timed apart
-("gather_ms").  Every rank checks every output of its shard against the C restatement of the reference before
-anything is reported.  Rank 0 prints ONE JSON line.  Synthetic data; integer arithmetic (u32 x 5 limbs of
-GF(2^127-1) inside, "u64" words at the ABI).
+HBM.  A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the
+last timed step computed (dump_outputs).  `--full` adds everything beyond the headline figure: every rank checks every
+output of its shard against the C restatement of the reference (and the edge-case mini-batch) before anything is
+reported, configs 3, 4, 5 are measured at their per-GPU sizes (nested under "configs"), and, on one GPU, the
+constant-time mode, the PCIe-inclusive rate of the host-array API ("pcie_inclusive"), the operation alongside, the
+size sweep, small batches and the CPU baseline.  Ranks are independent (weak scaling, no data-path collective); with
+`--full` the one collective of the path, the gather of results, is timed apart ("gather_ms").  Rank 0 prints ONE JSON
+line.  Synthetic data; integer arithmetic (u32 x 5 limbs of GF(2^127-1) inside, "u64" words at the ABI).
 """
 import argparse
 import json
@@ -360,6 +362,7 @@ class Bench:
             st1 = torch.empty(n, dtype=torch.uint8, device=self.dev)
             st2 = torch.empty(n, dtype=torch.uint8, device=self.dev)
             d["status"] = (st1, st2)
+            d["mid"] = mid
 
             def step():
                 eng.comb_mul_dev(second, None, mid, st1, n)               # == DH_endo(b, G, table_endo([392]G)), affine
@@ -862,6 +865,37 @@ def _built_from_sources():
         return None
 
 
+# ---- --dump-outputs ----------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 60 * 10 ** 6       # all files of a --dump-outputs run stay below 64 MB, npy headers and row indices included
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(dirname, workload, d, rank=0, world=1):
+    """Writes what the last timed step handed its caller as DIR/<name>.npy: `out` (cfg2, cfg3, cfg5: the R1 results, 20 words per
+    unit; cfg4: the affine shared points, 8 words), and for cfg4 `public` (the affine keys of the keygen half) and the two DH status
+    bytes `status_public` / `status`.  The outputs are integers, so each row is written as its little-endian bytes, one float32 per
+    byte: exact, and a changed word differs by at least 1 in some byte.  When the rows would exceed this rank's share of
+    DUMP_MAX_BYTES, the same fixed, seeded sample of rows is taken from every array and `rows.npy` holds their indices.  Ranks of an
+    N-GPU job (each with its own seeds) add `_rank<r>` to the names."""
+    import numpy as np
+    arrays = {"out": d["out"]}
+    if workload == "cfg4":
+        arrays = {"public": d["mid"], "out": d["out"], "status_public": d["status"][0], "status": d["status"][1]}
+    host = {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in arrays.items()}
+    n = len(host["out"])
+    host = {k: v.reshape(n, -1).view(np.uint8) for k, v in host.items()}
+    row_bytes = 4 * sum(v.shape[1] for v in host.values())
+    keep = max(1, DUMP_MAX_BYTES // world // (row_bytes + 8))
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    if n > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        host = {k: v[rows] for k, v in host.items()}
+        np.save(os.path.join(dirname, "rows%s.npy" % suffix), rows.astype(np.float64))
+    for k, v in host.items():
+        np.save(os.path.join(dirname, "%s%s.npy" % (k, suffix)), v.astype(np.float32))
+
+
 # ---- what is printed ---------------------------------------------------------------------------------------------
 LINE_MAX_BYTES = 6144        # the driver reads the tail of stdout: the line must stay far below what it keeps (VERDICT r5: 22 KB was not parsed)
 
@@ -1002,6 +1036,10 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="profiling runs only: skip the whole-shard C-oracle gate")
     ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"), help="where the full record goes (also printed on stderr); '' = nowhere")
     ap.add_argument("--no-ct", action="store_true", help="skip the constant-time-selection records (second context, FOURQ_CT_SELECT mode)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline figure: the C-oracle parity gates and edge cases, configs 3-5, the constant-time "
+                    "mode, PCIe-inclusive rates, the operation alongside, size sweep, small batches, CPU baseline and (N > 1) the timed gather; "
+                    "the --no-* options trim this")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -1048,22 +1086,29 @@ def main():
     n = args.batch or wl["batch"]
     steps = args.steps or wl["steps"]
     rec, d = b.run(args.workload, n, steps, args.warmup)
-    parity, got, want = ({"gate": "skipped (--no-parity)", "ok": None}, None, None) if args.no_parity else b.parity_gate(args.workload, d)
-    if not args.no_parity:                                  # the edge-case mini-batch belongs to EVERY run, on every rank (raises on a difference)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, args.workload, d, rank, world)
+    if not args.full:
+        parity, got, want = {"gate": "skipped (without --full)", "ok": None}, None, None
+    elif args.no_parity:
+        parity, got, want = {"gate": "skipped (--no-parity)", "ok": None}, None, None
+    else:
+        parity, got, want = b.parity_gate(args.workload, d)
+        # the edge-case mini-batch belongs to every --full run, on every rank (raises on a difference)
         parity["edge_cases_checked"] = edge_case_check(b.eng)
-    gather = b.gather_ms(d["out"], n) if dist_on else None
+    gather = b.gather_ms(d["out"], n) if dist_on and args.full else None
     alongside = None
-    if rank == 0 and args.workload in ("cfg2", "cfg3") and not args.no_alongside and not args.no_parity:
+    if rank == 0 and args.workload in ("cfg2", "cfg3") and args.full and not args.no_alongside and not args.no_parity:
         alongside = b.alongside(args.workload, d, steps=100 if args.workload == "cfg2" else 20)
 
     # constant-time selection mode beside the default, on a second context (one GPU only: the N > 1 runs measure scaling)
-    do_ct = world == 1 and not args.no_ct and not b.eng.ct_select
+    do_ct = world == 1 and args.full and not args.no_ct and not b.eng.ct_select
     ct = {}
     if do_ct:
         ct[args.workload] = b.ct_select_record(args.workload, n, max(5, steps // 5), 2, want, rec["ms_per_step"])
 
     configs = {}
-    others = [] if (args.no_configs or args.batch) else [w for w in sorted(WORKLOADS) if w != args.workload]
+    others = [] if (not args.full or args.no_configs or args.batch) else [w for w in sorted(WORKLOADS) if w != args.workload]
     pcie_reps = {"cfg2": 21, "cfg3": 5, "cfg4": 5, "cfg5": 11}
     for w in others:
         r, dw = b.run(w, WORKLOADS[w]["batch"], WORKLOADS[w]["steps"], max(2, args.warmup // 4))
@@ -1088,13 +1133,13 @@ def main():
         where = "cpu" if rehearse else b.dev
         ok = torch.tensor([1.0 if parity["ok"] in (True, None) else 0.0], device=where)
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        parity["all_ranks_ok"] = bool(ok.item() == 1.0)
+        parity["all_ranks_ok"] = bool(ok.item() == 1.0) if args.full else None     # without --full no rank ran a gate
         # ranks_seen is a record, not a guard: a rank that died makes the collectives above fail or time out (init_process_group's
         # timeout), and this process then exits non-zero without a line (tests/test_dist.py)
         here = torch.tensor([1.0], device=where)
         dist.all_reduce(here, op=dist.ReduceOp.SUM)
         ranks_seen = int(round(here.item()))
-        if ranks_seen != args.gpus or not parity["all_ranks_ok"]:
+        if ranks_seen != args.gpus or parity["all_ranks_ok"] is False:
             raise SystemExit("bench.py --gpus %d: %d ranks reported, all_ranks_ok=%s -- no result line is printed for an incomplete job"
                              % (args.gpus, ranks_seen, parity["all_ranks_ok"]))
         cyc = rec["cycles_per_unit"] or 0.0                                     # per-rank cycles per unit: the spread over the node's devices
@@ -1124,16 +1169,16 @@ def main():
             full["alongside"] = alongside
         if configs:
             full["configs"] = configs
-        if world == 1 and not args.no_pcie and want is not None:
+        if world == 1 and args.full and not args.no_pcie and want is not None:
             full["pcie_inclusive"] = b.pcie_inclusive(args.workload, d, want, reps=pcie_reps[args.workload], ct_ms=(ct.get(args.workload) or {}).get("ms_per_step"))
-        if world == 1 and args.workload == "cfg2" and not args.batch and not args.no_alongside:
+        if world == 1 and args.workload == "cfg2" and args.full and not args.batch and not args.no_alongside:
             full["size_sweep"] = b.size_sweep(d)
             if not args.no_parity:
                 full["small_batches"] = b.small_batches(d)
         if ct:
             full["ct_select"] = ct
         # The CPU baseline is an N = 1 figure (rank 0, alone on the host): at N > 1 the other ranks' oracle gates would share its cores
-        if world == 1 and not args.no_cpu_baseline and got is not None:
+        if world == 1 and args.full and not args.no_cpu_baseline and got is not None:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             sample = min(n, 1 << 16)
             items, extra, what = cpu_items(args.workload, d, sample)

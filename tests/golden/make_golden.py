@@ -18,11 +18,16 @@ Files written
   wire.json       encode / decode round trips, arbitrary strings, malformed inputs
   protocol.json   GFp.select / GFp2.select, and the protocol step encode(DH(m, decode(B))) composed from the reference's
                   own three functions (draft-ladd-cfrg-4q.md:707-723), incl. every way it fails
+  reference.json  what tests/test_oracle_vs_reference.py compares the oracle with: the reference's constants and public names,
+                  its self-tests' output, and its results on that test's seeded inputs (bulk results as digests(), see there)
 """
+import hashlib
+import io
 import json
 import os
 import random
 import sys
+from contextlib import redirect_stdout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
@@ -386,9 +391,84 @@ def make_protocol():
     return out
 
 
+def digest(values):
+    """16 hex digits of SHA-256 over the hex form of `values` (tests/test_oracle_vs_reference.py computes the same of the oracle's)."""
+    return hashlib.sha256(json.dumps(hx(values), separators=(",", ":")).encode()).hexdigest()[:16]
+
+
+def make_reference():
+    """The inputs are drawn exactly as tests/test_oracle_vs_reference.py draws them again (same seeds, same order)."""
+    out = {}
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        for fn in ("test_definitions", "test_reps", "test_core", "test_endo", "test_recoding", "test_mul_windowed", "test_mul_endo"):
+            getattr(C, fn)()
+    out["self_tests"] = buf.getvalue().splitlines()
+    if [ln for ln in out["self_tests"] if not ln.startswith("[PASS]")]:
+        raise SystemExit("the reference's self-tests did not all pass under the loader")
+    out["constants"] = hx({"p1271": F.p1271, "d": C.d, "N": C.N, "Gx": C.Gx, "Gy": C.Gy, "Ox": C.Ox, "Oy": C.Oy, "ctau": C.ctau,
+                           "ctaudual": C.ctaudual, "cphi": [getattr(C, "cphi%d" % i) for i in range(10)],
+                           "cpsi": [getattr(C, "cpsi%d" % i) for i in (1, 2, 3, 4)], "basis": [C.b1, C.b2, C.b3, C.b4],
+                           "ell": [C.L1, C.L2, C.L3, C.L4], "c": C.c, "cp": C.cp})
+    skip = {"getrandbits", "test"} | {n for n in dir(C) if n.startswith("test_")}
+    public = [n for n in dir(C) if not n.startswith("_") and n not in skip]
+    out["public_names"] = public
+    out["public_values"] = {n: hx(getattr(C, n)) for n in public if isinstance(getattr(C, n), (int, tuple, list))}
+    out["field_methods"] = {cls: [n for n in dir(getattr(F, cls)) if not n.startswith("_") and n not in ("A", "S", "M", "I", "ctr", "ctr_reset", "ctr_enabled")]
+                            for cls in ("GFp", "GFp2")}
+    rng = random.Random(11)
+    edge = [0, 1, 2, C.N - 1, C.N, C.N + 1, (1 << 256) - 1, 1 << 255, (1 << 64) - 1, 1 << 64]
+    ms = edge + [rng.getrandbits(256) for _ in range(20000)]
+    out["decompose_edge"] = hx([C.decompose(m) for m in edge])
+    out["decompose"] = digest([C.decompose(m) for m in ms])
+    ms = edge + [rng.getrandbits(256) for _ in range(1500)]
+    out["recode"] = digest([[list(x) for x in C.recode(C.decompose(m))] for m in ms])
+    rng = random.Random(12)
+    ops = []
+    for _ in range(3000):
+        a, b = (rng.getrandbits(127) % P, rng.getrandbits(127) % P), (rng.getrandbits(127) % P, rng.getrandbits(127) % P)
+        ops.append([F.GFp2.mul(a, b), F.GFp2.sqr(a), F.GFp2.add(a, b), F.GFp2.sub(a, b)])
+    out["field"] = digest(ops)
+    ops = []
+    for _ in range(40):
+        a = (rng.getrandbits(127) % P, rng.getrandbits(127) % P)
+        ops.append([F.GFp2.inv(a), F.GFp.invsqrt(a[0])])
+    out["field_inv"] = digest(ops)
+    rng = random.Random(13)
+    Pt, aff, chain = C.AffineToR1(C.Gx, C.Gy), (C.Gx, C.Gy), []
+    for i in range(60):
+        m = rng.getrandbits(256)
+        e = C.MUL_endo(m, Pt)
+        row = [e, C.MUL_windowed(m, Pt)]
+        if i % 6 == 0:
+            row += [C.table_endo(Pt), C.table_windowed(Pt), C.DH_endo(m, aff), C.DH_windowed(m, aff)]
+            aff = C.DH_endo(m, aff)
+        chain.append(digest(row))
+        Pt = e
+    out["scalar_mul_and_dh"] = chain
+    rng = random.Random(14)
+    wire = []
+    for _ in range(150):
+        raw = bytearray(rng.getrandbits(256).to_bytes(32, "little"))
+        raw[15] &= 0x7F
+        try:
+            wire.append(["ok", hx(C.decode(bytearray(raw)))])
+        except Exception as exc:
+            wire.append([type(exc).__name__, str(exc)])
+    out["wire"] = wire
+    rng = random.Random(15)
+    cases = [(rng.getrandbits(127) % P, rng.getrandbits(127) % P) for _ in range(40)]
+    cases += [(rng.getrandbits(127) % P, 0) for _ in range(20)] + [(4, 0), (1, 0), (2, 0)]
+    out["gfp2_invsqrt"] = hx([[a, F.GFp2.invsqrt(a)] for a in cases])
+    return out
+
+
 if __name__ == "__main__":
     if "--only-protocol" in sys.argv:                     # the other files are unchanged since round 1
         dump("protocol.json", make_protocol())
+        raise SystemExit(0)
+    if "--only-reference" in sys.argv:
+        dump("reference.json", make_reference())
         raise SystemExit(0)
     dump("kat.json", hx(make_kat()))
     dump("field.json", make_field())
@@ -399,3 +479,4 @@ if __name__ == "__main__":
     dump("dh.json", make_dh())
     dump("wire.json", make_wire())
     dump("protocol.json", make_protocol())
+    dump("reference.json", make_reference())

@@ -109,7 +109,7 @@ def test_bench_prints_no_line_for_a_job_that_is_not_whole(tmp_path):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    argv = ["--gpus", "2", "--batch", "256", "--steps", "1", "--warmup", "0", "--no-configs", "--no-pcie", "--no-alongside", "--no-ct", "--no-cpu-baseline"]
+    argv = ["--gpus", "2", "--batch", "256", "--steps", "1", "--warmup", "0", "--full", "--no-configs", "--no-pcie", "--no-alongside", "--no-ct", "--no-cpu-baseline"]
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2",
@@ -173,7 +173,7 @@ def test_bench_rank_body_runs_world_2_over_gloo_without_a_gpu(tmp_path):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    argv = ["--gpus", "2", "--batch", "384", "--steps", "2", "--warmup", "1", "--no-configs", "--no-pcie", "--no-alongside", "--no-ct", "--full-json", str(tmp_path / "full.json")]
+    argv = ["--gpus", "2", "--batch", "384", "--steps", "2", "--warmup", "1", "--full", "--no-configs", "--no-pcie", "--no-alongside", "--no-ct", "--full-json", str(tmp_path / "full.json")]
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2")
@@ -195,3 +195,34 @@ def test_bench_rank_body_runs_world_2_over_gloo_without_a_gpu(tmp_path):
     assert 0 < lo <= hi
     # whole-job value: both ranks' units over the slower rank's time
     assert abs(line["value"] - 2 * 384 * 2 / (line["ms_per_step"] * 2 * 1e-3)) / line["value"] < 0.01
+
+
+def test_bench_plain_run_over_gloo_dumps_each_ranks_outputs_without_a_gpu(tmp_path):
+    """Without --full a rank times its steps and prints the line, with no oracle gate, gather or CPU baseline; --dump-outputs writes
+    each rank's last-step results (bench.dump_outputs: one float32 per byte of the u64 words), which are the oracle's on that rank's seeds."""
+    import json
+    import subprocess
+    import oracle_c as oc
+    from bench import WORKLOADS, RANK_SEED_STRIDE, seeded_scalars
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    dump = tmp_path / "outputs"
+    argv = ["--gpus", "2", "--batch", "384", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump), "--full-json", ""]
+    procs = []
+    for rank in range(2):
+        env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "bench_cpu_rank.py")] + argv, env=env,
+                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    outs = [p.communicate(timeout=600) for p in procs]
+    assert all(p.returncode == 0 for p in procs), "\n".join(o[1][-2000:] for o in outs)
+    line = json.loads([ln for ln in outs[0][0].splitlines() if ln.startswith('{"metric"')][-1])
+    assert line["steps"] == 3 and line["parity_ok"] is None and line["config"]["ranks_seen"] == 2
+    assert "gather_ms" not in line and "cpu_baseline" not in line and "configs" not in line
+    assert sorted(os.listdir(dump)) == ["out_rank0.npy", "out_rank1.npy"]
+    for rank in range(2):
+        got = np.load(dump / ("out_rank%d.npy" % rank))
+        assert got.dtype == np.float32 and got.shape == (384, 160)
+        seed = WORKLOADS["cfg2"]["seed"] + RANK_SEED_STRIDE * rank
+        points = oc.mul(oc.ENDO, seeded_scalars(seed + 1, 384), None, oc.table(oc.ENDO, _g1()))
+        assert np.array_equal(got.astype(np.uint8).view("<u8"), oc.mul(oc.ENDO, seeded_scalars(seed, 384), points))

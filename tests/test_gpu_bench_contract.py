@@ -1,6 +1,7 @@
-"""The driver's contract with bench.py, checked on the GPU box: one JSON line on stdout with the agreed keys, the headline
-metric on BASELINE.json's configuration, `roofline` and `cpu_baseline` objects, a parity verdict, and the nested records
-of configs 3-5.  Short runs (few steps); the numbers themselves are not asserted, their consistency is."""
+"""The driver's contract with bench.py, checked on the GPU box: one JSON line on stdout with the agreed keys and the headline
+metric on BASELINE.json's configuration; with --full also `roofline` and `cpu_baseline` objects, a parity verdict, and the nested
+records of configs 3-5; --dump-outputs writes the last timed step's results.  Short runs (few steps); the numbers themselves are not
+asserted, their consistency is."""
 import json
 import os
 import subprocess
@@ -37,7 +38,7 @@ def run_bench(tmp_path, *args):
 def test_the_compact_line_is_what_the_driver_reads(tmp_path):
     """one line, numbers only, <= 6 KB, with the contract keys, `roofline` and `cpu_baseline` at top level and one flat
     record per nested config; everything else in the full record."""
-    short, full = run_bench(tmp_path, "--steps", "20", "--warmup", "5")         # the driver's own arguments
+    short, full = run_bench(tmp_path, "--full", "--steps", "20", "--warmup", "5")
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int), ("ms_per_step", float),
                      ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict), ("roofline", dict),
                      ("cpu_baseline", dict), ("valu_roofline", dict), ("configs", dict), ("pcie", dict), ("clock_mhz", float), ("cycles_per_unit", float),
@@ -74,7 +75,7 @@ def test_the_compact_line_is_what_the_driver_reads(tmp_path):
 
 
 def test_default_line_has_the_contract_keys(tmp_path):
-    _, line = run_bench(tmp_path, "--steps", "20", "--warmup", "2")
+    _, line = run_bench(tmp_path, "--full", "--steps", "20", "--warmup", "2")
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
                      ("config", dict), ("roofline", dict), ("cpu_baseline", dict), ("valu_roofline", dict), ("parity", dict),
@@ -141,8 +142,38 @@ def test_default_line_has_the_contract_keys(tmp_path):
 
 
 def test_single_workload_line(tmp_path):
-    short, line = run_bench(tmp_path, "--workload", "cfg5", "--steps", "10", "--warmup", "1", "--no-configs", "--no-cpu-baseline", "--no-pcie", "--no-ct")
+    short, line = run_bench(tmp_path, "--full", "--workload", "cfg5", "--steps", "10", "--warmup", "1", "--no-configs", "--no-cpu-baseline", "--no-pcie", "--no-ct")
     assert "configs[4]" in line["config"]["workload"] and "configs" not in line and "cpu_baseline" not in line and "alongside" not in line
     assert "ct_select" not in line and "pcie_inclusive" not in line
     assert line["parity"]["ok"] is True and line["config"]["batch_per_gpu"] == 1 << 17
     assert "configs" not in short and "cpu_baseline" not in short and "pcie" not in short and short["parity_ok"] is True and "configs[4]" in short["config"]["workload"]
+
+
+def test_plain_line_times_the_steps_it_is_given_and_dumps_what_they_computed(tmp_path):
+    """The driver's own arguments without --full: set-up, warm-up, exactly K timed steps and the line, nothing of what --full adds.
+    --dump-outputs writes the last timed step's R1 results, one float32 per byte, and they are the C oracle's on the seeded inputs."""
+    import numpy as np
+    import oracle_c as oc
+    import bench
+    from fourq_amd import codec, constants
+    dump = tmp_path / "outputs"
+    short, full = run_bench(tmp_path, "--steps", "7", "--warmup", "2", "--dump-outputs", str(dump))
+    for key, typ in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str)):
+        assert isinstance(short[key], typ), key
+    assert short["steps"] == 7 and short["warmup"] == 2 and short["unit"] == "scalar-mults/s" and short["dtype"] == "u64"
+    assert short["higher_is_better"] is True and short["metric"] == "FourQ scalar-mults/sec (batch, whole node)"
+    assert abs(short["value"] - (1 << 16) / (short["ms_per_step"] * 1e-3)) / short["value"] < 0.01
+    assert short["parity_ok"] is None and full["parity"]["ok"] is None
+    for key in ("configs", "cpu_baseline", "pcie", "ct_value", "alongside_value", "gather_ms"):
+        assert key not in short, key
+    for key in ("configs", "cpu_baseline", "pcie_inclusive", "ct_select", "alongside", "size_sweep", "small_batches", "gather_ms"):
+        assert key not in full, key
+    assert sorted(os.listdir(dump)) == ["out.npy"]
+    got = np.load(dump / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (1 << 16, 160) and os.path.getsize(dump / "out.npy") < 64 * 10 ** 6
+    words = got.astype(np.uint8).view("<u8")
+    n, seed = 1 << 16, bench.WORKLOADS["cfg2"]["seed"]
+    G_aff = (constants.Gx, constants.Gy)
+    table = oc.table(oc.ENDO, codec.pack_point(G_aff + ((1, 0),) + G_aff))
+    points = oc.mul(oc.ENDO, bench.seeded_scalars(seed + 1, n), None, table)
+    assert np.array_equal(words, oc.mul(oc.ENDO, bench.seeded_scalars(seed, n), points))

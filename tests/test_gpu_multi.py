@@ -106,7 +106,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     for var in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(var, None)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg2", "--steps", "5", "--warmup", "1",
-                           "--no-cpu-baseline", "--no-configs"], capture_output=True, text=True, env=env, timeout=900)
+                           "--full", "--no-cpu-baseline", "--no-configs"], capture_output=True, text=True, env=env, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines[:3]
@@ -279,7 +279,7 @@ def test_bench_rank_body_over_rccl_with_a_group_of_one():
     env = dict(os.environ, FOURQ_BENCH_FORCE_DIST="1", FOURQ_BENCH_SETTLE_MS="10", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("FOURQ_BENCH_REHEARSE", None)
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", "--no-ct",
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pcie", "--no-ct",
                            "--no-alongside", "--full-json", ""], capture_output=True, text=True, env=env, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]

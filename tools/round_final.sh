@@ -25,14 +25,14 @@ for stage in $STAGES; do
     cat $T/summary.txt ;;
   bench)
     for k in 1 2 3; do
-      python3 bench.py --steps 20 --warmup 5 --full-json $T/bench_driver_args_run$k.full.json > $T/bench_driver_args_run$k.json 2> $T/bench_d$k.err || { tail -20 $T/bench_d$k.err; exit 1; }
+      python3 bench.py --full --steps 20 --warmup 5 --full-json $T/bench_driver_args_run$k.full.json > $T/bench_driver_args_run$k.json 2> $T/bench_d$k.err || { tail -20 $T/bench_d$k.err; exit 1; }
     done
-    python3 bench.py --full-json $T/bench.full.json > $T/bench.json 2> $T/bench.err || { tail -20 $T/bench.err; exit 1; }
+    python3 bench.py --full --full-json $T/bench.full.json > $T/bench.json 2> $T/bench.err || { tail -20 $T/bench.err; exit 1; }
     for w in cfg3 cfg4 cfg5; do
-      python3 bench.py --workload $w --no-configs --full-json $T/bench_$w.full.json > $T/bench_$w.json 2> $T/bench_$w.err || { tail -20 $T/bench_$w.err; exit 1; }
+      python3 bench.py --full --workload $w --no-configs --full-json $T/bench_$w.full.json > $T/bench_$w.json 2> $T/bench_$w.err || { tail -20 $T/bench_$w.err; exit 1; }
     done
     for g in 2 4; do
-      FOURQ_BENCH_REHEARSE=1 python3 bench.py --gpus $g --full-json $T/rehearse_gpus$g.full.json > $T/rehearse_gpus$g.json 2> $T/rehearse$g.err || { tail -20 $T/rehearse$g.err; exit 1; }
+      FOURQ_BENCH_REHEARSE=1 python3 bench.py --gpus $g --full --full-json $T/rehearse_gpus$g.full.json > $T/rehearse_gpus$g.json 2> $T/rehearse$g.err || { tail -20 $T/rehearse$g.err; exit 1; }
     done
     python3 tools/single_call_probe.py > $T/single_call.txt 2>&1 || { tail -20 $T/single_call.txt; exit 1; }
     python3 tools/perf_probe.py --modes endo_var,win_var,dh_endo,endo_fixed,win_fixed,dh_fixed,comb --sizes 16,18,20 > $T/perf_probe.txt 2>/dev/null

@@ -9,7 +9,7 @@ Sources, in this order:
   1. the DRIVER'S own record of the newest round, BENCH_rNN.json at the repo root, when its `parsed` line exists -- stated first, with the
      build id it was taken on (it is the previous round's build until the driver has run this one);
   2. profiles/r06_bench_driver_args_run{1,2,3}.full.json = the full records (bench_full.json) of three runs of
-     `python bench.py --steps 20 --warmup 5` on one MI355X by the builder; the tables are run 1's.
+     `python bench.py --full --steps 20 --warmup 5` on one MI355X by the builder; the tables are run 1's.
 """
 import glob
 import json
@@ -159,7 +159,7 @@ def readme_block(d):
     vals = [r["value"] for r in [d] + earlier_runs()]
     head = e8(d["value"]) if e8(min(vals)) == e8(max(vals)) else "%.2f–%s" % (min(vals) / 1e8, e8(max(vals)))
     return ("%s\n\n"
-            "Numbers of `python bench.py --steps 20 --warmup 5` — the driver's protocol — on one MI355X (`%s`). Boxes of the pool hold clocks\n"
+            "Numbers of `python bench.py --full --steps 20 --warmup 5` — the driver's step counts — on one MI355X (`%s`). Boxes of the pool hold clocks\n"
             "several percent apart under the same kernel, so the line carries the clock of the timed steps and cycles per unit; the builder's three runs:\n"
             "%s.\n"
             "**%s** variable-base scalar multiplications per second at a batch of 2¹⁶ (device-resident;\n"
