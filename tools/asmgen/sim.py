@@ -4,6 +4,7 @@ integers, lane by lane, so that the CPU-only suite can check every generated bod
 (tests/test_asm_bodies.py).  Semantics per the gfx950 ISA for the forms the generator emits; anything else raises.
 
     regs = run(lines, {"%0": limb, ...})        # registers are 32-bit values; "%N" operands, "vN" temporaries, "v[a:b]" pairs
+    run(lines, regs, trace=f)                   # f(instruction, registers) after every instruction (tests/test_asm_bounds.py)
 """
 import re
 
@@ -52,7 +53,7 @@ class Machine:
         self.r["v" + m.group(2)] = (value >> 32) & M32
 
 
-def run(lines, regs):
+def run(lines, regs, trace=None):
     m = Machine(regs)
     for ln in lines:
         ln = ln.strip()
@@ -102,4 +103,6 @@ def run(lines, regs):
             m.put64(ops[0], ((m.get64(ops[1]) << (m.get(ops[2]) & 63)) + m.get64(ops[3])) & M64)
         else:
             raise ValueError("instruction %r is outside the simulated subset" % ln)
+        if trace is not None:
+            trace(ln, m.r)
     return m.r
