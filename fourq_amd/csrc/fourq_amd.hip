@@ -851,6 +851,7 @@ int ensure_work(fourq_ctx* c, size_t bytes) { return grow(c, &c->work, &c->work_
 size_t dh_bytes_work_bytes(size_t n) { return 2 * n * 64 + 2 * align256(n); }
 size_t exchange_work_bytes(size_t n) { return 2 * n * 64 + align256(n); }
 size_t mul_affine_work_bytes(size_t n) { return 2 * n * 160 + n * 64 + align256(n); }      // R1 in, R1 out, decoded points, decode status
+size_t double_mul_work_bytes(size_t n) { return 2 * n * 160 + 2 * align256(n); }             // lifted / decoded points, the ladder's rows, decode status, the comb's status
 
 int ensure_ticks(fourq_ctx* c, size_t count) {
     while (c->ticks.size() < count) {
@@ -865,7 +866,7 @@ using ChunkLaunch = std::function<int(char* const* in_dev, char* const* out_dev,
 
 // Which call this is, for the measured planner inputs, and the guess of its kernel time per element for the context's first call of it
 enum PipeRouteId { PR_MUL_VAR = 0, PR_MUL_FIX = 2, PR_DH_VAR = 4, PR_DH_FIX = 6, PR_MIXED = 8, PR_COMB = 9, PR_ENCODE = 10, PR_DECODE = 11, PR_DHB_VAR = 12,
-                   PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_COUNT = 23 };       // + algo (0 / 1) where two follow each other
+                   PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25, PR_COUNT = 26 };       // + algo (0 / 1) where two follow each other
 struct PipeRoute { int id; double kt_guess; };
 constexpr double KT_CT_GUESS = 1.3;                 // constant-time selection: x 1.07 - 1.5 by route until the context has measured it
 using PipeReserve = std::function<int(size_t big)>; // sizes the context's intermediates for the largest chunk BEFORE the first chunk is enqueued
@@ -1390,6 +1391,7 @@ FQ_API int fourq_ctx_reserve(fourq_ctx* c, size_t n) {
     size_t need = dh_bytes_work_bytes(n);
     if (exchange_work_bytes(n) > need) need = exchange_work_bytes(n);
     if (mul_affine_work_bytes(n) > need) need = mul_affine_work_bytes(n);
+    if (double_mul_work_bytes(n) > need) need = double_mul_work_bytes(n);
     return ensure_work(c, need);
 }
 FQ_API int fourq_ctx_lanes(const fourq_ctx* c, size_t* lanes) {
@@ -1881,6 +1883,104 @@ FQ_API int fourq_dh_exchange_comb_batch(fourq_ctx* c, const uint64_t* a, const u
     return run_pipeline(c, in, 2, o, 2, n, c->lanes_w4 / 2, PipeRoute{ PR_EXCH_COMB, KT_COMB + KT_DH_VAR }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_dh_exchange_comb_batch_dev(c, (const uint64_t*)di[0], (const uint64_t*)di[1], nullptr, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
     }, c->lanes_w4, [&](size_t big) { if (int r = ensure_proj(c, big)) return r; return ensure_work(c, exchange_work_bytes(big)); });
+}
+
+// ---- [k]B + [l]P: the curve part of a Schnorr-type verification (R' = [s]B + [h]A) -------------------------------------------
+// Three stages on the context's stream, nothing affine in between: (1) the comb with deferred normalisation leaves (X, Y, Z) of [k_i]B in
+// the context's projective planes -- comb_kernel<true, CT> for EVERY n, also the sizes fourq_comb_mul_batch gives to comb_quad_kernel, which
+// has only an affine + status output; its projective neutral for k = 0 (mod N) is an ordinary operand of the
+// addition, not FOURQ_DH_NEUTRAL; (2) MUL_endo through mul_dev as mul_affine_dev / mul_bytes_dev call it, so every variable-base route is
+// inherited: (X, Y, Z) rows of 12 words where the batch runs on the fused kernels, lift + R1 rows of 20 words otherwise; (3) combine_kernel
+// (combine.hip.h) adds the halves and lowers the sum, one inversion per element while the batch is within two generations (one wave per SIMD: the chain's latency is the
+// time either way, as launch_lower) and one per two beyond.  `points`: n x 8 affine words, or n x 32 bytes when `encoded`; out_kind: CombineOut.
+static int double_mul_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const void* points, bool encoded, int out_kind,
+                          const uint8_t* expect32, void* out, uint8_t* status, uint8_t* ok, size_t n) {
+    if (!c || !k || !l || !points || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (out_kind == COMBINE_VERIFY ? (!expect32 || !ok || !status || !aligned16(expect32)) : (!out || !aligned16(out))) return FOURQ_ERR_INVALID;
+    if (out_kind == COMBINE_ENCODE && !status) return FOURQ_ERR_INVALID;
+    if (!aligned16(k) || !aligned16(l) || !aligned16(points)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = ensure_proj(c, n))) return rc;
+    if ((rc = ensure_work(c, double_mul_work_bytes(n)))) return rc;
+    uint64_t* rows_in = (uint64_t*)c->work;                     // affine (fused I/O) or R1 rows of the decoded / lifted points
+    uint64_t* rows_out = (uint64_t*)(c->work + n * 160);        // the ladder's result rows
+    uint8_t* st_decode = (uint8_t*)(c->work + 2 * n * 160);
+    uint8_t* st_comb = st_decode + align256(n);                 // comb_kernel<true> writes FOURQ_DH_OK per element; nobody reads it here
+    // (1) [k_i]B, projective
+    const size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
+    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;      // as fourq_comb_mul_batch_dev
+    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, k, c->comb_limbs, nullptr, st_comb, c->proj, (u32)c->proj_capacity, (u32)n));
+    // (2) [l_i]P_i, projective
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const bool fused = fused_io(c, ENDO, n);
+    const uint64_t* ladder_in = rows_in;
+    if (encoded) {
+        if (fused) hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, st_decode, (u32)n);
+        else hipLaunchKernelGGL(decode_lift_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, st_decode, (u32)n);
+        HIP_TRY(c, hipGetLastError());
+    } else if (fused) {
+        ladder_in = (const uint64_t*)points;
+    } else {
+        hipLaunchKernelGGL(lift_affine_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, (u32)n);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if ((rc = mul_dev(c, ENDO, l, ladder_in, nullptr, rows_out, nullptr, n, fused ? (LADDER_IO_AFFINE_IN | LADDER_IO_XYZ_OUT) : 0))) return rc;
+    // (3) the sum, lowered
+    HIPRC_TRY(c, chain_launch_combine(n > 2 * c->lanes ? 2 : 1, out_kind, c->stream, c->proj, (u32)c->proj_capacity, rows_out, fused ? 12 : 20,
+                                      encoded ? st_decode : nullptr, (const u64*)expect32, (u64*)out, status, ok, (u32)n));
+    return FOURQ_OK;
+}
+static int double_mul_reserve(fourq_ctx* c, size_t big) {
+    if (int r = ensure_proj(c, big)) return r;
+    return ensure_work(c, double_mul_work_bytes(big));
+}
+constexpr double KT_DOUBLE = KT_COMB + KT_ENDO_VAR + KT_LIFT_LOWER;
+FQ_API int fourq_double_mul_affine_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
+    return double_mul_dev(c, k, comb, l, points_affine, false, COMBINE_AFFINE, nullptr, out_affine, nullptr, nullptr, n);
+}
+FQ_API int fourq_double_mul_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
+    return double_mul_dev(c, k, comb, l, points32, true, COMBINE_ENCODE, nullptr, out32, status, nullptr, n);
+}
+FQ_API int fourq_verify_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, const uint8_t* expect32,
+                                        uint8_t* ok, uint8_t* status, size_t n) {
+    return double_mul_dev(c, k, comb, l, points32, true, COMBINE_VERIFY, expect32, nullptr, status, ok, n);
+}
+FQ_API int fourq_double_mul_affine_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
+    if (!c || !k || !l || !points_affine || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;                            // compared once, not once per chunk
+    PipeArray in[3] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points_affine, nullptr, 64 } };
+    PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
+    return run_pipeline(c, in, 3, o, 1, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_AFF, KT_DOUBLE }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_double_mul_affine_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint64_t*)di[2], (uint64_t*)dout[0], m);
+    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
+}
+FQ_API int fourq_double_mul_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
+    if (!c || !k || !l || !points32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;
+    PipeArray in[3] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points32, nullptr, 32 } };
+    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
+    return run_pipeline(c, in, 3, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_BYTES, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_double_mul_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
+    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
+}
+FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, const uint8_t* expect32,
+                                    uint8_t* ok, uint8_t* status, size_t n) {
+    if (!c || !k || !l || !points32 || !expect32 || !ok || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;
+    PipeArray in[4] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points32, nullptr, 32 }, { (const char*)expect32, nullptr, 32 } };
+    PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
+    return run_pipeline(c, in, 4, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_VERIFY, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_verify_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (const uint8_t*)di[3], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
+    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
 }
 
 // ---- pinned host memory and transfer statistics of the host-pointer calls ---------------------------------------

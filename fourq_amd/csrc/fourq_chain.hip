@@ -1,11 +1,12 @@
 // Second translation unit of libfourq_amd.so: the kernels that profit from chained carries (FQ_CHAIN=1, see
 // kernels.hip.h): fixed-base ladders (table in LDS), the two-kernel route for large variable-base batches
 // (prep_kernel + ladder_kernel<PREBUILT>), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
-// translation unit; the C ABI lives in fourq_amd.hip.
+// translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P.
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
 #endif
 #include "kernels.hip.h"
+#include "combine.hip.h"
 
 namespace fq {
 
@@ -61,6 +62,23 @@ int chain_launch_normalize(int k, hipStream_t stream, const uint4* proj, u32 pro
     else if (k == 2) hipLaunchKernelGGL(normalize_kernel<2>, dim3(grid), dim3(BLOCK), 0, stream, proj, proj_stride, out, status, n);
     else hipLaunchKernelGGL(normalize_kernel<1>, dim3(grid), dim3(BLOCK), 0, stream, proj, proj_stride, out, status, n);
     return (int)hipGetLastError();
+}
+
+namespace {
+template <int OUT> int launch_combine(int k, hipStream_t stream, const uint4* proj, u32 proj_stride, const u64* rows, u32 row_stride, const uint8_t* st_decode,
+                                      const u64* expect, u64* out, uint8_t* status, uint8_t* ok, u32 n) {
+    const unsigned grid = ((n + k - 1) / k + BLOCK - 1) / BLOCK;
+    if (k == 2) hipLaunchKernelGGL((combine_kernel<2, OUT>), dim3(grid), dim3(BLOCK), 0, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
+    else hipLaunchKernelGGL((combine_kernel<1, OUT>), dim3(grid), dim3(BLOCK), 0, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
+    return (int)hipGetLastError();
+}
+}  // namespace
+// [k]B + [l]P from the two halves' projective results (combine.hip.h).  k: elements per inversion (1 or 2); out_kind: CombineOut
+int chain_launch_combine(int k, int out_kind, hipStream_t stream, const uint4* proj, u32 proj_stride, const u64* rows, u32 row_stride, const uint8_t* st_decode,
+                         const u64* expect, u64* out, uint8_t* status, uint8_t* ok, u32 n) {
+    if (out_kind == COMBINE_AFFINE) return launch_combine<COMBINE_AFFINE>(k, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
+    if (out_kind == COMBINE_ENCODE) return launch_combine<COMBINE_ENCODE>(k, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
+    return launch_combine<COMBINE_VERIFY>(k, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
 }
 
 }  // namespace fq

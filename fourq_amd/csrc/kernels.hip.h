@@ -1283,6 +1283,11 @@ int chain_launch_prep(int algo, bool dh, unsigned grid, hipStream_t stream, cons
 int chain_setup_device();       // per-device function attributes (the comb's dynamic LDS); called by fourq_ctx_create
 int chain_launch_comb(unsigned grid, hipStream_t stream, const u64* scalars, const u32* comb_limbs, u64* out, uint8_t* status, uint4* proj, u32 proj_stride, u32 n);
 int chain_launch_normalize(int k, hipStream_t stream, const uint4* proj, u32 proj_stride, u64* out, uint8_t* status, u32 n);   // k in {1, 2, 4, 8}
+// combine.hip.h: [k]B + [l]P from the comb's planes and the ladder's rows; k in {1, 2}; out_kind: canonical affine words, 32-byte encoding + status,
+// or one byte "the encoding equals expect" + status
+enum CombineOut { COMBINE_AFFINE = 0, COMBINE_ENCODE = 1, COMBINE_VERIFY = 2 };
+int chain_launch_combine(int k, int out_kind, hipStream_t stream, const uint4* proj, u32 proj_stride, const u64* rows, u32 row_stride, const uint8_t* st_decode,
+                         const u64* expect, u64* out, uint8_t* status, uint8_t* ok, u32 n);
 // constant-time selection builds of the same kernels: fourq_ct_fused.hip (FQ_CHAIN=0) and fourq_ct_chain.hip (FQ_CHAIN=1)
 int ct_launch_fused(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);
 int ct_launch_pair(int algo, bool dh, bool fixed, bool quad, unsigned grid, hipStream_t stream, const LadderArgs& a);

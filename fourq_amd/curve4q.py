@@ -226,6 +226,21 @@ def _g_comb():
     return _g_comb_table
 
 
+# MUL_double needs the comb of G ITSELF, a second table beside the one of [392]G above.  A context keeps ONE comb staged, so the table
+# travels with every call and the library compares it with the staged one (103.5 KiB on the host, a few microseconds); a process that
+# alternates key generation and MUL_double pays one upload per switch.
+_g1_comb_table = None
+
+
+def _g1_comb():
+    global _g1_comb_table
+    if _g1_comb_table is None:
+        with _g_comb_lock:
+            if _g1_comb_table is None:
+                _g1_comb_table = default_engine().comb_table(codec.pack_point((Gx, Gy, (1, 0), Gx, Gy)))
+    return _g1_comb_table
+
+
 def _run_batch(kind, items):
     eng = default_engine()
     cols = [np.concatenate(c) if len(items) > 1 else c[0] for c in zip(*items)]
@@ -234,6 +249,9 @@ def _run_batch(kind, items):
         return [(out[i], int(status[i])) for i in range(len(items))]
     if kind[0] == "mul":
         out = (eng.mul_endo if kind[1] == "endo" else eng.mul_windowed)(*cols)
+        return [(out[i], None) for i in range(len(items))]
+    if kind[0] == "double":
+        out = eng.double_mul(cols[0], cols[1], cols[2], _g1_comb())
         return [(out[i], None) for i in range(len(items))]
     out, status = (eng.dh_endo if kind[1] == "endo" else eng.dh_windowed)(*cols)
     return [(out[i], int(status[i])) for i in range(len(items))]
@@ -278,6 +296,20 @@ def MUL_endo_batch(ms, Ps=None, table=None):
     eng = default_engine()
     out = eng.mul_endo_fixed(s, codec.pack_table(table)) if table else eng.mul_endo(s, codec.pack_points(Ps, 5))
     return codec.unpack_points(out)
+
+
+# ---- [k]G + [l]P: an ADDITION to the reference's names (it has no double-scalar function) ----------
+def MUL_double(k, l, P):
+    """Affine (x, y) of [k]G + [l]P for an affine P = (x, y): R1toAffine(ADD(MUL_endo(k, G), R1toR2(MUL_endo(l, AffineToR1(P))))), the
+    curve part of a Schnorr-type verification.  Not a reference name.  Checks nothing, like MUL_*; the neutral point is (0, 1)."""
+    (X, Y) = P
+    ks, ls = codec.pack_scalars([_check_endo_scalar(k)]), codec.pack_scalars([_check_endo_scalar(l)])
+    pts = codec.pack_point((X, Y)).reshape(1, 8)
+    if _COMBINE:
+        out, _ = _combined(("double", "endo"), ks, ls, pts)
+    else:
+        out = default_engine().double_mul(ks, ls, pts, _g1_comb())[0]
+    return codec.unpack_fp2s(out)
 
 
 # ---- Diffie-Hellman ----------------------------------------------------------------------------

@@ -325,6 +325,55 @@ class Engine:
         t = None if comb_host is None else _host(comb_host, None).ravel()
         self._ck(self._lib.fourq_dh_exchange_comb_batch_dev(self._ctx, _ptr(a_scalars), _ptr(b_scalars), _ptr(t), _ptr(out_affine), _ptr(status), n))
 
+    # ---- [k]B + [l]P and signature checks (fourq_double_mul_* / fourq_verify_bytes_*) ----------------
+    def _comb_arg(self, comb):
+        if comb is None:
+            return None
+        t = _host(comb, None).ravel()
+        if t.size != _lib.COMB_WORDS:
+            raise ValueError("a comb table is %d words" % _lib.COMB_WORDS)
+        return t
+
+    def double_mul(self, k_scalars, l_scalars, points_affine, comb=None, out=None):
+        """Canonical affine [k_i]B + [l_i]P_i, (n, 8) words: B the base of `comb` (comb_table(B), B of order N; None = the table
+        staged by comb_stage()), P_i affine.  Checks nothing, like MUL_*; the neutral point (0, 1) is an ordinary result."""
+        k, l, p = _host(k_scalars, 4), _host(l_scalars, 4), _host(points_affine, 8)
+        if not len(k) == len(l) == len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        out = _out(out, len(k), 8)
+        self._ck(self._lib.fourq_double_mul_affine_batch(self._ctx, _ptr(k), _ptr(self._comb_arg(comb)), _ptr(l), _ptr(p), _ptr(out), len(k)))
+        return out
+
+    def double_mul_bytes(self, k_scalars, l_scalars, points32, comb=None, out=None, status=None):
+        """encode([k_i]B + [l_i]decode(points32[i])): ((n, 32) bytes, status); status[i] = 0 or BYTES_DECODE_BASE + DECODE_*."""
+        k, l, p = _host(k_scalars, 4), _host(l_scalars, 4), _host(points32, 32, np.uint8)
+        if not len(k) == len(l) == len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        out, status = _out(out, len(k), 32, np.uint8), _out(status, len(k), None, np.uint8)
+        self._ck(self._lib.fourq_double_mul_bytes_batch(self._ctx, _ptr(k), _ptr(self._comb_arg(comb)), _ptr(l), _ptr(p), _ptr(out), _ptr(status), len(k)))
+        return out, status
+
+    def verify_bytes(self, k_scalars, l_scalars, keys32, expect32, comb=None, ok=None, status=None):
+        """The curve part of a Schnorr-type verification: ok[i] = 1 iff keys32[i] decodes and encode([k_i]B + [l_i]decode(keys32[i]))
+        equals expect32[i] byte for byte.  Returns (ok, status): status says why a 0 is a 0 (non-zero = the key did not decode).
+        For SchnorrQ: verify_bytes(s, h, A32, R32) with h = H(R, A, msg) hashed by the caller and `comb` the table of the generator."""
+        k, l = _host(k_scalars, 4), _host(l_scalars, 4)
+        a, e = _host(keys32, 32, np.uint8), _host(expect32, 32, np.uint8)
+        if not len(k) == len(l) == len(a) == len(e):
+            raise ValueError("the scalar, key and expectation arrays differ in length")
+        ok, status = _out(ok, len(k), None, np.uint8), _out(status, len(k), None, np.uint8)
+        self._ck(self._lib.fourq_verify_bytes_batch(self._ctx, _ptr(k), _ptr(self._comb_arg(comb)), _ptr(l), _ptr(a), _ptr(e), _ptr(ok), _ptr(status), len(k)))
+        return ok, status
+
+    def double_mul_dev(self, k_scalars, l_scalars, points_affine, out_affine, n, comb_host=None):
+        self._ck(self._lib.fourq_double_mul_affine_batch_dev(self._ctx, _ptr(k_scalars), _ptr(self._comb_arg(comb_host)), _ptr(l_scalars), _ptr(points_affine), _ptr(out_affine), n))
+
+    def double_mul_bytes_dev(self, k_scalars, l_scalars, points32, out32, status, n, comb_host=None):
+        self._ck(self._lib.fourq_double_mul_bytes_batch_dev(self._ctx, _ptr(k_scalars), _ptr(self._comb_arg(comb_host)), _ptr(l_scalars), _ptr(points32), _ptr(out32), _ptr(status), n))
+
+    def verify_bytes_dev(self, k_scalars, l_scalars, keys32, expect32, ok, status, n, comb_host=None):
+        self._ck(self._lib.fourq_verify_bytes_batch_dev(self._ctx, _ptr(k_scalars), _ptr(self._comb_arg(comb_host)), _ptr(l_scalars), _ptr(keys32), _ptr(expect32), _ptr(ok), _ptr(status), n))
+
     def dh_exchange_dev(self, a_scalars, b_scalars, base_affine_host, table392_host, out_affine, status, n):
         base = _host(base_affine_host, None).ravel()
         t = None if table392_host is None else _host(table392_host, None).ravel()

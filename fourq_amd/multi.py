@@ -168,6 +168,19 @@ class MultiEngine:
         return self._sharded(lambda e, s, o, st: e.comb_mul(s, comb, out=o, status=st), [s],
                              [_out(out, len(s), 8), _out(status, len(s), None, np.uint8)])
 
+    # ---- [k]B + [l]P and signature checks -------------------------------------------------------------------------
+    def double_mul(self, k_scalars, l_scalars, points_affine, comb, out=None):
+        k, l, p = _host(k_scalars, 4), _host(l_scalars, 4), _host(points_affine, 8)
+        self._same_len(k, l, p)
+        return self._sharded(lambda e, k, l, p, o: e.double_mul(k, l, p, comb, out=o), [k, l, p], [_out(out, len(k), 8)])
+
+    def verify_bytes(self, k_scalars, l_scalars, keys32, expect32, comb, ok=None, status=None):
+        k, l = _host(k_scalars, 4), _host(l_scalars, 4)
+        a, x = _host(keys32, 32, np.uint8), _host(expect32, 32, np.uint8)
+        self._same_len(k, l, a, x)
+        return self._sharded(lambda e, k, l, a, x, o, st: e.verify_bytes(k, l, a, x, comb, ok=o, status=st), [k, l, a, x],
+                             [_out(ok, len(k), None, np.uint8), _out(status, len(k), None, np.uint8)])
+
     # ---- wire format ----------------------------------------------------------------------------------------------
     def encode(self, points_affine, out=None):
         p = _host(points_affine, 8)

@@ -179,6 +179,30 @@ def run(loops=1000, dh_loops=10, seed=None, out=sys.stdout):
             rep.check(label, False)
         except Exception:
             rep.check(label, True)
+
+    # beyond the reference: [k]G + [l]P through the comb, the ladder and the combining kernel, against the group law
+    # [k]G + [l][t]G = [(k + l t) mod N]G, and the byte-level signature check on the same identities
+    import numpy as np
+    from . import codec
+    from .engine import default_engine
+    eng, bad = default_engine(), 0
+    rows = [(rng.getrandbits(256), rng.getrandbits(256), rng.getrandbits(256)) for _ in range(6)] + [(0, 0, 5), (7, 1, c.N - 7)]
+    keys, want = [], []
+    for k, l, t in rows:
+        Pt = c.R1toAffine(c.MUL_endo(t, G))
+        R = c.R1toAffine(c.MUL_endo((k + l * t) % c.N, G))
+        bad += c.MUL_double(k, l, Pt) != R
+        keys.append(bytes(c.encode(*Pt)))
+        want.append(bytes(c.encode(*R)))
+    as_rows = lambda bs: np.frombuffer(b"".join(bs), dtype=np.uint8).reshape(len(bs), 32)
+    ks, ls = codec.pack_scalars([r[0] for r in rows]), codec.pack_scalars([r[1] for r in rows])
+    ok, st = eng.verify_bytes(ks, ls, as_rows(keys), as_rows(want), comb=eng.comb_table(codec.pack_point(G)))
+    bad += int((ok != 1).sum()) + int(st.any())
+    spoiled = as_rows(want).copy()
+    spoiled[:, 3] ^= 4
+    ok, st = eng.verify_bytes(ks, ls, as_rows(keys), spoiled)
+    bad += int(ok.any())
+    rep.check("double-scalar / verify", bad == 0, bad)
     return rep.failed
 
 

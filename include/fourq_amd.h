@@ -303,6 +303,33 @@ int fourq_dh_exchange_comb_batch(fourq_ctx *ctx, const uint64_t *a_scalars, cons
 int fourq_dh_exchange_comb_batch_dev(fourq_ctx *ctx, const uint64_t *a_scalars, const uint64_t *b_scalars, const uint64_t *comb,
                                      uint64_t *out_affine, uint8_t *status, size_t n);
 
+/* ---- double-scalar multiplication [k]B + [l]P: the curve part of a Schnorr-type verification R' = [s]B + [h]A (SchnorrQ) ------
+ * The fixed half goes through the comb, the variable half through MUL_endo, and one kernel adds the two projective results with the
+ * complete twisted-Edwards addition and lowers the sum; neither half is normalised on its own and nothing but the result leaves the
+ * device.  Hashing (h = H(R, A, msg)) stays with the caller.  Scalars: any value in [0, 2^256), as MUL_endo and the comb take them.
+ * `comb` as in fourq_comb_mul_batch: the table of B from fourq_comb_table (B of order N), NULL = the staged comb.
+ *
+ * out_affine[i] = R1toAffine(ADD(MUL_endo(k_i, B), R1toR2(MUL_endo(l_i, AffineToR1(P_i)))))  canonical, n x 8 words.
+ * Checks nothing, like MUL_*; the neutral point is a result like any other ((0, 1): no status, nothing zeroed -- unlike
+ * fourq_comb_mul_batch).  For a P_i that is not on the curve the value is unspecified; the other elements are not affected. */
+int fourq_double_mul_affine_batch(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                                  const uint64_t *points_affine, uint64_t *out_affine, size_t n);
+int fourq_double_mul_affine_batch_dev(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                                      const uint64_t *points_affine, uint64_t *out_affine, size_t n);
+/* The same on 32-byte encodings: decode(points32[i]) in, encode(...) out.
+ * status[i]: 0 | FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_* (out32[i] is all zero then). */
+int fourq_double_mul_bytes_batch(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                                 const uint8_t *points32, uint8_t *out32, uint8_t *status, size_t n);
+int fourq_double_mul_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                                     const uint8_t *points32, uint8_t *out32, uint8_t *status, size_t n);
+/* ok[i] = 1 iff points32[i] decodes and encode([k_i]B + [l_i]decode(points32[i])) == expect32[i] byte for byte; else 0.
+ * status[i] as above (why a 0 is a 0: a key that does not decode, or a plain mismatch).  expect32 is compared as bytes: a
+ * non-canonical or reserved-bit encoding of the right point is a mismatch.  One byte + one status byte per element leave the device. */
+int fourq_verify_bytes_batch(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                             const uint8_t *points32, const uint8_t *expect32, uint8_t *ok, uint8_t *status, size_t n);
+int fourq_verify_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                                 const uint8_t *points32, const uint8_t *expect32, uint8_t *ok, uint8_t *status, size_t n);
+
 /* ---- primitives (one reference function per op, batched) --------------------------------------
  * Used by the Python mirror of the reference's helper API (GFp.*, GFp2.*, DBL, ADD, phi, ...) and by
  * the parity tests to check every layer of the path on the GPU.  in/out are HOST pointers;
