@@ -25,6 +25,7 @@ ABI_VERSION = 600                    # fourq_version(): 0.6.0 (round 6: fourq_di
 COMB_POINTS = 1024 + 80              # FOURQ_COMB_POINTS: the fast comb and the one the constant-time mode scans
 COMB_WORDS = COMB_POINTS * 12        # FOURQ_COMB_WORDS
 BYTES_DECODE_BASE = 16
+SIG_S_RANGE, SIG_MSG_CLAMPED, SIG_MAX_MSG = 32, 64, 1 << 20   # FOURQ_SIG_*
 
 
 class HostStats(ctypes.Structure):
@@ -109,6 +110,14 @@ PROTOTYPES = {
     "fourq_double_mul_bytes_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_verify_bytes_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_verify_bytes_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_sha512_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "fourq_sha512_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "fourq_sig_keygen_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_sig_keygen_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_sig_sign_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "fourq_sig_sign_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "fourq_sig_verify_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_sig_verify_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_encode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_decode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
@@ -124,7 +133,7 @@ PRIM = {
     "PT_DBL": 32, "PT_ADD": 33, "PT_ADD_CORE": 34, "PT_R1TOR2": 35, "PT_R1TOR3": 36, "PT_R2TOR4": 37,
     "PT_TAU": 38, "PT_TAU_DUAL": 39, "PT_UPSILON": 40, "PT_CHI": 41, "PT_PHI": 42, "PT_PSI": 43,
     "PT_ON_CURVE": 44, "PT_COFACTOR392": 45, "PT_R1TOAFFINE": 46,
-    "SC_DECOMPOSE": 64, "SC_RECODE": 65, "SC_WINDOWED": 66,
+    "SC_DECOMPOSE": 64, "SC_RECODE": 65, "SC_WINDOWED": 66, "SC_REDUCE512": 67, "SC_MULSUB": 68, "SC_MUL": 69,
 }
 
 

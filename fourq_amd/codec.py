@@ -142,3 +142,16 @@ def unpack_table(words):
 def scalars_from_bytes(raw):
     """n*32 random bytes -> (n, 4) uint64 scalars (uniform on [0, 2^256))."""
     return np.frombuffer(raw, dtype="<u8").reshape(-1, 4).copy()
+
+
+def pack_messages(messages):
+    """List of bytes-like messages -> ((n, stride) uint8 matrix, (n,) uint32 lengths): one message per row, zero-filled behind its end;
+    stride = the longest message rounded up to 16 bytes, so that every row starts 16-byte aligned and is read by vector loads."""
+    messages = [bytes(m) for m in messages]
+    longest = max((len(m) for m in messages), default=0)
+    stride = (longest + 15) // 16 * 16
+    matrix = np.zeros((len(messages), stride), dtype=np.uint8)
+    for i, m in enumerate(messages):
+        if m:
+            matrix[i, :len(m)] = np.frombuffer(m, dtype=np.uint8)
+    return matrix, np.array([len(m) for m in messages], dtype=np.uint32)

@@ -38,6 +38,7 @@
 #endif
 #include "kernels.hip.h"
 #include "pipeline_plan.h"
+#include "sig.hip.h"
 
 using namespace fq;
 
@@ -440,6 +441,7 @@ const PrimShape PRIMS[] = {
     { FOURQ_PT_UPSILON, 12, 12 }, { FOURQ_PT_CHI, 12, 12 }, { FOURQ_PT_PHI, 20, 20 }, { FOURQ_PT_PSI, 20, 20 },
     { FOURQ_PT_ON_CURVE, 8, 1 }, { FOURQ_PT_COFACTOR392, 8, 20 }, { FOURQ_PT_R1TOAFFINE, 20, 8 },
     { FOURQ_SC_DECOMPOSE, 4, 4 }, { FOURQ_SC_RECODE, 4, 5 }, { FOURQ_SC_WINDOWED, 4, 8 },
+    { FOURQ_SC_REDUCE512, 8, 4 }, { FOURQ_SC_MULSUB, 12, 4 }, { FOURQ_SC_MUL, 8, 4 },        // sig.hip.h (scalar_n.hip.h)
 };
 const PrimShape* find_prim(int op) {
     for (const PrimShape& p : PRIMS) if (p.op == op) return &p;
@@ -851,7 +853,11 @@ int ensure_work(fourq_ctx* c, size_t bytes) { return grow(c, &c->work, &c->work_
 size_t dh_bytes_work_bytes(size_t n) { return 2 * n * 64 + 2 * align256(n); }
 size_t exchange_work_bytes(size_t n) { return 2 * n * 64 + align256(n); }
 size_t mul_affine_work_bytes(size_t n) { return 2 * n * 160 + n * 64 + align256(n); }      // R1 in, R1 out, decoded points, decode status
-size_t double_mul_work_bytes(size_t n) { return 2 * n * 160 + 2 * align256(n); }             // lifted / decoded points, the ladder's rows, decode status, the comb's status
+size_t double_mul_rows_bytes(size_t n) { return 2 * n * 160 + 2 * align256(n); }             // lifted / decoded points, the ladder's rows, decode status, the comb's status
+// ... and behind them what fourq_sig_verify_batch_dev hands the double multiplication: s, h and R as 32-byte rows, one pre-status byte per row
+size_t double_mul_work_bytes(size_t n) { return double_mul_rows_bytes(n) + 3 * n * 32 + align256(n); }
+// keygen / sign: a = LE(k[0:32]), r, encode([r]G) as 32-byte rows, the comb's affine rows, its status
+size_t sig_work_bytes(size_t n) { return 3 * n * 32 + n * 64 + align256(n); }
 
 int ensure_ticks(fourq_ctx* c, size_t count) {
     while (c->ticks.size() < count) {
@@ -866,7 +872,8 @@ using ChunkLaunch = std::function<int(char* const* in_dev, char* const* out_dev,
 
 // Which call this is, for the measured planner inputs, and the guess of its kernel time per element for the context's first call of it
 enum PipeRouteId { PR_MUL_VAR = 0, PR_MUL_FIX = 2, PR_DH_VAR = 4, PR_DH_FIX = 6, PR_MIXED = 8, PR_COMB = 9, PR_ENCODE = 10, PR_DECODE = 11, PR_DHB_VAR = 12,
-                   PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25, PR_COUNT = 26 };       // + algo (0 / 1) where two follow each other
+                   PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25,
+                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_COUNT = 30 };       // + algo (0 / 1) where two follow each other
 struct PipeRoute { int id; double kt_guess; };
 constexpr double KT_CT_GUESS = 1.3;                 // constant-time selection: x 1.07 - 1.5 by route until the context has measured it
 using PipeReserve = std::function<int(size_t big)>; // sizes the context's intermediates for the largest chunk BEFORE the first chunk is enqueued
@@ -1392,6 +1399,7 @@ FQ_API int fourq_ctx_reserve(fourq_ctx* c, size_t n) {
     if (exchange_work_bytes(n) > need) need = exchange_work_bytes(n);
     if (mul_affine_work_bytes(n) > need) need = mul_affine_work_bytes(n);
     if (double_mul_work_bytes(n) > need) need = double_mul_work_bytes(n);
+    if (sig_work_bytes(n) > need) need = sig_work_bytes(n);
     return ensure_work(c, need);
 }
 FQ_API int fourq_ctx_lanes(const fourq_ctx* c, size_t* lanes) {
@@ -1983,6 +1991,169 @@ FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint6
     }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
 }
 
+// ---- signatures from bytes (include/fourq_amd.h): SHA-512 and the arithmetic modulo N on the device (sig.hip.h) around the comb, the
+// ladder and the combiner.  Every intermediate -- H(sk), the nonce, the challenge, s / h / R as rows -- lives in the context's work buffer.
+static bool sig_msgs_dev_ok(const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len) {
+    if (msg_len > 0xffffffffu || (!msgs && stride != 0)) return false;
+    return aligned16(msgs) && aligned16(lens);
+}
+// the host-pointer calls can look at the lengths: nothing above `stride` or FOURQ_SIG_MAX_MSG gets through
+static bool sig_msgs_host_ok(const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, size_t n) {
+    if (!msgs && stride != 0) return false;
+    if (!lens) return msg_len <= stride && msg_len <= FOURQ_SIG_MAX_MSG;
+    for (size_t i = 0; i < n; i++) if (lens[i] > stride || lens[i] > FOURQ_SIG_MAX_MSG) return false;
+    return true;
+}
+constexpr double KT_SHA_BLOCK = 0.05;             // one 128-byte block per element: ~5 000 VALU instructions, a first-call guess like the other KT_*
+// chunk of a host-pointer call that carries a message matrix: the route's own chunk, cut down (to no less than one block's worth of rows)
+// where rows of `stride` bytes would make a pipeline slot larger than 64 MiB
+static size_t sig_chunk(size_t chunk, size_t stride) {
+    const size_t cap = stride ? (size_t)(64u << 20) / stride : chunk;
+    if (cap < chunk) chunk = cap < (size_t)BLOCK ? (size_t)BLOCK : cap;
+    return chunk;
+}
+static double sig_kt_hash(size_t stride, int prefix_bytes) { return KT_SHA_BLOCK * (double)((stride + prefix_bytes + 17 + 127) / 128); }
+
+FQ_API int fourq_sha512_batch_dev(fourq_ctx* c, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* out64, size_t n) {
+    if (!c || !out64 || n > FOURQ_MAX_BATCH || !aligned16(out64) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    HIPRC_TRY(c, sig_launch_sha512(c->stream, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, out64, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_sig_keygen_batch_dev(fourq_ctx* c, const uint8_t* sk32, const uint64_t* comb, uint8_t* pk32, size_t n) {
+    if (!c || !sk32 || !pk32 || n > FOURQ_MAX_BATCH || !aligned16(sk32) || !aligned16(pk32)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = ensure_proj(c, n))) return rc;
+    if ((rc = ensure_work(c, sig_work_bytes(n)))) return rc;
+    uint64_t* a = (uint64_t*)c->work;
+    uint64_t* affine = (uint64_t*)(c->work + 3 * n * 32);
+    uint8_t* st_comb = (uint8_t*)(c->work + 3 * n * 32 + n * 64);
+    HIPRC_TRY(c, sig_launch_nonce(c->stream, false, sk32, SigMsgs{ nullptr, 0, nullptr, 0 }, a, nullptr, (u32)n));
+    // [a]G through the comb with deferred normalisation, as the first stage of double_mul_dev; the projective neutral would need a = 0 mod N
+    const size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
+    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;
+    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, a, c->comb_limbs, nullptr, st_comb, c->proj, (u32)c->proj_capacity, (u32)n));
+    const int group = normalize_group(c, n);
+    HIPRC_TRY(c, chain_launch_normalize(group ? group : 1, c->stream, c->proj, (u32)c->proj_capacity, affine, st_comb, (u32)n));
+    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, affine, (u64*)pk32, (u32)n);
+    HIP_TRY(c, hipGetLastError());
+    return FOURQ_OK;
+}
+FQ_API int fourq_sig_sign_batch_dev(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb,
+                                    const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* sig64, size_t n) {
+    if (!c || !sk32 || !pk32 || !sig64 || n > FOURQ_MAX_BATCH || !aligned16(sk32) || !aligned16(pk32) || !aligned16(sig64)) return FOURQ_ERR_INVALID;
+    if (!sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = ensure_proj(c, n))) return rc;
+    if ((rc = ensure_work(c, sig_work_bytes(n)))) return rc;
+    uint64_t* a = (uint64_t*)c->work;
+    uint64_t* r = (uint64_t*)(c->work + n * 32);
+    uint8_t* r32 = (uint8_t*)(c->work + 2 * n * 32);
+    uint64_t* affine = (uint64_t*)(c->work + 3 * n * 32);
+    uint8_t* st_comb = (uint8_t*)(c->work + 3 * n * 32 + n * 64);
+    const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
+    HIPRC_TRY(c, sig_launch_nonce(c->stream, true, sk32, m, a, r, (u32)n));
+    const size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
+    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;
+    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, r, c->comb_limbs, nullptr, st_comb, c->proj, (u32)c->proj_capacity, (u32)n));
+    const int group = normalize_group(c, n);
+    HIPRC_TRY(c, chain_launch_normalize(group ? group : 1, c->stream, c->proj, (u32)c->proj_capacity, affine, st_comb, (u32)n));
+    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, affine, (u64*)r32, (u32)n);
+    HIP_TRY(c, hipGetLastError());
+    HIPRC_TRY(c, sig_launch_finish(c->stream, r32, pk32, m, a, r, sig64, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                      const uint8_t* sig64, uint8_t* ok, uint8_t* status, size_t n) {
+    if (!c || !pk32 || !sig64 || !ok || !status || n > FOURQ_MAX_BATCH || !aligned16(pk32) || !aligned16(sig64)) return FOURQ_ERR_INVALID;
+    if (!sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = ensure_proj(c, n))) return rc;
+    if ((rc = ensure_work(c, double_mul_work_bytes(n)))) return rc;        // the same size double_mul_dev asks for: it will not move the buffer
+    char* base = c->work + double_mul_rows_bytes(n);
+    uint64_t* s = (uint64_t*)base;
+    uint64_t* h = (uint64_t*)(base + n * 32);
+    uint64_t* r32 = (uint64_t*)(base + 2 * n * 32);
+    uint8_t* pre = (uint8_t*)(base + 3 * n * 32);
+    HIPRC_TRY(c, sig_launch_challenge(c->stream, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, s, h, r32, pre, (u32)n));
+    if ((rc = double_mul_dev(c, s, nullptr, h, pk32, true, COMBINE_VERIFY, (const uint8_t*)r32, nullptr, status, ok, n))) return rc;
+    HIPRC_TRY(c, sig_launch_merge(c->stream, pre, ok, status, (u32)n));
+    return FOURQ_OK;
+}
+
+// host-pointer twins: a message matrix is one more array of `stride` bytes per element (left out when stride is 0), the lengths one of four
+FQ_API int fourq_sha512_batch(fourq_ctx* c, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* out64, size_t n) {
+    if (!c || !out64 || n > FOURQ_MAX_BATCH || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    PipeArray in[2];
+    int n_in = 0, i_msg = -1, i_len = -1;
+    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
+    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    PipeArray o[1] = { { nullptr, (char*)out64, 64 } };
+    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(4 * c->lanes_w4, stride), PipeRoute{ PR_SHA512, sig_kt_hash(stride, 0) }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_sha512_batch_dev(c, i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg], stride, i_len < 0 ? nullptr : (const uint32_t*)di[i_len], msg_len, (uint8_t*)dout[0], m);
+    });
+}
+static int sig_reserve(fourq_ctx* c, size_t big) {
+    if (int r = ensure_proj(c, big)) return r;
+    return ensure_work(c, sig_work_bytes(big));
+}
+FQ_API int fourq_sig_keygen_batch(fourq_ctx* c, const uint8_t* sk32, const uint64_t* comb, uint8_t* pk32, size_t n) {
+    if (!c || !sk32 || !pk32 || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;                            // compared once, not once per chunk
+    PipeArray in[1] = { { (const char*)sk32, nullptr, 32 } };
+    PipeArray o[1] = { { nullptr, (char*)pk32, 32 } };
+    return run_pipeline(c, in, 1, o, 1, n, c->lanes_w4, PipeRoute{ PR_SIG_KEYGEN, KT_COMB + KT_SHA_BLOCK + KT_ENCODE }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_sig_keygen_batch_dev(c, (const uint8_t*)di[0], nullptr, (uint8_t*)dout[0], m);
+    }, 0, [&](size_t big) { return sig_reserve(c, big); });
+}
+FQ_API int fourq_sig_sign_batch(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb,
+                                const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* sig64, size_t n) {
+    if (!c || !sk32 || !pk32 || !sig64 || n > FOURQ_MAX_BATCH || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;
+    PipeArray in[4] = { { (const char*)sk32, nullptr, 32 }, { (const char*)pk32, nullptr, 32 } };
+    int n_in = 2, i_msg = -1, i_len = -1;
+    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
+    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    PipeArray o[1] = { { nullptr, (char*)sig64, 64 } };
+    const double kt = KT_COMB + KT_ENCODE + KT_SHA_BLOCK + sig_kt_hash(stride, 32) + sig_kt_hash(stride, 64);
+    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(c->lanes_w4, stride), PipeRoute{ PR_SIG_SIGN, kt }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_sig_sign_batch_dev(c, (const uint8_t*)di[0], (const uint8_t*)di[1], nullptr, i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg], stride,
+                                        i_len < 0 ? nullptr : (const uint32_t*)di[i_len], msg_len, (uint8_t*)dout[0], m);
+    }, 0, [&](size_t big) { return sig_reserve(c, big); });
+}
+FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                  const uint8_t* sig64, uint8_t* ok, uint8_t* status, size_t n) {
+    if (!c || !pk32 || !sig64 || !ok || !status || n > FOURQ_MAX_BATCH || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;
+    PipeArray in[4] = { { (const char*)pk32, nullptr, 32 }, { (const char*)sig64, nullptr, 64 } };
+    int n_in = 2, i_msg = -1, i_len = -1;
+    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
+    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
+    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c, true), stride), PipeRoute{ PR_SIG_VERIFY, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_sig_verify_batch_dev(c, (const uint8_t*)di[0], nullptr, i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg], stride,
+                                          i_len < 0 ? nullptr : (const uint32_t*)di[i_len], msg_len, (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
+    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
+}
+
 // ---- pinned host memory and transfer statistics of the host-pointer calls ---------------------------------------
 FQ_API int fourq_host_alloc(fourq_ctx* c, size_t bytes, void** out) {
     if (!c || !out) return FOURQ_ERR_INVALID;
@@ -2154,9 +2325,13 @@ FQ_API int fourq_prim_batch(fourq_ctx* c, int op, const uint64_t* in, uint64_t* 
     if (rc) return rc;
     char* base = (char*)c->stage;
     HIP_TRY(c, hipMemcpyAsync(base, in, ib, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(prim_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, op, (const u64*)base, (u64*)(base + ib),
-                       (u32)n, (u32)p->in_words, (u32)p->out_words);
-    HIP_TRY(c, hipGetLastError());
+    if (op == FOURQ_SC_REDUCE512 || op == FOURQ_SC_MULSUB || op == FOURQ_SC_MUL) {
+        HIPRC_TRY(c, sig_launch_scalar_prim(c->stream, op, (const uint64_t*)base, (uint64_t*)(base + ib), (u32)n));
+    } else {
+        hipLaunchKernelGGL(prim_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, op, (const u64*)base, (u64*)(base + ib),
+                           (u32)n, (u32)p->in_words, (u32)p->out_words);
+        HIP_TRY(c, hipGetLastError());
+    }
     HIP_TRY(c, hipMemcpyAsync(out, base + ib, ob, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FOURQ_OK;

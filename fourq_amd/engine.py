@@ -374,6 +374,74 @@ class Engine:
     def verify_bytes_dev(self, k_scalars, l_scalars, keys32, expect32, ok, status, n, comb_host=None):
         self._ck(self._lib.fourq_verify_bytes_batch_dev(self._ctx, _ptr(k_scalars), _ptr(self._comb_arg(comb_host)), _ptr(l_scalars), _ptr(keys32), _ptr(expect32), _ptr(ok), _ptr(status), n))
 
+    # ---- signatures from bytes (fourq_sha512_* / fourq_sig_*): SHA-512 and the arithmetic modulo N run on the device -------------
+    @staticmethod
+    def _msgs(msgs, lens, n=None):
+        """(matrix, stride, lens or None, msg_len): `msgs` a 2-D uint8 array, one message per row (row stride = its second dimension);
+        `lens` the rows' lengths, or None = every row is used whole."""
+        m = np.ascontiguousarray(msgs, dtype=np.uint8)
+        if m.ndim != 2:
+            raise ValueError("msgs must be a 2-D uint8 array, one message per row (codec.pack_messages makes one)")
+        if n is not None and len(m) != n:
+            raise ValueError("the message matrix and the other arrays differ in length")
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, dtype=np.uint32).ravel()
+            if len(lens) != len(m):
+                raise ValueError("lens must have one entry per message")
+        return m, m.shape[1], lens, m.shape[1]
+
+    def sha512(self, msgs, lens=None, out=None):
+        """SHA-512 of every row of `msgs` (its first lens[i] bytes): (n, 64) uint8."""
+        m, stride, lens, msg_len = self._msgs(msgs, lens)
+        out = _out(out, len(m), 64, np.uint8)
+        self._ck(self._lib.fourq_sha512_batch(self._ctx, _ptr(m) if stride else None, stride, _ptr(lens), msg_len, _ptr(out), len(m)))
+        return out
+
+    def sha512_dev(self, msgs, stride, lens, msg_len, out64, n):
+        self._ck(self._lib.fourq_sha512_batch_dev(self._ctx, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(out64), n))
+
+    def sig_keygen(self, sk32, comb=None, out=None):
+        """Public keys encode([LE(SHA-512(sk)[0:32])]G), (n, 32) uint8, from (n, 32) secret keys.  `comb`: the comb of the generator
+        (comb_table(AffineToR1(Gx, Gy))) or None = the table staged by comb_stage()."""
+        sk = _host(sk32, 32, np.uint8)
+        out = _out(out, len(sk), 32, np.uint8)
+        self._ck(self._lib.fourq_sig_keygen_batch(self._ctx, _ptr(sk), _ptr(self._comb_arg(comb)), _ptr(out), len(sk)))
+        return out
+
+    def sig_keygen_dev(self, sk32, pk32, n, comb_host=None):
+        self._ck(self._lib.fourq_sig_keygen_batch_dev(self._ctx, _ptr(sk32), _ptr(self._comb_arg(comb_host)), _ptr(pk32), n))
+
+    def sig_sign(self, sk32, pk32, msgs, lens=None, comb=None, out=None):
+        """Signatures R || s, (n, 64) uint8 (the scheme: include/fourq_amd.h).  pk32 is an input; it is not checked against sk32."""
+        sk, pk = _host(sk32, 32, np.uint8), _host(pk32, 32, np.uint8)
+        if len(sk) != len(pk):
+            raise ValueError("the secret and public key arrays differ in length")
+        m, stride, lens, msg_len = self._msgs(msgs, lens, len(sk))
+        out = _out(out, len(sk), 64, np.uint8)
+        self._ck(self._lib.fourq_sig_sign_batch(self._ctx, _ptr(sk), _ptr(pk), _ptr(self._comb_arg(comb)), _ptr(m) if stride else None, stride, _ptr(lens), msg_len,
+                                                _ptr(out), len(sk)))
+        return out
+
+    def sig_sign_dev(self, sk32, pk32, msgs, stride, lens, msg_len, sig64, n, comb_host=None):
+        self._ck(self._lib.fourq_sig_sign_batch_dev(self._ctx, _ptr(sk32), _ptr(pk32), _ptr(self._comb_arg(comb_host)), _ptr(msgs), stride, _ptr(lens), msg_len,
+                                                    _ptr(sig64), n))
+
+    def sig_verify(self, pk32, msgs, sig64, lens=None, comb=None, ok=None, status=None):
+        """(ok, status) per row: ok[i] = 1 iff sig64[i] is a valid signature of msgs[i] under pk32[i].  status says why a 0 is a 0:
+        0 = plain mismatch, _lib.SIG_S_RANGE = s >= N, _lib.BYTES_DECODE_BASE + DECODE_* = the key does not decode."""
+        pk, sig = _host(pk32, 32, np.uint8), _host(sig64, 64, np.uint8)
+        if len(pk) != len(sig):
+            raise ValueError("the key and signature arrays differ in length")
+        m, stride, lens, msg_len = self._msgs(msgs, lens, len(pk))
+        ok, status = _out(ok, len(pk), None, np.uint8), _out(status, len(pk), None, np.uint8)
+        self._ck(self._lib.fourq_sig_verify_batch(self._ctx, _ptr(pk), _ptr(self._comb_arg(comb)), _ptr(m) if stride else None, stride, _ptr(lens), msg_len,
+                                                  _ptr(sig), _ptr(ok), _ptr(status), len(pk)))
+        return ok, status
+
+    def sig_verify_dev(self, pk32, msgs, stride, lens, msg_len, sig64, ok, status, n, comb_host=None):
+        self._ck(self._lib.fourq_sig_verify_batch_dev(self._ctx, _ptr(pk32), _ptr(self._comb_arg(comb_host)), _ptr(msgs), stride, _ptr(lens), msg_len,
+                                                      _ptr(sig64), _ptr(ok), _ptr(status), n))
+
     def dh_exchange_dev(self, a_scalars, b_scalars, base_affine_host, table392_host, out_affine, status, n):
         base = _host(base_affine_host, None).ravel()
         t = None if table392_host is None else _host(table392_host, None).ravel()

@@ -181,6 +181,19 @@ class MultiEngine:
         return self._sharded(lambda e, k, l, a, x, o, st: e.verify_bytes(k, l, a, x, comb, ok=o, status=st), [k, l, a, x],
                              [_out(ok, len(k), None, np.uint8), _out(status, len(k), None, np.uint8)])
 
+    def sig_sign(self, sk32, pk32, msgs, lens=None, comb=None, out=None):
+        sk, pk, m = _host(sk32, 32, np.uint8), _host(pk32, 32, np.uint8), np.ascontiguousarray(msgs, dtype=np.uint8)
+        ln = np.full(len(m), m.shape[1], dtype=np.uint32) if lens is None else np.ascontiguousarray(lens, dtype=np.uint32).ravel()
+        self._same_len(sk, pk, m, ln)
+        return self._sharded(lambda e, sk, pk, m, ln, o: e.sig_sign(sk, pk, m, ln, comb, out=o), [sk, pk, m, ln], [_out(out, len(sk), 64, np.uint8)])
+
+    def sig_verify(self, pk32, msgs, sig64, lens=None, comb=None, ok=None, status=None):
+        pk, sig, m = _host(pk32, 32, np.uint8), _host(sig64, 64, np.uint8), np.ascontiguousarray(msgs, dtype=np.uint8)
+        ln = np.full(len(m), m.shape[1], dtype=np.uint32) if lens is None else np.ascontiguousarray(lens, dtype=np.uint32).ravel()
+        self._same_len(pk, sig, m, ln)
+        return self._sharded(lambda e, pk, m, sig, ln, o, st: e.sig_verify(pk, m, sig, ln, comb, ok=o, status=st), [pk, m, sig, ln],
+                             [_out(ok, len(pk), None, np.uint8), _out(status, len(pk), None, np.uint8)])
+
     # ---- wire format ----------------------------------------------------------------------------------------------
     def encode(self, points_affine, out=None):
         p = _host(points_affine, 8)

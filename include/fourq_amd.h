@@ -306,7 +306,8 @@ int fourq_dh_exchange_comb_batch_dev(fourq_ctx *ctx, const uint64_t *a_scalars, 
 /* ---- double-scalar multiplication [k]B + [l]P: the curve part of a Schnorr-type verification R' = [s]B + [h]A (SchnorrQ) ------
  * The fixed half goes through the comb, the variable half through MUL_endo, and one kernel adds the two projective results with the
  * complete twisted-Edwards addition and lowers the sum; neither half is normalised on its own and nothing but the result leaves the
- * device.  Hashing (h = H(R, A, msg)) stays with the caller.  Scalars: any value in [0, 2^256), as MUL_endo and the comb take them.
+ * device.  This is the scalar-level call for a caller with a hash of its own (h = H(R, A, msg) computed elsewhere); with SHA-512 the
+ * fourq_sig_* calls below take the bytes and hash on the device.  Scalars: any value in [0, 2^256), as MUL_endo and the comb take them.
  * `comb` as in fourq_comb_mul_batch: the table of B from fourq_comb_table (B of order N), NULL = the staged comb.
  *
  * out_affine[i] = R1toAffine(ADD(MUL_endo(k_i, B), R1toR2(MUL_endo(l_i, AffineToR1(P_i)))))  canonical, n x 8 words.
@@ -329,6 +330,47 @@ int fourq_verify_bytes_batch(fourq_ctx *ctx, const uint64_t *k_scalars, const ui
                              const uint8_t *points32, const uint8_t *expect32, uint8_t *ok, uint8_t *status, size_t n);
 int fourq_verify_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
                                  const uint8_t *points32, const uint8_t *expect32, uint8_t *ok, uint8_t *status, size_t n);
+
+/* ---- signatures from bytes: SchnorrQ-shaped sign / verify with SHA-512 and the arithmetic modulo N on the device ---------------------
+ * Nothing but byte arrays crosses the ABI -- secret keys, public keys, messages, signatures, one ok and one status byte per row -- and no
+ * intermediate (the hash of the secret key, the nonce, the challenge, R as a point) is ever on the host.  With H = SHA-512, LE(x) the
+ * little-endian integer of a byte string, G the generator (`comb` = fourq_comb_table of AffineToR1(Gx, Gy), or NULL = the staged comb):
+ *   keygen(sk)           k = H(sk);  pk = encode([LE(k[0:32])]G)           (the 256-bit value is used unreduced, as MUL_endo takes it)
+ *   sign(sk, pk, msg)    k = H(sk);  r = LE(H(k[32:64] || msg)) mod N;  R = encode([r]G);  h = LE(H(R || pk || msg)) mod N;
+ *                        s = (r - LE(k[0:32]) h) mod N;  sig = R || s (s: 32 bytes little-endian).  pk is an input: it is neither
+ *                        derived again nor checked against sk.
+ *   verify(pk, msg, sig) ok = 0 with status FOURQ_SIG_S_RANGE when LE(sig[32:64]) >= N; ok = 0 with FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_*
+ *                        when pk does not decode (takes precedence); otherwise ok = (encode([s]G + [h]decode(pk)) == sig[0:32]) byte for
+ *                        byte -- fourq_verify_bytes_batch with k = s, l = h -- so a non-canonical R is a plain mismatch (ok 0, status 0).
+ * This is the structure of SchnorrQ (Costello, Longa: "SchnorrQ: Schnorr signatures on FourQ"); byte-for-byte interoperability with
+ * FourQlib's schnorrq.c is NOT claimed (no vectors of it were available to check against), and s < N is deliberately stricter than a
+ * bit-length check: it is what rules out a second encoding (s + N still fits 32 bytes) of the same signature.
+ * Messages: n rows of `stride` bytes (stride >= the longest row; 0 only when every length is 0, msgs may then be NULL); lens: n x uint32,
+ * or NULL = every row is msg_len bytes.  A row is never read at or past its length.  The host-pointer calls return FOURQ_ERR_INVALID for a
+ * length above `stride` or above FOURQ_SIG_MAX_MSG.  The _dev calls cannot look: they CLAMP a row's length to `stride`;
+ * fourq_sig_verify_batch_dev reports such a row as ok = 0, status FOURQ_SIG_MSG_CLAMPED (unless the key does not decode), while
+ * fourq_sha512_batch_dev and fourq_sig_sign_batch_dev, which have no status, hash the clamped row.  _dev base pointers are 16-byte
+ * aligned (msgs and lens included), `stride` is arbitrary: rows that start 8- or 16-byte aligned are read by vector loads, others by bytes.
+ * The secret scalar and the nonce meet no branch and no address that depends on their value, in both table-selection modes of the comb
+ * only when fourq_ctx_set_ct_select is on (the comb's digits are addresses otherwise, as everywhere in this library). */
+#define FOURQ_SIG_S_RANGE 32          /* status: LE(sig[32:64]) >= N */
+#define FOURQ_SIG_MSG_CLAMPED 64      /* status of the _dev verify: the row's length exceeded `stride` and was clamped */
+#define FOURQ_SIG_MAX_MSG (1u << 20)  /* per-row message bytes the host-pointer calls accept */
+/* out64[i] = SHA-512(msgs[i][0 : len_i]) */
+int fourq_sha512_batch(fourq_ctx *ctx, const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *out64, size_t n);
+int fourq_sha512_batch_dev(fourq_ctx *ctx, const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *out64, size_t n);
+int fourq_sig_keygen_batch(fourq_ctx *ctx, const uint8_t *sk32, const uint64_t *comb, uint8_t *pk32, size_t n);
+int fourq_sig_keygen_batch_dev(fourq_ctx *ctx, const uint8_t *sk32, const uint64_t *comb, uint8_t *pk32, size_t n);
+int fourq_sig_sign_batch(fourq_ctx *ctx, const uint8_t *sk32, const uint8_t *pk32, const uint64_t *comb,
+                         const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *sig64, size_t n);
+int fourq_sig_sign_batch_dev(fourq_ctx *ctx, const uint8_t *sk32, const uint8_t *pk32, const uint64_t *comb,
+                             const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *sig64, size_t n);
+int fourq_sig_verify_batch(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb,
+                           const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                           const uint8_t *sig64, uint8_t *ok, uint8_t *status, size_t n);
+int fourq_sig_verify_batch_dev(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb,
+                               const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                               const uint8_t *sig64, uint8_t *ok, uint8_t *status, size_t n);
 
 /* ---- primitives (one reference function per op, batched) --------------------------------------
  * Used by the Python mirror of the reference's helper API (GFp.*, GFp2.*, DBL, ADD, phi, ...) and by
@@ -364,7 +406,11 @@ enum fourq_prim {
     /* curve4q.py:216-226, :339-380 */
     FOURQ_SC_DECOMPOSE = 64,    /* m[4] -> a1..a4 [4] */
     FOURQ_SC_RECODE = 65,       /* v[4] = decompose(m) -> [5]: sign bits 0..63, digit bit-planes 0,1,2, digit 64 */
-    FOURQ_SC_WINDOWED = 66      /* m[4] -> [8]: 63 bytes, byte i = (sgn[i] << 3) | ind[i] */
+    FOURQ_SC_WINDOWED = 66,     /* m[4] -> [8]: 63 bytes, byte i = (sgn[i] << 3) | ind[i] */
+    /* arithmetic modulo N (scalar_n.hip.h): inputs ANY value of their width, outputs canonical in [0, N) */
+    FOURQ_SC_REDUCE512 = 67,    /* x[8] -> [4]: x mod N */
+    FOURQ_SC_MULSUB = 68,       /* r[4] a[4] h[4] -> [4]: (r - a h) mod N */
+    FOURQ_SC_MUL = 69           /* a[4] b[4] -> [4]: a b mod N */
 };
 int fourq_prim_words(int op, size_t *in_words, size_t *out_words);
 int fourq_prim_batch(fourq_ctx *ctx, int op, const uint64_t *in, uint64_t *out, size_t n);
