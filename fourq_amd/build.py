@@ -24,7 +24,7 @@ RESOURCES_PATH = os.path.join(HERE, "kernel_resources.json")
 PLACEMENT_PATH = os.path.join(HERE, "code_placement.json")
 # four translation units: FQ_CHAIN=0 / 1 (kernels.hip.h), and the constant-time-selection builds of both flavours
 SOURCES = ["fourq_amd.hip", "fourq_chain.hip", "fourq_ct_fused.hip", "fourq_ct_chain.hip"]
-HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "kernels.hip.h", "combine.hip.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
+HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "kernels.hip.h", "combine.hip.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", "h2c.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Rpass-analysis=kernel-resource-usage"]
 # Code placement (tools/asmgen/place_asm.py, profiles/r04_ladder_step.txt): the device code of every translation unit goes through
 # assembly text, where every 8-byte instruction is put on an 8-byte boundary (an _e32 instruction in front of it re-encoded as _e64),
@@ -55,6 +55,10 @@ RESOURCE_POLICY = [
      "the hashing kernels hold 40 live 64-bit values: state, schedule, working variables, prefix -- nothing of it may spill"),
     (r"\b(sha512_kernel|sig_challenge_kernel|sig_nonce_kernel<\w+>|sig_finish_kernel)\(", "occupancy", lambda v: v >= 4,
      "the hashing kernels are throughput code held to 128 VGPRs: four waves per SIMD"),
+    (r"\b(h2f_kernel|ell2_kernel)<", "scratch", lambda v: v == 0, "hash to curve: neither the hashing nor the map may spill (DST_prime is read from the kernel arguments, not copied)"),
+    (r"\bh2f_kernel<1>", "occupancy", lambda v: v >= 4, "hash_to_field for one element is a hashing kernel like the signature layer's: four waves per SIMD"),
+    (r"\bh2f_kernel<2>", "occupancy", lambda v: v >= 3, "hash_to_field for two elements keeps b_0 live across b_1: 48 64-bit values, three waves per SIMD"),
+    (r"\bell2_kernel<", "occupancy", lambda v: v >= 2, "the map runs the generated GF(p^2) bodies, whose temporaries are fixed high registers: two waves per SIMD"),
 ]
 
 

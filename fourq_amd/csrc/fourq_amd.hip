@@ -39,6 +39,7 @@
 #include "kernels.hip.h"
 #include "pipeline_plan.h"
 #include "sig.hip.h"
+#include "h2c.hip.h"
 
 using namespace fq;
 
@@ -440,6 +441,7 @@ const PrimShape PRIMS[] = {
     { FOURQ_PT_R1TOR3, 20, 16 }, { FOURQ_PT_R2TOR4, 16, 12 }, { FOURQ_PT_TAU, 12, 12 }, { FOURQ_PT_TAU_DUAL, 12, 20 },
     { FOURQ_PT_UPSILON, 12, 12 }, { FOURQ_PT_CHI, 12, 12 }, { FOURQ_PT_PHI, 20, 20 }, { FOURQ_PT_PSI, 20, 20 },
     { FOURQ_PT_ON_CURVE, 8, 1 }, { FOURQ_PT_COFACTOR392, 8, 20 }, { FOURQ_PT_R1TOAFFINE, 20, 8 },
+    { FOURQ_PT_MAP_ELL2, 4, 8 },                                                             // h2c.hip.h
     { FOURQ_SC_DECOMPOSE, 4, 4 }, { FOURQ_SC_RECODE, 4, 5 }, { FOURQ_SC_WINDOWED, 4, 8 },
     { FOURQ_SC_REDUCE512, 8, 4 }, { FOURQ_SC_MULSUB, 12, 4 }, { FOURQ_SC_MUL, 8, 4 },        // sig.hip.h (scalar_n.hip.h)
 };
@@ -502,7 +504,7 @@ struct fourq_ctx {
     // Measured planner inputs (round 6): every multi-chunk host-array call times ONE middle chunk (six events, `probe_ticks`) and leaves the
     // kernel time per element of its route -- per selection mode -- and the link's rate each way here; the next call of that route is planned
     // with them.  0 = not measured yet: the first call plans with the KT_* guesses (x KT_CT_GUESS in constant-time mode) and 48 GB/s.
-    double plan_kt[32][2] = {};
+    double plan_kt[40][2] = {};
     double plan_link_in = 0, plan_link_out = 0;     // bytes per nanosecond
     hipEvent_t probe_ticks[6] = {};
     bool fused_io = true;          // FOURQ_FUSED_IO=0 (test hook): the affine / encoded flavours of MUL_* always through lift + full R1 rows, as round 5
@@ -858,6 +860,8 @@ size_t double_mul_rows_bytes(size_t n) { return 2 * n * 160 + 2 * align256(n); }
 size_t double_mul_work_bytes(size_t n) { return double_mul_rows_bytes(n) + 3 * n * 32 + align256(n); }
 // keygen / sign: a = LE(k[0:32]), r, encode([r]G) as 32-byte rows, the comb's affine rows, its status
 size_t sig_work_bytes(size_t n) { return 3 * n * 32 + n * 64 + align256(n); }
+// hash to curve: u_0, u_1 as 32-byte rows
+size_t h2c_work_bytes(size_t n) { return 2 * n * 32; }
 
 int ensure_ticks(fourq_ctx* c, size_t count) {
     while (c->ticks.size() < count) {
@@ -873,7 +877,7 @@ using ChunkLaunch = std::function<int(char* const* in_dev, char* const* out_dev,
 // Which call this is, for the measured planner inputs, and the guess of its kernel time per element for the context's first call of it
 enum PipeRouteId { PR_MUL_VAR = 0, PR_MUL_FIX = 2, PR_DH_VAR = 4, PR_DH_FIX = 6, PR_MIXED = 8, PR_COMB = 9, PR_ENCODE = 10, PR_DECODE = 11, PR_DHB_VAR = 12,
                    PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25,
-                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_COUNT = 30 };       // + algo (0 / 1) where two follow each other
+                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_H2F = 30, PR_H2C_MAP = 31, PR_H2C = 32, PR_H2C_AFFINE = 34, PR_COUNT = 36 };       // + algo (0 / 1) where two follow each other
 struct PipeRoute { int id; double kt_guess; };
 constexpr double KT_CT_GUESS = 1.3;                 // constant-time selection: x 1.07 - 1.5 by route until the context has measured it
 using PipeReserve = std::function<int(size_t big)>; // sizes the context's intermediates for the largest chunk BEFORE the first chunk is enqueued
@@ -894,7 +898,7 @@ int run_pipeline(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* o
     return rc;
 }
 int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch, size_t chunk_bounce, const PipeReserve& reserve) {
-    if (n_in > PIPE_MAX_ARRAYS || n_out > PIPE_MAX_ARRAYS || chunk == 0 || route.id < 0 || route.id >= 32) return FOURQ_ERR_INVALID;
+    if (n_in > PIPE_MAX_ARRAYS || n_out > PIPE_MAX_ARRAYS || chunk == 0 || route.id < 0 || route.id >= 40) return FOURQ_ERR_INVALID;
     bool is_pin_in[PIPE_MAX_ARRAYS], is_pin_out[PIPE_MAX_ARRAYS], any_pageable = false;
     for (int i = 0; i < n_in; i++) { is_pin_in[i] = is_pinned(in[i].src); any_pageable |= !is_pin_in[i]; }
     for (int i = 0; i < n_out; i++) { is_pin_out[i] = is_pinned(out[i].dst); any_pageable |= !is_pin_out[i]; }
@@ -1400,6 +1404,7 @@ FQ_API int fourq_ctx_reserve(fourq_ctx* c, size_t n) {
     if (mul_affine_work_bytes(n) > need) need = mul_affine_work_bytes(n);
     if (double_mul_work_bytes(n) > need) need = double_mul_work_bytes(n);
     if (sig_work_bytes(n) > need) need = sig_work_bytes(n);
+    if (h2c_work_bytes(n) > need) need = h2c_work_bytes(n);
     return ensure_work(c, need);
 }
 FQ_API int fourq_ctx_lanes(const fourq_ctx* c, size_t* lanes) {
@@ -2154,6 +2159,95 @@ FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint6
     }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
 }
 
+// ---- bytes to a point (include/fourq_amd.h, "hash to curve"): expand_message_xmd + hash_to_field in one kernel, the map, the addition, the
+// x392 chain and the lowering in a second (h2c.hip.h).  The only intermediate is u: n x count rows of 32 bytes in the context's work buffer.
+// DST_prime travels in the kernel arguments, so nothing is staged and every _dev call below only enqueues once the work buffer is sized.
+static bool h2c_args_ok(const uint8_t* dst, size_t dst_len, int mode) {
+    return dst && dst_len >= 1 && dst_len <= FOURQ_H2C_MAX_DST && (mode == FOURQ_H2C_RO || mode == FOURQ_H2C_NU);
+}
+constexpr double KT_ELL2 = 0.20;                  // one map: four GF(p) exponentiations' worth, a first-call guess like the other KT_*
+static double h2c_kt_hash(size_t stride, size_t dst_len, int count) {
+    return KT_SHA_BLOCK * (double)((stride + dst_len + 4 + 17 + 127) / 128 + count * ((64 + dst_len + 2 + 17 + 127) / 128));
+}
+FQ_API int fourq_hash_to_field_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                         uint64_t* out_u, size_t n) {
+    if (!c || !out_u || n > FOURQ_MAX_BATCH || !aligned16(out_u) || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    const int count = mode == FOURQ_H2C_RO ? 2 : 1;
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), out_u, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_map_to_curve_batch_dev(fourq_ctx* c, const uint64_t* u, uint64_t* out_affine, size_t n) {
+    if (!c || !u || !out_affine || n > FOURQ_MAX_BATCH || !aligned16(u) || !aligned16(out_affine)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 1, H2C_OUT_MAP, u, out_affine, (u32)n));
+    return FOURQ_OK;
+}
+static int hash_to_curve_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                             int out_kind, void* out, size_t n) {
+    if (!c || !out || n > FOURQ_MAX_BATCH || !aligned16(out) || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = ensure_work(c, h2c_work_bytes(n))) return rc;
+    const int count = mode == FOURQ_H2C_RO ? 2 : 1;
+    uint64_t* u = (uint64_t*)c->work;
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, count, out_kind, u, (uint64_t*)out, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_hash_to_curve_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                         uint8_t* out32, size_t n) {
+    return hash_to_curve_dev(c, dst, dst_len, mode, msgs, stride, lens, msg_len, H2C_OUT_BYTES, out32, n);
+}
+FQ_API int fourq_hash_to_curve_affine_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                                uint64_t* out_affine, size_t n) {
+    return hash_to_curve_dev(c, dst, dst_len, mode, msgs, stride, lens, msg_len, H2C_OUT_AFFINE, out_affine, n);
+}
+// host-pointer twins; what = 0: hash_to_field (out: count x 32 bytes per row), 1: 32-byte points, 2: affine words
+static int h2c_host(fourq_ctx* c, int what, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, void* out, size_t n) {
+    if (!c || !out || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    const int count = mode == FOURQ_H2C_RO ? 2 : 1;
+    PipeArray in[2];
+    int n_in = 0, i_msg = -1, i_len = -1;
+    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
+    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    PipeArray o[1] = { { nullptr, (char*)out, what == 0 ? (size_t)32 * count : what == 1 ? (size_t)32 : (size_t)64 } };
+    const double kt = h2c_kt_hash(stride, dst_len, count) + (what == 0 ? 0.0 : count * KT_ELL2 + KT_LIFT_LOWER);
+    const PipeRoute route{ what == 0 ? PR_H2F : (what == 1 ? PR_H2C : PR_H2C_AFFINE) + mode, kt };
+    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(what == 0 ? 4 * c->lanes_w4 : pipe_chunk(c, true), stride), route, [&](char* const* di, char* const* dout, size_t m) {
+        const uint8_t* dm = i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg];
+        const uint32_t* dl = i_len < 0 ? nullptr : (const uint32_t*)di[i_len];
+        if (what == 0) return fourq_hash_to_field_batch_dev(c, dst, dst_len, mode, dm, stride, dl, msg_len, (uint64_t*)dout[0], m);
+        return hash_to_curve_dev(c, dst, dst_len, mode, dm, stride, dl, msg_len, what == 1 ? H2C_OUT_BYTES : H2C_OUT_AFFINE, dout[0], m);
+    }, 0, [&](size_t big) { return what == 0 ? FOURQ_OK : ensure_work(c, h2c_work_bytes(big)); });
+}
+FQ_API int fourq_hash_to_field_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                     uint64_t* out_u, size_t n) {
+    return h2c_host(c, 0, dst, dst_len, mode, msgs, stride, lens, msg_len, out_u, n);
+}
+FQ_API int fourq_hash_to_curve_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                     uint8_t* out32, size_t n) {
+    return h2c_host(c, 1, dst, dst_len, mode, msgs, stride, lens, msg_len, out32, n);
+}
+FQ_API int fourq_hash_to_curve_affine_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                            uint64_t* out_affine, size_t n) {
+    return h2c_host(c, 2, dst, dst_len, mode, msgs, stride, lens, msg_len, out_affine, n);
+}
+FQ_API int fourq_map_to_curve_batch(fourq_ctx* c, const uint64_t* u, uint64_t* out_affine, size_t n) {
+    if (!c || !u || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    PipeArray in[1] = { { (const char*)u, nullptr, 32 } };
+    PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
+    return run_pipeline(c, in, 1, o, 1, n, pipe_chunk(c, true), PipeRoute{ PR_H2C_MAP, KT_ELL2 + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_map_to_curve_batch_dev(c, (const uint64_t*)di[0], (uint64_t*)dout[0], m);
+    });
+}
+
 // ---- pinned host memory and transfer statistics of the host-pointer calls ---------------------------------------
 FQ_API int fourq_host_alloc(fourq_ctx* c, size_t bytes, void** out) {
     if (!c || !out) return FOURQ_ERR_INVALID;
@@ -2327,6 +2421,8 @@ FQ_API int fourq_prim_batch(fourq_ctx* c, int op, const uint64_t* in, uint64_t* 
     HIP_TRY(c, hipMemcpyAsync(base, in, ib, hipMemcpyHostToDevice, c->stream));
     if (op == FOURQ_SC_REDUCE512 || op == FOURQ_SC_MULSUB || op == FOURQ_SC_MUL) {
         HIPRC_TRY(c, sig_launch_scalar_prim(c->stream, op, (const uint64_t*)base, (uint64_t*)(base + ib), (u32)n));
+    } else if (op == FOURQ_PT_MAP_ELL2) {
+        HIPRC_TRY(c, h2c_launch_ell2(c->stream, 1, H2C_OUT_MAP, (const uint64_t*)base, (uint64_t*)(base + ib), (u32)n));
     } else {
         hipLaunchKernelGGL(prim_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, op, (const u64*)base, (u64*)(base + ib),
                            (u32)n, (u32)p->in_words, (u32)p->out_words);

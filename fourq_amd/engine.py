@@ -442,6 +442,55 @@ class Engine:
         self._ck(self._lib.fourq_sig_verify_batch_dev(self._ctx, _ptr(pk32), _ptr(self._comb_arg(comb_host)), _ptr(msgs), stride, _ptr(lens), msg_len,
                                                       _ptr(sig64), _ptr(ok), _ptr(status), n))
 
+    # ---- bytes to a point (fourq_hash_to_*: RFC 9380 with SHA-512 XMD, Elligator 2 and the x392 chain, include/fourq_amd.h) --------
+    @staticmethod
+    def _h2c(dst, mode):
+        """(DST as a ctypes buffer, its length, FOURQ_H2C_*); a DST of 0 or more than 255 bytes is the library's FOURQ_ERR_INVALID."""
+        dst = bytes(dst)
+        modes = {"ro": _lib.H2C_RO, "nu": _lib.H2C_NU, _lib.H2C_RO: _lib.H2C_RO, _lib.H2C_NU: _lib.H2C_NU}
+        if mode not in modes:
+            raise ValueError('mode must be "ro" or "nu"')
+        return ctypes.create_string_buffer(dst, max(len(dst), 1)), len(dst), modes[mode]
+
+    def hash_to_field(self, msgs, lens=None, dst=b"", mode="ro", out=None):
+        """u_0 [, u_1] of every row of `msgs`: (n, count, 4) uint64 canonical words, count = 2 ("ro") or 1 ("nu")."""
+        buf, dst_len, mode = self._h2c(dst, mode)
+        m, stride, lens, msg_len = self._msgs(msgs, lens)
+        count = 2 if mode == _lib.H2C_RO else 1
+        out = _out(out, len(m), 4 * count).reshape(len(m), count, 4)
+        self._ck(self._lib.fourq_hash_to_field_batch(self._ctx, buf, dst_len, mode, _ptr(m) if stride else None, stride, _ptr(lens), msg_len, _ptr(out), len(m)))
+        return out
+
+    def hash_to_field_dev(self, msgs, stride, lens, msg_len, out_u, n, dst=b"", mode="ro"):
+        buf, dst_len, mode = self._h2c(dst, mode)
+        self._ck(self._lib.fourq_hash_to_field_batch_dev(self._ctx, buf, dst_len, mode, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(out_u), n))
+
+    def map_to_curve(self, u, out=None):
+        """Elligator 2 + the rational map of every u (n, 4) -- each coordinate any value below 2^128 -- as affine points (n, 8);
+        no cofactor clearing."""
+        u = _host(u, 4)
+        out = _out(out, len(u), 8)
+        self._ck(self._lib.fourq_map_to_curve_batch(self._ctx, _ptr(u), _ptr(out), len(u)))
+        return out
+
+    def map_to_curve_dev(self, u, out_affine, n):
+        self._ck(self._lib.fourq_map_to_curve_batch_dev(self._ctx, _ptr(u), _ptr(out_affine), n))
+
+    def hash_to_curve(self, msgs, lens=None, dst=b"", mode="ro", affine=False, out=None):
+        """The point every row of `msgs` hashes to under the domain separation tag `dst` (1..255 bytes): (n, 32) uint8 encodings, or
+        (n, 8) uint64 affine words with `affine`.  mode "ro": [392](map(u_0) + map(u_1)); "nu": [392]map(u_0)."""
+        buf, dst_len, mode = self._h2c(dst, mode)
+        m, stride, lens, msg_len = self._msgs(msgs, lens)
+        out = _out(out, len(m), 8) if affine else _out(out, len(m), 32, np.uint8)
+        fn = self._lib.fourq_hash_to_curve_affine_batch if affine else self._lib.fourq_hash_to_curve_batch
+        self._ck(fn(self._ctx, buf, dst_len, mode, _ptr(m) if stride else None, stride, _ptr(lens), msg_len, _ptr(out), len(m)))
+        return out
+
+    def hash_to_curve_dev(self, msgs, stride, lens, msg_len, out, n, dst=b"", mode="ro", affine=False):
+        buf, dst_len, mode = self._h2c(dst, mode)
+        fn = self._lib.fourq_hash_to_curve_affine_batch_dev if affine else self._lib.fourq_hash_to_curve_batch_dev
+        self._ck(fn(self._ctx, buf, dst_len, mode, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(out), n))
+
     def dh_exchange_dev(self, a_scalars, b_scalars, base_affine_host, table392_host, out_affine, status, n):
         base = _host(base_affine_host, None).ravel()
         t = None if table392_host is None else _host(table392_host, None).ravel()

@@ -194,6 +194,13 @@ class MultiEngine:
         return self._sharded(lambda e, pk, m, sig, ln, o, st: e.sig_verify(pk, m, sig, ln, comb, ok=o, status=st), [pk, m, sig, ln],
                              [_out(ok, len(pk), None, np.uint8), _out(status, len(pk), None, np.uint8)])
 
+    def hash_to_curve(self, msgs, lens=None, dst=b"", mode="ro", affine=False, out=None):
+        m = np.ascontiguousarray(msgs, dtype=np.uint8)
+        ln = np.full(len(m), m.shape[1], dtype=np.uint32) if lens is None else np.ascontiguousarray(lens, dtype=np.uint32).ravel()
+        self._same_len(m, ln)
+        out = _out(out, len(m), 8) if affine else _out(out, len(m), 32, np.uint8)
+        return self._sharded(lambda e, m, ln, o: e.hash_to_curve(m, ln, dst, mode, affine, out=o), [m, ln], [out])
+
     # ---- wire format ----------------------------------------------------------------------------------------------
     def encode(self, points_affine, out=None):
         p = _host(points_affine, 8)

@@ -203,6 +203,9 @@ def run(loops=1000, dh_loops=10, seed=None, out=sys.stdout):
     ok, st = eng.verify_bytes(ks, ls, as_rows(keys), spoiled)
     bad += int(ok.any())
     rep.check("double-scalar / verify", bad == 0, bad)
+    # bytes to a point: a fixed message hashes to the point the CPU restatement of the construction gives (include/fourq_amd.h)
+    from . import h2c
+    rep.check("hash-to-curve", h2c.hash_to_curve(h2c.KAT_MSG, h2c.KAT_DST, "ro").hex() == h2c.KAT_POINT)
     return rep.failed
 
 

@@ -372,6 +372,54 @@ int fourq_sig_verify_batch_dev(fourq_ctx *ctx, const uint8_t *pk32, const uint64
                                const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
                                const uint8_t *sig64, uint8_t *ok, uint8_t *status, size_t n);
 
+/* ---- bytes to a point: hash to curve (RFC 9380) with SHA-512 XMD, Elligator 2 and the x392 chain on the device -----------------------------
+ * RFC 9380's construction instantiated for FourQ.  The suite names FourQ_XMD:SHA-512_ELL2_RO_ and FourQ_XMD:SHA-512_ELL2_NU_ are OURS: no
+ * such suite is registered with the RFC or anywhere else, and no other implementation was available to check against -- the yardstick is
+ * the CPU restatement tests/h2c_ref.py (hashlib + the oracle's field and point functions) and the fixture made from it with the reference's
+ * own point functions (tests/golden/h2c.json).
+ *   field      F = GF(p^2), p = 2^127 - 1, elements (re, im), i^2 = -1;  m = 2, k = 128, L = 32
+ *   expand_message_xmd (section 5.3.1), H = SHA-512, b_in_bytes = 64, s_in_bytes = 128:
+ *              DST_prime = DST || I2OSP(len(DST), 1);  b_0 = H(Z_pad(128 zero bytes) || msg || I2OSP(len_in_bytes, 2) || 0x00 || DST_prime);
+ *              b_1 = H(b_0 || 0x01 || DST_prime);  b_2 = H((b_0 xor b_1) || 0x02 || DST_prime);  len_in_bytes = 128 (RO: b_1 || b_2) or
+ *              64 (NU: b_1).  DST is 1..FOURQ_H2C_MAX_DST bytes (FOURQ_ERR_INVALID otherwise: no oversize-DST hashing); a HOST pointer in
+ *              both flavours, like `table` (it travels in the kernel arguments: nothing is staged, the _dev calls stay capturable).
+ *   hash_to_field (section 5.2), count = 2 (RO) or 1 (NU):  e_(i,j) = OS2IP(uniform[32 (j + 2 i) : 32 (j + 2 i) + 32]) mod p, big-endian;
+ *              u_i = (e_(i,0), e_(i,1)).
+ *   curve      the Montgomery model K t^2 = s^3 + J s^2 + s with J = 2 (a + d) / (a - d), K = 4 / (a - d), a = -1 (appendix D.1):
+ *              J = (0x7ffffffffffffc700000000000000509, 0x637a835bf687a14faadcb5733c136818),
+ *              K = (0x38ffffffffffffffaf4, 0x1c857ca409785eb055234a8cc3ec97e7);  Z = 2 + i, the first non-square of F in 1 + i, 2 + i, ...
+ *              (an element of F is a square iff its norm re^2 + im^2 is a square of GF(p) or zero).  1 + Z u^2 = 0 has no solution.
+ *   map_to_curve_elligator2 (section 6.7.1):  x1 = -(J/K) inv0(1 + Z u^2) (-J/K when that is 0);  gx = x^3 + (J/K) x^2 + x / K^2;
+ *              x2 = -x1 - J/K;  (x1, sqrt(gx1)) with sgn0 = 1 when gx1 is a square (zero is one), otherwise (x2, sqrt(gx2)) with sgn0 = 0;
+ *              (s, t) = (x K, y K).  sgn0 (section 4.1, m = 2) on canonical residues: (re & 1) | ((re == 0) & (im & 1)).
+ *   rational map (appendix D.1):  (x, y) = (s / t, (s - 1) / (s + 1)) on -x^2 + y^2 = 1 + d x^2 y^2;  t (s + 1) = 0 gives (0, 1).
+ *   RO         P = [392](map(u_0) + map(u_1)), the sum by the complete addition;   NU   P = [392]map(u_0);   x392: curve4q.py:450-455.
+ *   output     encode(P) (curve4q.py:41), or canonical affine words.  The neutral point is an ordinary result (01 00 ... 00), as in
+ *              fourq_double_mul_*; there is no status.
+ * Messages and their rules are those of fourq_sha512_batch: rows of `stride` bytes, lens or msg_len, FOURQ_SIG_MAX_MSG for the host-pointer
+ * calls, and the _dev calls clamp a length to `stride` and hash the clamped row.  No branch and no address depends on u or on a message
+ * byte (the message may be a password; lengths are public): every selection is a mask, so the same code serves both table-selection
+ * modes and fourq_ctx_set_ct_select changes nothing here.  fourq_ctx_reserve covers the one intermediate (u). */
+#define FOURQ_H2C_RO 0
+#define FOURQ_H2C_NU 1
+#define FOURQ_H2C_MAX_DST 255
+/* out_u: n x count x 4 words, canonical */
+int fourq_hash_to_field_batch(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, int mode,
+                              const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint64_t *out_u, size_t n);
+int fourq_hash_to_field_batch_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, int mode,
+                                  const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint64_t *out_u, size_t n);
+/* u: n x 4 words, each coordinate any value in [0, 2^128); out_affine: the map and the rational map, NO cofactor clearing */
+int fourq_map_to_curve_batch(fourq_ctx *ctx, const uint64_t *u, uint64_t *out_affine, size_t n);
+int fourq_map_to_curve_batch_dev(fourq_ctx *ctx, const uint64_t *u, uint64_t *out_affine, size_t n);
+int fourq_hash_to_curve_batch(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, int mode,
+                              const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *out32, size_t n);
+int fourq_hash_to_curve_batch_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, int mode,
+                                  const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *out32, size_t n);
+int fourq_hash_to_curve_affine_batch(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, int mode,
+                                     const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint64_t *out_affine, size_t n);
+int fourq_hash_to_curve_affine_batch_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, int mode,
+                                         const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint64_t *out_affine, size_t n);
+
 /* ---- primitives (one reference function per op, batched) --------------------------------------
  * Used by the Python mirror of the reference's helper API (GFp.*, GFp2.*, DBL, ADD, phi, ...) and by
  * the parity tests to check every layer of the path on the GPU.  in/out are HOST pointers;
@@ -403,6 +451,7 @@ enum fourq_prim {
     FOURQ_PT_ON_CURVE = 44,     /* affine[8] -> [1] (0/1)            curve4q.py:23 */
     FOURQ_PT_COFACTOR392 = 45,  /* affine[8] -> R1[20]               curve4q.py:450-455 */
     FOURQ_PT_R1TOAFFINE = 46,   /* R1[20] -> affine[8]               curve4q.py:103 */
+    FOURQ_PT_MAP_ELL2 = 47,     /* u[4] -> affine[8]: Elligator 2 + the rational map ("bytes to a point" above) */
     /* curve4q.py:216-226, :339-380 */
     FOURQ_SC_DECOMPOSE = 64,    /* m[4] -> a1..a4 [4] */
     FOURQ_SC_RECODE = 65,       /* v[4] = decompose(m) -> [5]: sign bits 0..63, digit bit-planes 0,1,2, digit 64 */
