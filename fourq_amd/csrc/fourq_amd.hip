@@ -38,6 +38,7 @@
 #endif
 #include "kernels.hip.h"
 #include "pipeline_plan.h"
+#include "work_layout.h"
 #include "sig.hip.h"
 #include "h2c.hip.h"
 
@@ -453,6 +454,11 @@ const PrimShape* find_prim(int op) {
 }  // namespace
 
 // ====================================================================================== C ABI
+// Which host-array call this is, for the measured planner inputs (fourq_ctx::plan_kt)
+enum PipeRouteId { PR_MUL_VAR = 0, PR_MUL_FIX = 2, PR_DH_VAR = 4, PR_DH_FIX = 6, PR_MIXED = 8, PR_COMB = 9, PR_ENCODE = 10, PR_DECODE = 11, PR_DHB_VAR = 12,
+                   PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25,
+                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_H2F = 30, PR_H2C_MAP = 31, PR_H2C = 32, PR_H2C_AFFINE = 34, PR_COUNT = 36 };       // + algo or mode (0 / 1) where two follow each other
+static_assert(PR_H2C_AFFINE + FOURQ_H2C_NU < PR_COUNT && FOURQ_H2C_RO == 0 && FOURQ_H2C_NU == 1, "the highest route id plus its mode offset must fit fourq_ctx::plan_kt");
 constexpr int PIPE_SLOTS_MAX = 6;
 struct fourq_ctx {
     int device = 0;
@@ -504,7 +510,7 @@ struct fourq_ctx {
     // Measured planner inputs (round 6): every multi-chunk host-array call times ONE middle chunk (six events, `probe_ticks`) and leaves the
     // kernel time per element of its route -- per selection mode -- and the link's rate each way here; the next call of that route is planned
     // with them.  0 = not measured yet: the first call plans with the KT_* guesses (x KT_CT_GUESS in constant-time mode) and 48 GB/s.
-    double plan_kt[40][2] = {};
+    double plan_kt[PR_COUNT][2] = {};
     double plan_link_in = 0, plan_link_out = 0;     // bytes per nanosecond
     hipEvent_t probe_ticks[6] = {};
     bool fused_io = true;          // FOURQ_FUSED_IO=0 (test hook): the affine / encoded flavours of MUL_* always through lift + full R1 rows, as round 5
@@ -600,13 +606,19 @@ bool takes_split_route(const fourq_ctx* c, int algo, bool dh, size_t n) {
 // generation instead of a whole one.  Both selection modes.
 // At most quad_max (a QUARTER generation) elements: FOUR lanes per element -- the element's two pairs take every other product of a
 // formula level in the ladder steps -- 0.73 of the two-lane latency again (profiles/r03_quadlane.txt).
+// The grid of n elements on the two- / four-lane kernels.  *quad: at most a quarter generation, four lanes per element, the ladder steps' products
+// shared between two pairs.  The ladders walk their elements with one block per CU at the most; the comb's kernels take every block.
+unsigned pair_grid(const fourq_ctx* c, size_t n, bool one_block_per_cu, bool* quad) {
+    *quad = n <= c->quad_max;
+    const size_t per_block = BLOCK / (*quad ? 4 : 2);
+    const size_t blocks = (n + per_block - 1) / per_block;
+    return (unsigned)(one_block_per_cu && blocks > (size_t)c->cus ? (size_t)c->cus : blocks);
+}
 // FIXED: the staged fixed-base table (c->table_limbs) instead of a table built per element.
 template <int ALGO, bool DH, bool FIXED = false> int launch_pair(fourq_ctx* c, LadderArgs a) {
     if (a.n == 0) return FOURQ_OK;
-    const bool quad = a.n <= c->quad_max;   // at most a quarter generation: four lanes per element, the ladder steps' products shared between two pairs
-    const size_t per_block = BLOCK / (quad ? 4 : 2);
-    const size_t blocks = ((size_t)a.n + per_block - 1) / per_block;
-    const unsigned grid = (unsigned)(blocks < (size_t)c->cus ? blocks : (size_t)c->cus);
+    bool quad;
+    const unsigned grid = pair_grid(c, a.n, true, &quad);
     a.table = c->table_limbs;
     if (c->ct) {                            // fourq_ct_fused.hip: the same kernels with the lane's table scanned at every step
         HIPRC_TRY(c, ct_launch_pair(ALGO, DH, FIXED, quad, grid, c->stream, a));
@@ -619,10 +631,8 @@ template <int ALGO, bool DH, bool FIXED = false> int launch_pair(fourq_ctx* c, L
 }
 // A mixed batch of at most half a generation: the same kernels with the table chosen per element (kernels.hip.h, pair_kernel<..., MIXED>)
 int launch_pair_mixed(fourq_ctx* c, LadderArgs a) {
-    const bool quad = a.n <= c->quad_max;
-    const size_t per_block = BLOCK / (quad ? 4 : 2);
-    const size_t blocks = ((size_t)a.n + per_block - 1) / per_block;
-    const unsigned grid = (unsigned)(blocks < (size_t)c->cus ? blocks : (size_t)c->cus);
+    bool quad;
+    const unsigned grid = pair_grid(c, a.n, true, &quad);
     a.table = c->table_limbs;
     if (c->ct) {
         HIPRC_TRY(c, ct_launch_pair_mixed(quad, grid, c->stream, a));
@@ -807,7 +817,7 @@ struct PipeArray {
     char* dst;           // output array (host) or NULL
     size_t stride;       // bytes per element
 };
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using fq_work::align256;
 
 bool is_pinned(const void* p) {
     hipPointerAttribute_t attr;
@@ -850,18 +860,20 @@ int grow(fourq_ctx* c, char** buf, size_t* have, size_t want, bool pinned) {
     *buf = (char*)p; *have = want;
     return FOURQ_OK;
 }
+// Intermediates of the protocol-level calls: each call carves c->work by its layout in work_layout.h and asks for that layout's bytes(n)
 int ensure_work(fourq_ctx* c, size_t bytes) { return grow(c, &c->work, &c->work_bytes, bytes + bytes / 4, false); }
-// intermediates of the protocol-level calls for n elements (decoded keys / first-half results, their status bytes)
-size_t dh_bytes_work_bytes(size_t n) { return 2 * n * 64 + 2 * align256(n); }
-size_t exchange_work_bytes(size_t n) { return 2 * n * 64 + align256(n); }
-size_t mul_affine_work_bytes(size_t n) { return 2 * n * 160 + n * 64 + align256(n); }      // R1 in, R1 out, decoded points, decode status
-size_t double_mul_rows_bytes(size_t n) { return 2 * n * 160 + 2 * align256(n); }             // lifted / decoded points, the ladder's rows, decode status, the comb's status
-// ... and behind them what fourq_sig_verify_batch_dev hands the double multiplication: s, h and R as 32-byte rows, one pre-status byte per row
-size_t double_mul_work_bytes(size_t n) { return double_mul_rows_bytes(n) + 3 * n * 32 + align256(n); }
-// keygen / sign: a = LE(k[0:32]), r, encode([r]G) as 32-byte rows, the comb's affine rows, its status
-size_t sig_work_bytes(size_t n) { return 3 * n * 32 + n * 64 + align256(n); }
-// hash to curve: u_0, u_1 as 32-byte rows
-size_t h2c_work_bytes(size_t n) { return 2 * n * 32; }
+// What a host-array call sizes for its largest chunk BEFORE the first chunk is enqueued (PipeReserve; ensure_proj is one of them as it stands):
+// the projective planes where the _dev call behind it defers a normalisation, and that call's layout of the work buffer
+int reserve_work(fourq_ctx* c, size_t big, bool proj, size_t bytes) {
+    if (int r = proj ? ensure_proj(c, big) : FOURQ_OK) return r;
+    return ensure_work(c, bytes);
+}
+int reserve_dh_bytes(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::DhBytes::bytes(big)); }
+int reserve_exchange(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::Exchange::bytes(big)); }
+int reserve_mul_rows(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::MulRows::bytes(big)); }
+int reserve_double_mul(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::DoubleMul::bytes(big)); }      // also the signature check's
+int reserve_sig(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::Sig::bytes(big)); }
+int reserve_h2c(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::H2c::bytes(big)); }
 
 int ensure_ticks(fourq_ctx* c, size_t count) {
     while (c->ticks.size() < count) {
@@ -874,21 +886,18 @@ int ensure_ticks(fourq_ctx* c, size_t count) {
 
 using ChunkLaunch = std::function<int(char* const* in_dev, char* const* out_dev, size_t m)>;
 
-// Which call this is, for the measured planner inputs, and the guess of its kernel time per element for the context's first call of it
-enum PipeRouteId { PR_MUL_VAR = 0, PR_MUL_FIX = 2, PR_DH_VAR = 4, PR_DH_FIX = 6, PR_MIXED = 8, PR_COMB = 9, PR_ENCODE = 10, PR_DECODE = 11, PR_DHB_VAR = 12,
-                   PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25,
-                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_H2F = 30, PR_H2C_MAP = 31, PR_H2C = 32, PR_H2C_AFFINE = 34, PR_COUNT = 36 };       // + algo (0 / 1) where two follow each other
+// Which call this is (PipeRouteId), and the guess of its kernel time per element for the context's first call of it
 struct PipeRoute { int id; double kt_guess; };
 constexpr double KT_CT_GUESS = 1.3;                 // constant-time selection: x 1.07 - 1.5 by route until the context has measured it
-using PipeReserve = std::function<int(size_t big)>; // sizes the context's intermediates for the largest chunk BEFORE the first chunk is enqueued
-int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch, size_t chunk_bounce, const PipeReserve& reserve);
+using PipeReserve = int (*)(fourq_ctx* c, size_t big);  // sizes the context's intermediates for the largest chunk BEFORE the first chunk is enqueued
+int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch, size_t chunk_bounce, PipeReserve reserve);
 // `chunk`: elements of one kernel generation of the route the call takes; `ns_per_elem`: that route's kernel time per element (the
 // KT_* constants below: what sizes the chunks is the ratio of kernel time to copy time, pipeline_plan.h).  `chunk_bounce` (0 = `chunk`):
 // the uniform chunk of a call from PAGEABLE arrays -- its pace is the host's bounce copies (and, where the call allocates its result, the
 // page faults of 160 fresh bytes per element), not the link: such calls keep the chunk shape they were measured with in rounds 2-4
 // (cfg3's call, result array reused: 10.3-10.4 ms at 2^20 then and now; profiles/r02_host_api.txt, profiles/r05_pipeline.txt).
 int run_pipeline(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch,
-                 size_t chunk_bounce = 0, const PipeReserve& reserve = nullptr) {
+                 size_t chunk_bounce = 0, PipeReserve reserve = nullptr) {
     const int rc = run_pipeline_inner(c, in, n_in, out, n_out, n, chunk, route, launch, chunk_bounce, reserve);
     if (rc != FOURQ_OK) {                      // a chunk failed half way: nothing of this call may still be in flight when the caller
         (void)hipStreamSynchronize(c->copy_in);    // gets its buffers (and the context its slots) back
@@ -897,121 +906,157 @@ int run_pipeline(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* o
     }
     return rc;
 }
-int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch, size_t chunk_bounce, const PipeReserve& reserve) {
-    if (n_in > PIPE_MAX_ARRAYS || n_out > PIPE_MAX_ARRAYS || chunk == 0 || route.id < 0 || route.id >= 40) return FOURQ_ERR_INVALID;
-    bool is_pin_in[PIPE_MAX_ARRAYS], is_pin_out[PIPE_MAX_ARRAYS], any_pageable = false;
-    for (int i = 0; i < n_in; i++) { is_pin_in[i] = is_pinned(in[i].src); any_pageable |= !is_pin_in[i]; }
-    for (int i = 0; i < n_out; i++) { is_pin_out[i] = is_pinned(out[i].dst); any_pageable |= !is_pin_out[i]; }
-    const bool uniform = any_pageable && c->host_bounce && chunk_bounce > chunk && n > chunk_bounce;
-    if (uniform) chunk = chunk_bounce;
-    if (chunk > n) chunk = n;
-    size_t off_in[PIPE_MAX_ARRAYS], off_out[PIPE_MAX_ARRAYS], slot = 0;
-    bool pin_in[PIPE_MAX_ARRAYS], pin_out[PIPE_MAX_ARRAYS], bounce = false;
-    const size_t chunks = (n + chunk - 1) / chunk;
-    // "direct" = hipMemcpyAsync on the caller's array.  Pinned arrays always; pageable ones when the batch is a single
-    // chunk (nothing to overlap with, and the runtime's own staging of a pageable copy beats a bounce pass: 0.92 vs
-    // 1.29 ms at 2^16 variable-base elements), through the bounce slots otherwise (8.5 vs 13.9 ms at 2^20).
-    const bool direct_pageable = !c->host_bounce || chunks == 1;
-    fourq_host_stats st = {};
-    st.chunks = (uint32_t)chunks;
-    st.pinned_in = st.pinned_out = 1;
-    for (int i = 0; i < n_in; i++) {
-        const bool pinned = is_pin_in[i];
-        off_in[i] = slot; slot += align256(chunk * in[i].stride); pin_in[i] = pinned || direct_pageable; bounce |= !pin_in[i];
-        st.pinned_in &= pinned ? 1 : 0;
+// One host-array call as its three paths below see it.  pin_in / pin_out: the array is copied "directly", hipMemcpyAsync on the caller's
+// array -- pinned arrays always; pageable ones when the batch is a single chunk (nothing to overlap with, and the runtime's own staging of
+// a pageable copy beats a bounce pass: 0.92 vs 1.29 ms at 2^16 variable-base elements), through the bounce slots otherwise (8.5 vs 13.9 ms at 2^20).
+struct PipeCall {
+    fourq_ctx* c;
+    const PipeArray* in; int n_in;
+    const PipeArray* out; int n_out;
+    size_t n;
+    const ChunkLaunch& launch;
+    bool pin_in[PIPE_MAX_ARRAYS], pin_out[PIPE_MAX_ARRAYS], bounce;
+};
+// A slot holds the arrays of one chunk of m elements, inputs then outputs, each on a 256-byte boundary
+struct SlotLayout { size_t off_in[PIPE_MAX_ARRAYS], off_out[PIPE_MAX_ARRAYS], bytes; };
+SlotLayout slot_layout(const PipeCall& p, size_t m) {
+    SlotLayout s = {};
+    for (int i = 0; i < p.n_in; i++) { s.off_in[i] = s.bytes; s.bytes += align256(m * p.in[i].stride); }
+    for (int i = 0; i < p.n_out; i++) { s.off_out[i] = s.bytes; s.bytes += align256(m * p.out[i].stride); }
+    return s;
+}
+// Tiny calls (the batch of one above all): the arrays fit 64 KiB of pinned host memory that the kernels read and write in
+// place -- two CPU memcpys of a few hundred bytes instead of three trips through the copy engine (profiles/r03_single_call.txt).
+constexpr size_t ZERO_COPY_BYTES = 64u << 10;
+int pipe_zero_copy(const PipeCall& p, const SlotLayout& s, const fourq_host_stats& st) {
+    fourq_ctx* c = p.c;
+    if (!c->zero_copy) HIP_TRY(c, hipHostMalloc((void**)&c->zero_copy, ZERO_COPY_BYTES, hipHostMallocDefault));
+    char *din[PIPE_MAX_ARRAYS], *dout[PIPE_MAX_ARRAYS];
+    for (int i = 0; i < p.n_in; i++) {
+        din[i] = c->zero_copy + s.off_in[i];
+        memcpy(din[i], p.in[i].src, p.n * p.in[i].stride);            // a CPU copy: no h2d / d2h bytes or times are reported for it
     }
-    for (int i = 0; i < n_out; i++) {
-        const bool pinned = is_pin_out[i];
-        off_out[i] = slot; slot += align256(chunk * out[i].stride); pin_out[i] = pinned || direct_pageable; bounce |= !pin_out[i];
-        st.pinned_out &= pinned ? 1 : 0;
+    for (int i = 0; i < p.n_out; i++) dout[i] = c->zero_copy + s.off_out[i];
+    if (int rc = p.launch(din, dout, p.n)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < p.n_out; i++) memcpy(p.out[i].dst, dout[i], p.n * p.out[i].stride);
+    c->host_stats = st;
+    return FOURQ_OK;
+}
+// A single chunk (down to the reference-shaped call, a batch of one): copies and kernels in order on the context's own stream.
+// Nothing can overlap, so the three-stream choreography below would only add its cross-stream event hops (50 us) to the call.
+// The four timing events around the copies are recorded only under fourq_ctx_set_host_timing; otherwise copy durations read 0.
+int pipe_single_chunk(const PipeCall& p, const SlotLayout& s, fourq_host_stats st) {
+    fourq_ctx* c = p.c;
+    const size_t n = p.n;
+    int rc = grow(c, &c->pipe_dev, &c->pipe_dev_bytes, s.bytes, false);
+    if (rc) return rc;
+    const bool timed = c->host_timing;
+    if (timed && (rc = ensure_ticks(c, 4))) return rc;
+    char *din[PIPE_MAX_ARRAYS], *dout[PIPE_MAX_ARRAYS];
+    if (timed) HIP_TRY(c, hipEventRecord(c->ticks[0], c->stream));
+    for (int i = 0; i < p.n_in; i++) {
+        din[i] = c->pipe_dev + s.off_in[i];
+        HIP_TRY(c, hipMemcpyAsync(din[i], p.in[i].src, n * p.in[i].stride, hipMemcpyHostToDevice, c->stream));
+        st.h2d_bytes += n * p.in[i].stride;
     }
-    // A single chunk (down to the reference-shaped call, a batch of one): copies and kernels in order on the context's own stream.
-    // Nothing can overlap, so the three-stream choreography below would only add its cross-stream event hops (50 us) to the call.
-    // The four timing events around the copies are recorded only under fourq_ctx_set_host_timing; otherwise copy durations read 0.
-    // Tiny calls (the batch of one above all): the arrays fit 64 KiB of pinned host memory that the kernels read and write in
-    // place -- two CPU memcpys of a few hundred bytes instead of three trips through the copy engine (profiles/r03_single_call.txt).
-    constexpr size_t ZERO_COPY_BYTES = 64u << 10;
-    if (chunks == 1 && slot <= ZERO_COPY_BYTES && c->host_zero_copy) {
-        if (!c->zero_copy) {
-            void* zp = nullptr;
-            HIP_TRY(c, hipHostMalloc(&zp, ZERO_COPY_BYTES, hipHostMallocDefault));
-            c->zero_copy = (char*)zp;
-        }
-        char *din[PIPE_MAX_ARRAYS], *dout[PIPE_MAX_ARRAYS];
-        for (int i = 0; i < n_in; i++) {
-            din[i] = c->zero_copy + off_in[i];
-            memcpy(din[i], in[i].src, n * in[i].stride);              // a CPU copy: no h2d / d2h bytes or times are reported for it
-        }
-        for (int i = 0; i < n_out; i++) dout[i] = c->zero_copy + off_out[i];
-        if (int rc = launch(din, dout, n)) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < n_out; i++) {
-            memcpy(out[i].dst, dout[i], n * out[i].stride);
-        }
-        c->host_stats = st;
-        return FOURQ_OK;
+    if (timed) HIP_TRY(c, hipEventRecord(c->ticks[1], c->stream));
+    for (int i = 0; i < p.n_out; i++) dout[i] = c->pipe_dev + s.off_out[i];
+    if ((rc = p.launch(din, dout, n))) return rc;
+    if (timed) HIP_TRY(c, hipEventRecord(c->ticks[2], c->stream));
+    for (int i = 0; i < p.n_out; i++) {
+        HIP_TRY(c, hipMemcpyAsync(p.out[i].dst, dout[i], n * p.out[i].stride, hipMemcpyDeviceToHost, c->stream));
+        st.d2h_bytes += n * p.out[i].stride;
     }
-    if (chunks == 1) {
-        int rc = grow(c, &c->pipe_dev, &c->pipe_dev_bytes, slot, false);
-        if (rc) return rc;
-        const bool timed = c->host_timing;
-        if (timed && (rc = ensure_ticks(c, 4))) return rc;
-        char *din[PIPE_MAX_ARRAYS], *dout[PIPE_MAX_ARRAYS];
-        if (timed) HIP_TRY(c, hipEventRecord(c->ticks[0], c->stream));
-        for (int i = 0; i < n_in; i++) {
-            din[i] = c->pipe_dev + off_in[i];
-            HIP_TRY(c, hipMemcpyAsync(din[i], in[i].src, n * in[i].stride, hipMemcpyHostToDevice, c->stream));
-            st.h2d_bytes += n * in[i].stride;
-        }
-        if (timed) HIP_TRY(c, hipEventRecord(c->ticks[1], c->stream));
-        for (int i = 0; i < n_out; i++) dout[i] = c->pipe_dev + off_out[i];
-        if ((rc = launch(din, dout, n))) return rc;
-        if (timed) HIP_TRY(c, hipEventRecord(c->ticks[2], c->stream));
-        for (int i = 0; i < n_out; i++) {
-            HIP_TRY(c, hipMemcpyAsync(out[i].dst, dout[i], n * out[i].stride, hipMemcpyDeviceToHost, c->stream));
-            st.d2h_bytes += n * out[i].stride;
-        }
-        if (timed) HIP_TRY(c, hipEventRecord(c->ticks[3], c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (timed) {
-            float ms = 0;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[0], c->ticks[1]));
-            st.h2d_ms = ms;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[2], c->ticks[3]));
-            st.d2h_ms = ms;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[1], c->ticks[2]));
-            st.kernels_ms = st.kernels_span_ms = ms;
-        }
-        c->host_stats = st;
-        return FOURQ_OK;
+    if (timed) HIP_TRY(c, hipEventRecord(c->ticks[3], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (timed) {
+        float ms = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[0], c->ticks[1]));
+        st.h2d_ms = ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[2], c->ticks[3]));
+        st.d2h_ms = ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[1], c->ticks[2]));
+        st.kernels_ms = st.kernels_span_ms = ms;
     }
-    // The chunks of this call (pipeline_plan.h): one generation first and last, growing in between as far as the copies' lead allows
-    size_t bytes_in = 0, bytes_out = 0;
-    for (int i = 0; i < n_in; i++) bytes_in += in[i].stride;
-    for (int i = 0; i < n_out; i++) bytes_out += out[i].stride;
-    using fq_plan::Piece;
-    std::vector<Piece> plan;
-    // what the plan is priced with: this context's own measurements of this route in this selection mode, or the first call's guesses
+    c->host_stats = st;
+    return FOURQ_OK;
+}
+// What a plan is priced with: this context's own measurements of this route in this selection mode, or the first call's guesses
+fq_plan::Rates plan_rates(const fourq_ctx* c, PipeRoute route, fourq_host_stats* st) {
     const int mode = c->ct ? 1 : 0;
     fq_plan::Rates rates;
     const bool measured = c->plan_measure && c->plan_kt[route.id][mode] > 0;
     rates.ns_per_elem = measured ? c->plan_kt[route.id][mode] : route.kt_guess * (c->ct ? KT_CT_GUESS : 1.0);
     rates.link_in = c->plan_measure && c->plan_link_in > 0 ? c->plan_link_in : fq_plan::LINK_BYTES_PER_NS;
     rates.link_out = c->plan_measure && c->plan_link_out > 0 ? c->plan_link_out : fq_plan::LINK_BYTES_PER_NS;
-    st.planned_kernel_ns_per_elem = rates.ns_per_elem; st.planned_link_in_gbs = rates.link_in; st.planned_link_out_gbs = rates.link_out;
-    st.planned_from_measurement = measured ? 1 : 0;
-    try { plan = fq_plan::plan_pieces(n, chunk, bytes_in, bytes_out, rates, (bounce && !c->pipe_gens) ? 1 : c->pipe_gens); } catch (...) { return FOURQ_ERR_NOMEM; }
+    st->planned_kernel_ns_per_elem = rates.ns_per_elem; st->planned_link_in_gbs = rates.link_in; st->planned_link_out_gbs = rates.link_out;
+    st->planned_from_measurement = measured ? 1 : 0;
+    return rates;
+}
+// What the next call of this route will be planned with, from the probed chunk of m elements.  The link's rates only from a chunk that had
+// neighbours on both sides (a call of one or two chunks copies with the link to itself), and only from a chunk copied directly (a bounce
+// slot's copy is paced by the host threads that fill it): `link`.
+int read_probe(fourq_ctx* c, PipeRoute route, double m, bool link, size_t bytes_in, size_t bytes_out, fourq_host_stats* st) {
+    const int mode = c->ct ? 1 : 0;
+    float t_in = 0, t_k = 0, t_out = 0;
+    HIP_TRY(c, hipEventElapsedTime(&t_in, c->probe_ticks[0], c->probe_ticks[1]));
+    HIP_TRY(c, hipEventElapsedTime(&t_k, c->probe_ticks[2], c->probe_ticks[3]));
+    HIP_TRY(c, hipEventElapsedTime(&t_out, c->probe_ticks[4], c->probe_ticks[5]));
+    if (t_k > 0) c->plan_kt[route.id][mode] = (double)t_k * 1e6 / m;
+    if (link) {
+        if (t_in > 0 && bytes_in) c->plan_link_in = m * (double)bytes_in / ((double)t_in * 1e6);
+        if (t_out > 0 && bytes_out) c->plan_link_out = m * (double)bytes_out / ((double)t_out * 1e6);
+    }
+    st->measured_kernel_ns_per_elem = c->plan_kt[route.id][mode];
+    return FOURQ_OK;
+}
+// Timing (on request): six events per chunk -- around its copy in, its kernels, its copy out -- for the first TIMED_MAX chunks; a call of
+// more chunks reports their copy durations scaled to the call's bytes (a 2^28-element call has 4 096 chunks: it does not get 24 576 events)
+constexpr size_t TIMED_MAX = 256, TK = 6;
+int read_chunk_timing(fourq_ctx* c, size_t timed_pieces, uint64_t timed_h2d, uint64_t timed_d2h, fourq_host_stats* st) {
+    try {
+        c->chunk_stamps.resize(TK * timed_pieces);
+        for (size_t i = 0; i < TK * timed_pieces; i++) HIP_TRY(c, hipEventElapsedTime(&c->chunk_stamps[i], c->ticks[0], c->ticks[i]));
+    } catch (...) { c->chunk_stamps.clear(); }
+    for (size_t k = 0; k < timed_pieces; k++) {
+        float ms = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[TK * k], c->ticks[TK * k + 1]));
+        st->h2d_ms += ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[TK * k + 2], c->ticks[TK * k + 3]));
+        st->d2h_ms += ms;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[TK * k + 4], c->ticks[TK * k + 5]));
+        st->kernels_ms += ms;
+    }
+    float span = 0;
+    HIP_TRY(c, hipEventElapsedTime(&span, c->ticks[4], c->ticks[TK * (timed_pieces - 1) + 5]));
+    st->kernels_span_ms = span;
+    if (timed_h2d && timed_h2d < st->h2d_bytes) st->h2d_ms *= (double)st->h2d_bytes / (double)timed_h2d;
+    if (timed_d2h && timed_d2h < st->d2h_bytes) st->d2h_ms *= (double)st->d2h_bytes / (double)timed_d2h;
+    return FOURQ_OK;
+}
+// Several chunks: chunk k uses slot k mod slots and goes copy in -> kernels -> copy out on three streams
+int pipe_chunked(const PipeCall& p, size_t chunk, PipeRoute route, PipeReserve reserve, fourq_host_stats st) {
+    fourq_ctx* c = p.c;
+    const PipeArray *in = p.in, *out = p.out;
+    const int n_in = p.n_in, n_out = p.n_out;
+    const bool bounce = p.bounce;
+    // The chunks of this call (pipeline_plan.h): one generation first and last, growing in between as far as the copies' lead allows
+    size_t bytes_in = 0, bytes_out = 0;
+    for (int i = 0; i < n_in; i++) bytes_in += in[i].stride;
+    for (int i = 0; i < n_out; i++) bytes_out += out[i].stride;
+    using fq_plan::Piece;
+    std::vector<Piece> plan;
+    const fq_plan::Rates rates = plan_rates(c, route, &st);
+    try { plan = fq_plan::plan_pieces(p.n, chunk, bytes_in, bytes_out, rates, (bounce && !c->pipe_gens) ? 1 : c->pipe_gens); } catch (...) { return FOURQ_ERR_NOMEM; }
     const size_t pieces = plan.size();
     size_t big = 0;
     for (const Piece& pc : plan) if (pc.m > big) big = pc.m;
     // planned chunks grow within a call; the context's intermediates (work, proj) are sized ONCE for the largest, so that no
     // launch() inside the loop reaches grow() -- which would drain the kernel stream and block the host in mid-pipeline
-    if (reserve) { if (int rrc = reserve(big)) return rrc; }
-    if (big != chunk) {                                                 // the slot layout above was made for `chunk` elements: redo it for `big`
-        slot = 0;
-        for (int i = 0; i < n_in; i++) { off_in[i] = slot; slot += align256(big * in[i].stride); }
-        for (int i = 0; i < n_out; i++) { off_out[i] = slot; slot += align256(big * out[i].stride); }
-    }
+    if (reserve) { if (int rrc = reserve(c, big)) return rrc; }
+    const SlotLayout s = slot_layout(p, big);
+    const size_t slot = s.bytes;
     st.chunks = (uint32_t)pieces;
     // who hands a slot on: the GPU when every array is copied directly, the host when it has bounce slots to fill and drain
     const bool host_wait = bounce || c->pipe_host_wait;
@@ -1027,14 +1072,11 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
     int rc = grow(c, &c->pipe_dev, &c->pipe_dev_bytes, slot * slots, false);
     if (rc) return rc;
     if (bounce && (rc = grow(c, &c->pipe_pin, &c->pipe_pin_bytes, slot * slots, true))) return rc;
-    // timing (on request): six events per chunk -- around its copy in, its kernels, its copy out -- for the first TIMED_MAX chunks; a call of
-    // more chunks reports their copy durations scaled to the call's bytes (a 2^28-element call has 4 096 chunks: it does not get 24 576 events)
-    constexpr size_t TIMED_MAX = 256, TK = 6;
     const size_t timed_pieces = c->host_timing ? (pieces < TIMED_MAX ? pieces : TIMED_MAX) : 0;
     if (timed_pieces && (rc = ensure_ticks(c, TK * timed_pieces))) return rc;
     uint64_t timed_h2d = 0, timed_d2h = 0;
     // the measured planner inputs: ONE chunk of whole generations from the middle of the call, where both directions of the link are busy
-    const size_t whole_pieces = pieces - ((n % chunk) ? 1 : 0);
+    const size_t whole_pieces = pieces - ((p.n % chunk) ? 1 : 0);
     const size_t probe = (c->plan_measure && whole_pieces >= 1) ? (whole_pieces >= 3 ? whole_pieces / 2 : 0) : (size_t)-1;
     if (probe != (size_t)-1)
         for (hipEvent_t& e : c->probe_ticks) if (!e) HIP_TRY(c, hipEventCreate(&e));
@@ -1048,7 +1090,7 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
             HIP_TRY(c, hipEventSynchronize(c->out_done[b]));
         }
         for (int i = 0; i < n_out; i++)
-            if (!pin_out[i]) host_copy(out[i].dst + plan[k].off * out[i].stride, c->pipe_pin + (size_t)b * slot + off_out[i], plan[k].m * out[i].stride);
+            if (!p.pin_out[i]) host_copy(out[i].dst + plan[k].off * out[i].stride, c->pipe_pin + (size_t)b * slot + s.off_out[i], plan[k].m * out[i].stride);
         return FOURQ_OK;
     };
     for (size_t k = 0; k < pieces; k++) {
@@ -1062,14 +1104,14 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
         char* pin = bounce ? c->pipe_pin + (size_t)b * slot : nullptr;
         char *din[PIPE_MAX_ARRAYS], *dout[PIPE_MAX_ARRAYS];
         for (int i = 0; i < n_in; i++) {
-            din[i] = dev + off_in[i];
-            if (!pin_in[i]) host_copy(pin + off_in[i], in[i].src + off * in[i].stride, m * in[i].stride);
+            din[i] = dev + s.off_in[i];
+            if (!p.pin_in[i]) host_copy(pin + s.off_in[i], in[i].src + off * in[i].stride, m * in[i].stride);
         }
         const bool timed = k < timed_pieces, probed = k == probe;
         if (probed) HIP_TRY(c, hipEventRecord(c->probe_ticks[0], c->copy_in));
         if (timed) HIP_TRY(c, hipEventRecord(c->ticks[TK * k], c->copy_in));
         for (int i = 0; i < n_in; i++) {
-            const char* src = pin_in[i] ? in[i].src + off * in[i].stride : pin + off_in[i];
+            const char* src = p.pin_in[i] ? in[i].src + off * in[i].stride : pin + s.off_in[i];
             HIP_TRY(c, hipMemcpyAsync(din[i], src, m * in[i].stride, hipMemcpyHostToDevice, c->copy_in));
             st.h2d_bytes += m * in[i].stride;
             if (timed) timed_h2d += m * in[i].stride;
@@ -1080,8 +1122,8 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->in_done[b], 0));
         if (timed) HIP_TRY(c, hipEventRecord(c->ticks[TK * k + 4], c->stream));      // the kernel stream is past its wait: the chunk's bytes are there
         if (probed) HIP_TRY(c, hipEventRecord(c->probe_ticks[2], c->stream));
-        for (int i = 0; i < n_out; i++) dout[i] = dev + off_out[i];
-        if ((rc = launch(din, dout, m))) return rc;
+        for (int i = 0; i < n_out; i++) dout[i] = dev + s.off_out[i];
+        if ((rc = p.launch(din, dout, m))) return rc;
         if (probed) HIP_TRY(c, hipEventRecord(c->probe_ticks[3], c->stream));
         if (timed) HIP_TRY(c, hipEventRecord(c->ticks[TK * k + 5], c->stream));
         HIP_TRY(c, hipEventRecord(c->kernels_done[b], c->stream));
@@ -1089,7 +1131,7 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
         if (probed) HIP_TRY(c, hipEventRecord(c->probe_ticks[4], c->copy_out));
         if (timed) HIP_TRY(c, hipEventRecord(c->ticks[TK * k + 2], c->copy_out));
         for (int i = 0; i < n_out; i++) {
-            char* dst = pin_out[i] ? out[i].dst + off * out[i].stride : pin + off_out[i];
+            char* dst = p.pin_out[i] ? out[i].dst + off * out[i].stride : pin + s.off_out[i];
             HIP_TRY(c, hipMemcpyAsync(dst, dout[i], m * out[i].stride, hipMemcpyDeviceToHost, c->copy_out));
             st.d2h_bytes += m * out[i].stride;
             if (timed) timed_d2h += m * out[i].stride;
@@ -1104,44 +1146,31 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
     }
     HIP_TRY(c, hipStreamSynchronize(c->copy_out));      // in order behind every chunk's copy out, which is behind its kernels and its copy in
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (probe != (size_t)-1) {                          // what the next call of this route will be planned with
-        float t_in = 0, t_k = 0, t_out = 0;
-        HIP_TRY(c, hipEventElapsedTime(&t_in, c->probe_ticks[0], c->probe_ticks[1]));
-        HIP_TRY(c, hipEventElapsedTime(&t_k, c->probe_ticks[2], c->probe_ticks[3]));
-        HIP_TRY(c, hipEventElapsedTime(&t_out, c->probe_ticks[4], c->probe_ticks[5]));
-        const double m = (double)plan[probe].m;
-        if (t_k > 0) c->plan_kt[route.id][mode] = (double)t_k * 1e6 / m;
-        // the link's rates only from a chunk that had neighbours on both sides (a call of one or two chunks copies with the link to itself),
-        // and only from a chunk copied directly (a bounce slot's copy is paced by the host threads that fill it)
-        if (whole_pieces >= 3 && !bounce) {
-            if (t_in > 0 && bytes_in) c->plan_link_in = m * (double)bytes_in / ((double)t_in * 1e6);
-            if (t_out > 0 && bytes_out) c->plan_link_out = m * (double)bytes_out / ((double)t_out * 1e6);
-        }
-        st.measured_kernel_ns_per_elem = c->plan_kt[route.id][mode];
-    }
+    if (probe != (size_t)-1 && (rc = read_probe(c, route, (double)plan[probe].m, whole_pieces >= 3 && !bounce, bytes_in, bytes_out, &st))) return rc;
     try { c->chunk_stamps.clear(); } catch (...) {}
-    if (timed_pieces) {
-        try {
-            c->chunk_stamps.resize(TK * timed_pieces);
-            for (size_t i = 0; i < TK * timed_pieces; i++) HIP_TRY(c, hipEventElapsedTime(&c->chunk_stamps[i], c->ticks[0], c->ticks[i]));
-        } catch (...) { c->chunk_stamps.clear(); }
-        for (size_t k = 0; k < timed_pieces; k++) {
-            float ms = 0;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[TK * k], c->ticks[TK * k + 1]));
-            st.h2d_ms += ms;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[TK * k + 2], c->ticks[TK * k + 3]));
-            st.d2h_ms += ms;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ticks[TK * k + 4], c->ticks[TK * k + 5]));
-            st.kernels_ms += ms;
-        }
-        float span = 0;
-        HIP_TRY(c, hipEventElapsedTime(&span, c->ticks[4], c->ticks[TK * (timed_pieces - 1) + 5]));
-        st.kernels_span_ms = span;
-        if (timed_h2d && timed_h2d < st.h2d_bytes) st.h2d_ms *= (double)st.h2d_bytes / (double)timed_h2d;
-        if (timed_d2h && timed_d2h < st.d2h_bytes) st.d2h_ms *= (double)st.d2h_bytes / (double)timed_d2h;
-    }
+    if (timed_pieces && (rc = read_chunk_timing(c, timed_pieces, timed_h2d, timed_d2h, &st))) return rc;
     c->host_stats = st;
     return FOURQ_OK;
+}
+int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch, size_t chunk_bounce, PipeReserve reserve) {
+    if (n_in > PIPE_MAX_ARRAYS || n_out > PIPE_MAX_ARRAYS || chunk == 0 || route.id < 0 || route.id >= PR_COUNT) return FOURQ_ERR_INVALID;
+    bool is_pin_in[PIPE_MAX_ARRAYS], is_pin_out[PIPE_MAX_ARRAYS], any_pageable = false;
+    for (int i = 0; i < n_in; i++) { is_pin_in[i] = is_pinned(in[i].src); any_pageable |= !is_pin_in[i]; }
+    for (int i = 0; i < n_out; i++) { is_pin_out[i] = is_pinned(out[i].dst); any_pageable |= !is_pin_out[i]; }
+    const bool uniform = any_pageable && c->host_bounce && chunk_bounce > chunk && n > chunk_bounce;
+    if (uniform) chunk = chunk_bounce;
+    if (chunk > n) chunk = n;
+    const size_t chunks = (n + chunk - 1) / chunk;
+    const bool direct_pageable = !c->host_bounce || chunks == 1;
+    PipeCall p = { c, in, n_in, out, n_out, n, launch, {}, {}, false };
+    fourq_host_stats st = {};
+    st.chunks = (uint32_t)chunks;
+    st.pinned_in = st.pinned_out = 1;
+    for (int i = 0; i < n_in; i++) { p.pin_in[i] = is_pin_in[i] || direct_pageable; p.bounce |= !p.pin_in[i]; st.pinned_in &= is_pin_in[i] ? 1 : 0; }
+    for (int i = 0; i < n_out; i++) { p.pin_out[i] = is_pin_out[i] || direct_pageable; p.bounce |= !p.pin_out[i]; st.pinned_out &= is_pin_out[i] ? 1 : 0; }
+    if (chunks > 1) return pipe_chunked(p, chunk, route, reserve, st);
+    const SlotLayout s = slot_layout(p, chunk);
+    return s.bytes <= ZERO_COPY_BYTES && c->host_zero_copy ? pipe_zero_copy(p, s, st) : pipe_single_chunk(p, s, st);
 }
 
 // chunk of a host-pointer batch: whole generations of the kernels that will run it
@@ -1180,7 +1209,7 @@ int dh_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* poi
     const double kt = table ? KT_DH_FIXED : (algo == ENDO ? KT_DH_VAR : KT_WIN_VAR + 0.3);
     return run_pipeline(c, in, 2, o, 2, n, unit, PipeRoute{ (table ? PR_DH_FIX : PR_DH_VAR) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
         return dh_dev(c, algo, (const uint64_t*)di[0], (const uint64_t*)di[1], table, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    }, pipe_chunk(c, fused), [&](size_t big) { return ensure_proj(c, big); });
+    }, pipe_chunk(c, fused), ensure_proj);
 }
 
 int table_host(fourq_ctx* c, int algo, const uint64_t* p_r1, uint64_t* table) {
@@ -1327,20 +1356,9 @@ FQ_API int fourq_ctx_destroy(fourq_ctx* c) {
     { CtxGuard last(c); }                      // a call still running on another thread finishes first; the caller must not start new ones
     DeviceGuard g(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->proj) (void)hipFree(c->proj);
-    if (c->table_limbs) (void)hipFree(c->table_limbs);
-    if (c->table_slots) (void)hipFree(c->table_slots);
-    if (c->table_packed) (void)hipFree(c->table_packed);
-    if (c->part_counter) (void)hipFree(c->part_counter);
-    if (c->part_list) (void)hipFree(c->part_list);
-    if (c->part_slot) (void)hipFree(c->part_slot);
-    if (c->part_fix) (void)hipFree(c->part_fix);
-    if (c->comb_limbs) (void)hipFree(c->comb_limbs);
-    if (c->comb_packed) (void)hipFree(c->comb_packed);
-    if (c->stage) (void)hipFree(c->stage);
-    if (c->work) (void)hipFree(c->work);
-    if (c->pipe_dev) (void)hipFree(c->pipe_dev);
+    for (void* p : { (void*)c->scratch, (void*)c->proj, (void*)c->table_limbs, (void*)c->table_slots, (void*)c->table_packed, (void*)c->part_counter, (void*)c->part_list,
+                     (void*)c->part_slot, (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, c->stage, (void*)c->work, (void*)c->pipe_dev })
+        if (p) (void)hipFree(p);
     if (c->pipe_pin) (void)hipHostFree(c->pipe_pin);
     if (c->zero_copy) (void)hipHostFree(c->zero_copy);
     if (c->diag_stamps) (void)hipFree(c->diag_stamps);
@@ -1397,15 +1415,9 @@ FQ_API int fourq_ctx_sync(fourq_ctx* c) {
 FQ_API int fourq_ctx_reserve(fourq_ctx* c, size_t n) {
     if (!c || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
     CtxGuard g(c);
-    int rc = ensure_proj(c, n);
-    if (rc) return rc;
-    size_t need = dh_bytes_work_bytes(n);
-    if (exchange_work_bytes(n) > need) need = exchange_work_bytes(n);
-    if (mul_affine_work_bytes(n) > need) need = mul_affine_work_bytes(n);
-    if (double_mul_work_bytes(n) > need) need = double_mul_work_bytes(n);
-    if (sig_work_bytes(n) > need) need = sig_work_bytes(n);
-    if (h2c_work_bytes(n) > need) need = h2c_work_bytes(n);
-    return ensure_work(c, need);
+    if (int rc = ensure_proj(c, n)) return rc;
+    using namespace fq_work;
+    return ensure_work(c, std::max({ DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n) }));
 }
 FQ_API int fourq_ctx_lanes(const fourq_ctx* c, size_t* lanes) {
     if (!c || !lanes) return FOURQ_ERR_INVALID;
@@ -1443,30 +1455,14 @@ FQ_API int fourq_dev_download(fourq_ctx* c, void* dst, const void* src, size_t b
 FQ_API int fourq_table_windowed(fourq_ctx* c, const uint64_t* p, uint64_t* t) { return table_host(c, WINDOWED, p, t); }
 FQ_API int fourq_table_endo(fourq_ctx* c, const uint64_t* p, uint64_t* t) { return table_host(c, ENDO, p, t); }
 
-FQ_API int fourq_mul_endo_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) {
-    return p ? mul_host(c, ENDO, s, p, nullptr, o, n) : FOURQ_ERR_INVALID;
-}
-FQ_API int fourq_mul_windowed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) {
-    return p ? mul_host(c, WINDOWED, s, p, nullptr, o, n) : FOURQ_ERR_INVALID;
-}
-FQ_API int fourq_mul_endo_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) {
-    return p ? mul_dev(c, ENDO, s, p, nullptr, o, nullptr, n) : FOURQ_ERR_INVALID;
-}
-FQ_API int fourq_mul_windowed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) {
-    return p ? mul_dev(c, WINDOWED, s, p, nullptr, o, nullptr, n) : FOURQ_ERR_INVALID;
-}
-FQ_API int fourq_mul_endo_fixed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) {
-    return t ? mul_host(c, ENDO, s, nullptr, t, o, n) : FOURQ_ERR_INVALID;
-}
-FQ_API int fourq_mul_windowed_fixed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) {
-    return t ? mul_host(c, WINDOWED, s, nullptr, t, o, n) : FOURQ_ERR_INVALID;
-}
-FQ_API int fourq_mul_endo_fixed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) {
-    return t ? mul_dev(c, ENDO, s, nullptr, t, o, nullptr, n) : FOURQ_ERR_INVALID;
-}
-FQ_API int fourq_mul_windowed_fixed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) {
-    return t ? mul_dev(c, WINDOWED, s, nullptr, t, o, nullptr, n) : FOURQ_ERR_INVALID;
-}
+FQ_API int fourq_mul_endo_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return p ? mul_host(c, ENDO, s, p, nullptr, o, n) : FOURQ_ERR_INVALID; }
+FQ_API int fourq_mul_windowed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return p ? mul_host(c, WINDOWED, s, p, nullptr, o, n) : FOURQ_ERR_INVALID; }
+FQ_API int fourq_mul_endo_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return p ? mul_dev(c, ENDO, s, p, nullptr, o, nullptr, n) : FOURQ_ERR_INVALID; }
+FQ_API int fourq_mul_windowed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return p ? mul_dev(c, WINDOWED, s, p, nullptr, o, nullptr, n) : FOURQ_ERR_INVALID; }
+FQ_API int fourq_mul_endo_fixed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) { return t ? mul_host(c, ENDO, s, nullptr, t, o, n) : FOURQ_ERR_INVALID; }
+FQ_API int fourq_mul_windowed_fixed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) { return t ? mul_host(c, WINDOWED, s, nullptr, t, o, n) : FOURQ_ERR_INVALID; }
+FQ_API int fourq_mul_endo_fixed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) { return t ? mul_dev(c, ENDO, s, nullptr, t, o, nullptr, n) : FOURQ_ERR_INVALID; }
+FQ_API int fourq_mul_windowed_fixed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* t, uint64_t* o, size_t n) { return t ? mul_dev(c, WINDOWED, s, nullptr, t, o, nullptr, n) : FOURQ_ERR_INVALID; }
 
 FQ_API int fourq_mul_endo_mixed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint8_t* flags,
                                           const uint64_t* table, uint64_t* o, size_t n) {
@@ -1554,18 +1550,10 @@ FQ_API int fourq_mul_endo_mixed_batch(fourq_ctx* c, const uint64_t* s, const uin
     }, c->split_chunk);
 }
 
-FQ_API int fourq_dh_endo_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) {
-    return dh_host(c, ENDO, s, p, t, o, st, n);
-}
-FQ_API int fourq_dh_windowed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) {
-    return dh_host(c, WINDOWED, s, p, t, o, st, n);
-}
-FQ_API int fourq_dh_endo_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) {
-    return dh_dev(c, ENDO, s, p, t, o, st, n);
-}
-FQ_API int fourq_dh_windowed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) {
-    return dh_dev(c, WINDOWED, s, p, t, o, st, n);
-}
+FQ_API int fourq_dh_endo_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) { return dh_host(c, ENDO, s, p, t, o, st, n); }
+FQ_API int fourq_dh_windowed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) { return dh_host(c, WINDOWED, s, p, t, o, st, n); }
+FQ_API int fourq_dh_endo_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) { return dh_dev(c, ENDO, s, p, t, o, st, n); }
+FQ_API int fourq_dh_windowed_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) { return dh_dev(c, WINDOWED, s, p, t, o, st, n); }
 
 FQ_API int fourq_comb_table(fourq_ctx* c, const uint64_t* p_r1, uint64_t* comb) {
     if (!c || !p_r1 || !comb) return FOURQ_ERR_INVALID;
@@ -1608,6 +1596,25 @@ FQ_API int fourq_comb_stage(fourq_ctx* c, const uint64_t* comb) {
     CtxGuard g(c);
     return stage_comb(c, comb);
 }
+// The one-lane comb.  Constant-time mode: 256-lane blocks, four per CU, over the small shape; otherwise one block per CU with the fast shape's
+// table.  proj != NULL defers the normalisation: (X, Y, Z) go to the context's projective planes.
+static int launch_comb(fourq_ctx* c, const uint64_t* scalars, uint64_t* out, uint8_t* status, uint4* proj, size_t n) {
+    const size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
+    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;
+    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, scalars, c->comb_limbs, out, status, proj, (u32)c->proj_capacity, (u32)n));
+    return FOURQ_OK;
+}
+// ... deferred for EVERY n, also the sizes fourq_comb_mul_batch_dev gives to comb_quad_kernel; the caller has sized the planes (ensure_proj)
+static int launch_comb_deferred(fourq_ctx* c, const uint64_t* scalars, uint8_t* status, size_t n) { return launch_comb(c, scalars, nullptr, status, c->proj, n); }
+// comb -> normalize -> encode: [k_i]B as 32-byte strings through `affine` (key generation's public keys, a signature's R)
+static int comb_encode(fourq_ctx* c, const uint64_t* scalars, uint64_t* affine, uint8_t* st_comb, uint8_t* out32, size_t n) {
+    if (int rc = launch_comb_deferred(c, scalars, st_comb, n)) return rc;
+    const int group = normalize_group(c, n);
+    HIPRC_TRY(c, chain_launch_normalize(group ? group : 1, c->stream, c->proj, (u32)c->proj_capacity, affine, st_comb, (u32)n));
+    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, affine, (u64*)out32, (u32)n);
+    HIP_TRY(c, hipGetLastError());
+    return FOURQ_OK;
+}
 FQ_API int fourq_comb_mul_batch_dev(fourq_ctx* c, const uint64_t* scalars, const uint64_t* comb, uint64_t* out, uint8_t* status, size_t n) {
     if (!c || !scalars || !out || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
     if (!aligned16(scalars) || !aligned16(out)) return FOURQ_ERR_INVALID;
@@ -1618,9 +1625,8 @@ FQ_API int fourq_comb_mul_batch_dev(fourq_ctx* c, const uint64_t* scalars, const
     // At most a quarter generation, selection by address: four lanes per element, entries gathered where the table lies (kernels.hip.h,
     // comb_quad_kernel): a batch of one 0.107 -> 0.05x ms (profiles/r03_quadlane.txt)
     if (!group && n <= c->pair_max) {         // two lanes per element between a quarter and half a generation: 0.100 -> 0.06x ms
-        const bool quad = n <= c->quad_max;
-        const size_t per_block = BLOCK / (quad ? 4 : 2);
-        const unsigned grid = (unsigned)((n + per_block - 1) / per_block);
+        bool quad;
+        const unsigned grid = pair_grid(c, n, false, &quad);
         if (c->ct) {
             HIPRC_TRY(c, ct_launch_comb_quad(quad, grid, c->stream, scalars, c->comb_limbs, out, status, (u32)n));
             return FOURQ_OK;
@@ -1632,11 +1638,7 @@ FQ_API int fourq_comb_mul_batch_dev(fourq_ctx* c, const uint64_t* scalars, const
     }
     int rc = group ? ensure_proj(c, n) : FOURQ_OK;
     if (rc) return rc;
-    size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
-    // constant-time mode: 256-lane blocks, four per CU, over the small shape; otherwise one block per CU with the fast shape's table
-    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;
-    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, scalars, c->comb_limbs, out, status,
-                                                             group ? c->proj : nullptr, (u32)c->proj_capacity, (u32)n));
+    if ((rc = launch_comb(c, scalars, out, status, group ? c->proj : nullptr, n))) return rc;
     if (group) HIPRC_TRY(c, chain_launch_normalize(group, c->stream, c->proj, (u32)c->proj_capacity, out, status, (u32)n));
     return FOURQ_OK;
 }
@@ -1698,16 +1700,12 @@ static int dh_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const u
     if (!aligned16(scalars) || !aligned16(keys32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    const size_t nb = align256(n);
-    int rc = ensure_work(c, dh_bytes_work_bytes(n));
+    int rc = ensure_work(c, fq_work::DhBytes::bytes(n));       // the planes only if dh_dev defers: not reserve_dh_bytes
     if (rc) return rc;
-    uint64_t* pts = (uint64_t*)c->work;                       // decoded public keys
-    uint64_t* shared = (uint64_t*)(c->work + n * 64);         // affine shared points
-    uint8_t* st_decode = (uint8_t*)(c->work + 2 * n * 64);
-    uint8_t* st_dh = st_decode + nb;
-    if ((rc = fourq_decode_batch_dev(c, keys32, pts, st_decode, n))) return rc;
-    if ((rc = dh_dev(c, algo, scalars, pts, table, shared, st_dh, n))) return rc;    // an undecodable key is (0, 0): rejected again here
-    hipLaunchKernelGGL(encode_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, shared, st_decode, st_dh,
+    const fq_work::DhBytes w(c->work, n);
+    if ((rc = fourq_decode_batch_dev(c, keys32, w.pts, w.st_decode, n))) return rc;
+    if ((rc = dh_dev(c, algo, scalars, w.pts, table, w.shared, w.st_dh, n))) return rc;    // an undecodable key is (0, 0): rejected again here
+    hipLaunchKernelGGL(encode_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, w.shared, w.st_decode, w.st_dh,
                        (u64*)out32, status, (u32)n);
     HIP_TRY(c, hipGetLastError());
     return FOURQ_OK;
@@ -1724,7 +1722,7 @@ static int dh_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const 
     const double kt = (table ? KT_DH_FIXED : (algo == ENDO ? KT_DH_VAR : KT_WIN_VAR + 0.3)) + KT_CODEC;
     return run_pipeline(c, in, 2, o, 2, n, unit, PipeRoute{ (table ? PR_DHB_FIX : PR_DHB_VAR) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
         return dh_bytes_dev(c, algo, (const uint64_t*)di[0], (const uint8_t*)di[1], table, (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, pipe_chunk(c, fused), [&](size_t big) { if (int r = ensure_proj(c, big)) return r; return ensure_work(c, dh_bytes_work_bytes(big)); });
+    }, pipe_chunk(c, fused), reserve_dh_bytes);
 }
 // ---- MUL_* with affine / encoded I/O: R1toAffine(MUL_<algo>(m, AffineToR1(P))) and encode(.) of it --------------------------
 // 160 (96) bytes per operation across the ABI instead of the raw-R1 form's 352: the host-array calls are bound by the link, not by the
@@ -1734,13 +1732,10 @@ static int launch_lower(fourq_ctx* c, bool enc, const uint64_t* r1, u32 stride, 
     const bool batched = n > 2 * c->lanes;
     const size_t lanes = batched ? (n + 3) / 4 : n;
     const unsigned grid = (unsigned)((lanes + BLOCK - 1) / BLOCK);
-    if (enc) {
-        if (batched) hipLaunchKernelGGL((lower_kernel<4, true>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
-        else hipLaunchKernelGGL((lower_kernel<1, true>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
-    } else {
-        if (batched) hipLaunchKernelGGL((lower_kernel<4, false>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
-        else hipLaunchKernelGGL((lower_kernel<1, false>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
-    }
+    if (enc && batched) hipLaunchKernelGGL((lower_kernel<4, true>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
+    else if (enc) hipLaunchKernelGGL((lower_kernel<1, true>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
+    else if (batched) hipLaunchKernelGGL((lower_kernel<4, false>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
+    else hipLaunchKernelGGL((lower_kernel<1, false>), dim3(grid), dim3(BLOCK), 0, c->stream, r1, stride, st_decode, out, status, (u32)n);
     HIP_TRY(c, hipGetLastError());
     return FOURQ_OK;
 }
@@ -1748,24 +1743,38 @@ static int launch_lower(fourq_ctx* c, bool enc, const uint64_t* r1, u32 stride, 
 // then the lane lifts its own point and leaves the three coordinates R1toAffine reads -- no lift kernel, no R1 rows.  Batches with a
 // two-lane tail or on the two-kernel route keep the separate lift and full R1 rows (FOURQ_FUSED_IO=0, a test hook, forces that everywhere).
 static bool fused_io(const fourq_ctx* c, int algo, size_t n) { return c->fused_io && variable_route(c, algo, false, n, false) == ROUTE_FUSED; }
+// The ladder half that MUL_* with affine / encoded I/O and [k]B + [l]P share: prepares the ladder's input rows and runs MUL_<algo> into rows_out.
+// Where the whole batch runs on the fused kernels the lanes lift their own points and leave (X, Y, Z): encoded points are decoded to affine rows,
+// affine ones read where they lie, and *stride, the words per row of rows_out, is 12; otherwise decode + lift / lift to full R1 rows, and 20.
+static int mul_rows_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const void* points, bool encoded, uint64_t* rows_in, uint64_t* rows_out,
+                        uint8_t* st_decode, size_t n, u32* stride) {
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const bool fused = fused_io(c, algo, n);
+    const uint64_t* ladder_in = rows_in;
+    if (encoded) {
+        if (fused) hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, st_decode, (u32)n);
+        else hipLaunchKernelGGL(decode_lift_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, st_decode, (u32)n);
+        HIP_TRY(c, hipGetLastError());
+    } else if (fused) {
+        ladder_in = (const uint64_t*)points;
+    } else {
+        hipLaunchKernelGGL(lift_affine_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, (u32)n);
+        HIP_TRY(c, hipGetLastError());
+    }
+    *stride = fused ? 12 : 20;
+    return mul_dev(c, algo, scalars, ladder_in, nullptr, rows_out, nullptr, n, fused ? (LADDER_IO_AFFINE_IN | LADDER_IO_XYZ_OUT) : 0);
+}
 static int mul_affine_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
     if (!c || !scalars || !points_affine || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
     if (!aligned16(scalars) || !aligned16(points_affine) || !aligned16(out_affine)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, mul_affine_work_bytes(n));
+    int rc = reserve_mul_rows(c, n);
     if (rc) return rc;
-    uint64_t* r1_in = (uint64_t*)c->work;
-    uint64_t* r1_out = (uint64_t*)(c->work + n * 160);
-    if (fused_io(c, algo, n)) {
-        if ((rc = mul_dev(c, algo, scalars, points_affine, nullptr, r1_out, nullptr, n, LADDER_IO_AFFINE_IN | LADDER_IO_XYZ_OUT))) return rc;
-        return launch_lower(c, false, r1_out, 12, nullptr, out_affine, nullptr, n);
-    }
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(lift_affine_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, points_affine, r1_in, (u32)n);
-    HIP_TRY(c, hipGetLastError());
-    if ((rc = mul_dev(c, algo, scalars, r1_in, nullptr, r1_out, nullptr, n))) return rc;
-    return launch_lower(c, false, r1_out, 20, nullptr, out_affine, nullptr, n);
+    const fq_work::MulRows w(c->work, n);
+    u32 stride;
+    if ((rc = mul_rows_dev(c, algo, scalars, points_affine, false, w.rows_in, w.rows_out, nullptr, n, &stride))) return rc;
+    return launch_lower(c, false, w.rows_out, stride, nullptr, out_affine, nullptr, n);
 }
 static int mul_affine_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
     if (!c || !scalars || !points_affine || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
@@ -1775,7 +1784,7 @@ static int mul_affine_host(fourq_ctx* c, int algo, const uint64_t* scalars, cons
     PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
     return run_pipeline(c, in, 2, o, 1, n, pipe_chunk(c, true), PipeRoute{ PR_AFF + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
         return mul_affine_dev(c, algo, (const uint64_t*)di[0], (const uint64_t*)di[1], (uint64_t*)dout[0], m);
-    }, 0, [&](size_t big) { return ensure_work(c, mul_affine_work_bytes(big)); });
+    }, 0, reserve_mul_rows);
 }
 // decode -> MUL_<algo> -> encode.  status: 0 ok | 16 + FOURQ_DECODE_* (out32 is zero then); MUL_* itself cannot fail.
 static int mul_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
@@ -1783,22 +1792,12 @@ static int mul_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const 
     if (!aligned16(scalars) || !aligned16(points32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, mul_affine_work_bytes(n));
+    int rc = reserve_mul_rows(c, n);
     if (rc) return rc;
-    uint64_t* r1_in = (uint64_t*)c->work;                       // decoded (and lifted) points
-    uint64_t* r1_out = (uint64_t*)(c->work + n * 160);
-    uint8_t* st_decode = (uint8_t*)(c->work + 2 * n * 160 + n * 64);
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    if (fused_io(c, algo, n)) {                                 // decode to affine rows; the ladder's lanes lift them and leave (X, Y, Z)
-        hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points32, r1_in, st_decode, (u32)n);
-        HIP_TRY(c, hipGetLastError());
-        if ((rc = mul_dev(c, algo, scalars, r1_in, nullptr, r1_out, nullptr, n, LADDER_IO_AFFINE_IN | LADDER_IO_XYZ_OUT))) return rc;
-        return launch_lower(c, true, r1_out, 12, st_decode, (uint64_t*)out32, status, n);
-    }
-    hipLaunchKernelGGL(decode_lift_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points32, r1_in, st_decode, (u32)n);
-    HIP_TRY(c, hipGetLastError());
-    if ((rc = mul_dev(c, algo, scalars, r1_in, nullptr, r1_out, nullptr, n))) return rc;
-    return launch_lower(c, true, r1_out, 20, st_decode, (uint64_t*)out32, status, n);
+    const fq_work::MulRows w(c->work, n);
+    u32 stride;
+    if ((rc = mul_rows_dev(c, algo, scalars, points32, true, w.rows_in, w.rows_out, w.st_decode, n, &stride))) return rc;
+    return launch_lower(c, true, w.rows_out, stride, w.st_decode, (uint64_t*)out32, status, n);
 }
 static int mul_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
     if (!c || !scalars || !points32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
@@ -1808,7 +1807,7 @@ static int mul_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const
     PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
     return run_pipeline(c, in, 2, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_BYTES + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER + KT_CODEC }, [&](char* const* di, char* const* dout, size_t m) {
         return mul_bytes_dev(c, algo, (const uint64_t*)di[0], (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, [&](size_t big) { return ensure_work(c, mul_affine_work_bytes(big)); });
+    }, 0, reserve_mul_rows);
 }
 FQ_API int fourq_mul_endo_affine_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return mul_affine_dev(c, ENDO, s, p, o, n); }
 FQ_API int fourq_mul_windowed_affine_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return mul_affine_dev(c, WINDOWED, s, p, o, n); }
@@ -1819,18 +1818,10 @@ FQ_API int fourq_mul_windowed_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, c
 FQ_API int fourq_mul_endo_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t n) { return mul_bytes_host(c, ENDO, s, p, o, st, n); }
 FQ_API int fourq_mul_windowed_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t n) { return mul_bytes_host(c, WINDOWED, s, p, o, st, n); }
 
-FQ_API int fourq_dh_endo_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) {
-    return dh_bytes_dev(c, ENDO, s, k, t, o, st, n);
-}
-FQ_API int fourq_dh_windowed_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) {
-    return dh_bytes_dev(c, WINDOWED, s, k, t, o, st, n);
-}
-FQ_API int fourq_dh_endo_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) {
-    return dh_bytes_host(c, ENDO, s, k, t, o, st, n);
-}
-FQ_API int fourq_dh_windowed_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) {
-    return dh_bytes_host(c, WINDOWED, s, k, t, o, st, n);
-}
+FQ_API int fourq_dh_endo_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) { return dh_bytes_dev(c, ENDO, s, k, t, o, st, n); }
+FQ_API int fourq_dh_windowed_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) { return dh_bytes_dev(c, WINDOWED, s, k, t, o, st, n); }
+FQ_API int fourq_dh_endo_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) { return dh_bytes_host(c, ENDO, s, k, t, o, st, n); }
+FQ_API int fourq_dh_windowed_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* k, const uint64_t* t, uint8_t* o, uint8_t* st, size_t n) { return dh_bytes_host(c, WINDOWED, s, k, t, o, st, n); }
 
 // dh_exchange: DH_endo(a_i, DH_endo(b_i, base [, table392])) with the first half's public keys kept on the device
 FQ_API int fourq_dh_exchange_batch_dev(fourq_ctx* c, const uint64_t* a, const uint64_t* b, const uint64_t* base_affine, const uint64_t* table392,
@@ -1839,19 +1830,17 @@ FQ_API int fourq_dh_exchange_batch_dev(fourq_ctx* c, const uint64_t* a, const ui
     if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, exchange_work_bytes(n));
+    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_exchange
     if (rc) return rc;
-    uint64_t* base = (uint64_t*)c->work;                      // the base point, once per exchange
-    uint64_t* mid = (uint64_t*)(c->work + n * 64);            // DH(b_i, base): the public keys
-    uint8_t* st_first = (uint8_t*)(c->work + 2 * n * 64);
+    const fq_work::Exchange w(c->work, n);                     // mid = DH(b_i, base): the public keys
     AffineArg point;
     memcpy(point.w, base_affine, sizeof point.w);             // read once, here: the launch carries it
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(broadcast_point_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, point, base, (u32)n);
+    hipLaunchKernelGGL(broadcast_point_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, point, w.base_pts, (u32)n);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = dh_dev(c, ENDO, b, base, table392, mid, st_first, n))) return rc;
-    if ((rc = dh_dev(c, ENDO, a, mid, nullptr, out, status, n))) return rc;
-    hipLaunchKernelGGL(merge_status_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, st_first, status, (u32)n);
+    if ((rc = dh_dev(c, ENDO, b, w.base_pts, table392, w.mid, w.st_first, n))) return rc;
+    if ((rc = dh_dev(c, ENDO, a, w.mid, nullptr, out, status, n))) return rc;
+    hipLaunchKernelGGL(merge_status_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, w.st_first, status, (u32)n);
     HIP_TRY(c, hipGetLastError());
     return FOURQ_OK;
 }
@@ -1867,7 +1856,7 @@ FQ_API int fourq_dh_exchange_batch(fourq_ctx* c, const uint64_t* a, const uint64
     // one generation of the fixed-base half (two waves per SIMD) = two of the variable-base half (one wave per SIMD)
     return run_pipeline(c, in, 2, o, 2, n, c->lanes_w4 / 2, PipeRoute{ PR_EXCH + (table392 ? 1 : 0), (table392 ? KT_DH_FIXED : KT_DH_VAR) + KT_DH_VAR }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_dh_exchange_batch_dev(c, (const uint64_t*)di[0], (const uint64_t*)di[1], base_copy, table392, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    }, c->lanes_w4, [&](size_t big) { if (int r = ensure_proj(c, big)) return r; return ensure_work(c, exchange_work_bytes(big)); });
+    }, c->lanes_w4, reserve_exchange);
 }
 
 // dh_exchange with the key-generation half through the comb (bench.py's cfg4 step as one call)
@@ -1876,13 +1865,12 @@ FQ_API int fourq_dh_exchange_comb_batch_dev(fourq_ctx* c, const uint64_t* a, con
     if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, exchange_work_bytes(n));
+    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_exchange
     if (rc) return rc;
-    uint64_t* mid = (uint64_t*)(c->work + n * 64);            // [b_i]B: the public keys (same place as in fourq_dh_exchange_batch_dev)
-    uint8_t* st_first = (uint8_t*)(c->work + 2 * n * 64);
-    if ((rc = fourq_comb_mul_batch_dev(c, b, comb, mid, st_first, n))) return rc;
-    if ((rc = dh_dev(c, ENDO, a, mid, nullptr, out, status, n))) return rc;
-    hipLaunchKernelGGL(merge_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, st_first, status, (u32)n);
+    const fq_work::Exchange w(c->work, n);                     // mid = [b_i]B: the public keys
+    if ((rc = fourq_comb_mul_batch_dev(c, b, comb, w.mid, w.st_first, n))) return rc;
+    if ((rc = dh_dev(c, ENDO, a, w.mid, nullptr, out, status, n))) return rc;
+    hipLaunchKernelGGL(merge_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, w.st_first, status, (u32)n);
     HIP_TRY(c, hipGetLastError());
     return FOURQ_OK;
 }
@@ -1895,7 +1883,7 @@ FQ_API int fourq_dh_exchange_comb_batch(fourq_ctx* c, const uint64_t* a, const u
     PipeArray o[2] = { { nullptr, (char*)out, 64 }, { nullptr, (char*)status, 1 } };
     return run_pipeline(c, in, 2, o, 2, n, c->lanes_w4 / 2, PipeRoute{ PR_EXCH_COMB, KT_COMB + KT_DH_VAR }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_dh_exchange_comb_batch_dev(c, (const uint64_t*)di[0], (const uint64_t*)di[1], nullptr, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    }, c->lanes_w4, [&](size_t big) { if (int r = ensure_proj(c, big)) return r; return ensure_work(c, exchange_work_bytes(big)); });
+    }, c->lanes_w4, reserve_exchange);
 }
 
 // ---- [k]B + [l]P: the curve part of a Schnorr-type verification (R' = [s]B + [h]A) -------------------------------------------
@@ -1916,51 +1904,22 @@ static int double_mul_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb,
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = ensure_proj(c, n))) return rc;
-    if ((rc = ensure_work(c, double_mul_work_bytes(n)))) return rc;
-    uint64_t* rows_in = (uint64_t*)c->work;                     // affine (fused I/O) or R1 rows of the decoded / lifted points
-    uint64_t* rows_out = (uint64_t*)(c->work + n * 160);        // the ladder's result rows
-    uint8_t* st_decode = (uint8_t*)(c->work + 2 * n * 160);
-    uint8_t* st_comb = st_decode + align256(n);                 // comb_kernel<true> writes FOURQ_DH_OK per element; nobody reads it here
+    if ((rc = reserve_double_mul(c, n))) return rc;
+    const fq_work::DoubleMul w(c->work, n);
     // (1) [k_i]B, projective
-    const size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
-    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;      // as fourq_comb_mul_batch_dev
-    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, k, c->comb_limbs, nullptr, st_comb, c->proj, (u32)c->proj_capacity, (u32)n));
+    if ((rc = launch_comb_deferred(c, k, w.st_comb, n))) return rc;
     // (2) [l_i]P_i, projective
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    const bool fused = fused_io(c, ENDO, n);
-    const uint64_t* ladder_in = rows_in;
-    if (encoded) {
-        if (fused) hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, st_decode, (u32)n);
-        else hipLaunchKernelGGL(decode_lift_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, st_decode, (u32)n);
-        HIP_TRY(c, hipGetLastError());
-    } else if (fused) {
-        ladder_in = (const uint64_t*)points;
-    } else {
-        hipLaunchKernelGGL(lift_affine_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, (u32)n);
-        HIP_TRY(c, hipGetLastError());
-    }
-    if ((rc = mul_dev(c, ENDO, l, ladder_in, nullptr, rows_out, nullptr, n, fused ? (LADDER_IO_AFFINE_IN | LADDER_IO_XYZ_OUT) : 0))) return rc;
+    u32 stride;
+    if ((rc = mul_rows_dev(c, ENDO, l, points, encoded, w.rows_in, w.rows_out, w.st_decode, n, &stride))) return rc;
     // (3) the sum, lowered
-    HIPRC_TRY(c, chain_launch_combine(n > 2 * c->lanes ? 2 : 1, out_kind, c->stream, c->proj, (u32)c->proj_capacity, rows_out, fused ? 12 : 20,
-                                      encoded ? st_decode : nullptr, (const u64*)expect32, (u64*)out, status, ok, (u32)n));
+    HIPRC_TRY(c, chain_launch_combine(n > 2 * c->lanes ? 2 : 1, out_kind, c->stream, c->proj, (u32)c->proj_capacity, w.rows_out, stride,
+                                      encoded ? w.st_decode : nullptr, (const u64*)expect32, (u64*)out, status, ok, (u32)n));
     return FOURQ_OK;
 }
-static int double_mul_reserve(fourq_ctx* c, size_t big) {
-    if (int r = ensure_proj(c, big)) return r;
-    return ensure_work(c, double_mul_work_bytes(big));
-}
 constexpr double KT_DOUBLE = KT_COMB + KT_ENDO_VAR + KT_LIFT_LOWER;
-FQ_API int fourq_double_mul_affine_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
-    return double_mul_dev(c, k, comb, l, points_affine, false, COMBINE_AFFINE, nullptr, out_affine, nullptr, nullptr, n);
-}
-FQ_API int fourq_double_mul_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
-    return double_mul_dev(c, k, comb, l, points32, true, COMBINE_ENCODE, nullptr, out32, status, nullptr, n);
-}
-FQ_API int fourq_verify_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, const uint8_t* expect32,
-                                        uint8_t* ok, uint8_t* status, size_t n) {
-    return double_mul_dev(c, k, comb, l, points32, true, COMBINE_VERIFY, expect32, nullptr, status, ok, n);
-}
+FQ_API int fourq_double_mul_affine_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* p, uint64_t* o, size_t n) { return double_mul_dev(c, k, comb, l, p, false, COMBINE_AFFINE, nullptr, o, nullptr, nullptr, n); }
+FQ_API int fourq_double_mul_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* p, uint8_t* o, uint8_t* st, size_t n) { return double_mul_dev(c, k, comb, l, p, true, COMBINE_ENCODE, nullptr, o, st, nullptr, n); }
+FQ_API int fourq_verify_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* p, const uint8_t* expect32, uint8_t* ok, uint8_t* st, size_t n) { return double_mul_dev(c, k, comb, l, p, true, COMBINE_VERIFY, expect32, nullptr, st, ok, n); }
 FQ_API int fourq_double_mul_affine_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
     if (!c || !k || !l || !points_affine || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
@@ -1970,7 +1929,7 @@ FQ_API int fourq_double_mul_affine_batch(fourq_ctx* c, const uint64_t* k, const 
     PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
     return run_pipeline(c, in, 3, o, 1, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_AFF, KT_DOUBLE }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_double_mul_affine_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint64_t*)di[2], (uint64_t*)dout[0], m);
-    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
+    }, 0, reserve_double_mul);
 }
 FQ_API int fourq_double_mul_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
     if (!c || !k || !l || !points32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
@@ -1981,7 +1940,7 @@ FQ_API int fourq_double_mul_bytes_batch(fourq_ctx* c, const uint64_t* k, const u
     PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
     return run_pipeline(c, in, 3, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_BYTES, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_double_mul_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
+    }, 0, reserve_double_mul);
 }
 FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, const uint8_t* expect32,
                                     uint8_t* ok, uint8_t* status, size_t n) {
@@ -1993,7 +1952,7 @@ FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint6
     PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
     return run_pipeline(c, in, 4, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_VERIFY, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_verify_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (const uint8_t*)di[3], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
+    }, 0, reserve_double_mul);
 }
 
 // ---- signatures from bytes (include/fourq_amd.h): SHA-512 and the arithmetic modulo N on the device (sig.hip.h) around the comb, the
@@ -2032,21 +1991,10 @@ FQ_API int fourq_sig_keygen_batch_dev(fourq_ctx* c, const uint8_t* sk32, const u
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = ensure_proj(c, n))) return rc;
-    if ((rc = ensure_work(c, sig_work_bytes(n)))) return rc;
-    uint64_t* a = (uint64_t*)c->work;
-    uint64_t* affine = (uint64_t*)(c->work + 3 * n * 32);
-    uint8_t* st_comb = (uint8_t*)(c->work + 3 * n * 32 + n * 64);
-    HIPRC_TRY(c, sig_launch_nonce(c->stream, false, sk32, SigMsgs{ nullptr, 0, nullptr, 0 }, a, nullptr, (u32)n));
-    // [a]G through the comb with deferred normalisation, as the first stage of double_mul_dev; the projective neutral would need a = 0 mod N
-    const size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
-    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;
-    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, a, c->comb_limbs, nullptr, st_comb, c->proj, (u32)c->proj_capacity, (u32)n));
-    const int group = normalize_group(c, n);
-    HIPRC_TRY(c, chain_launch_normalize(group ? group : 1, c->stream, c->proj, (u32)c->proj_capacity, affine, st_comb, (u32)n));
-    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, affine, (u64*)pk32, (u32)n);
-    HIP_TRY(c, hipGetLastError());
-    return FOURQ_OK;
+    if ((rc = reserve_sig(c, n))) return rc;
+    const fq_work::Sig w(c->work, n);
+    HIPRC_TRY(c, sig_launch_nonce(c->stream, false, sk32, SigMsgs{ nullptr, 0, nullptr, 0 }, w.a, nullptr, (u32)n));
+    return comb_encode(c, w.a, w.affine, w.st_comb, pk32, n);      // [a]G; the projective neutral would need a = 0 mod N
 }
 FQ_API int fourq_sig_sign_batch_dev(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb,
                                     const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* sig64, size_t n) {
@@ -2056,23 +2004,12 @@ FQ_API int fourq_sig_sign_batch_dev(fourq_ctx* c, const uint8_t* sk32, const uin
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = ensure_proj(c, n))) return rc;
-    if ((rc = ensure_work(c, sig_work_bytes(n)))) return rc;
-    uint64_t* a = (uint64_t*)c->work;
-    uint64_t* r = (uint64_t*)(c->work + n * 32);
-    uint8_t* r32 = (uint8_t*)(c->work + 2 * n * 32);
-    uint64_t* affine = (uint64_t*)(c->work + 3 * n * 32);
-    uint8_t* st_comb = (uint8_t*)(c->work + 3 * n * 32 + n * 64);
+    if ((rc = reserve_sig(c, n))) return rc;
+    const fq_work::Sig w(c->work, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
-    HIPRC_TRY(c, sig_launch_nonce(c->stream, true, sk32, m, a, r, (u32)n));
-    const size_t blocks = (n + BLOCK - 1) / BLOCK, blocks_max = c->lanes_w4 / BLOCK;
-    const unsigned grid_or_cus = c->ct ? (unsigned)(blocks < blocks_max ? blocks : blocks_max) : (unsigned)c->cus;
-    HIPRC_TRY(c, (c->ct ? ct_launch_comb : chain_launch_comb)(grid_or_cus, c->stream, r, c->comb_limbs, nullptr, st_comb, c->proj, (u32)c->proj_capacity, (u32)n));
-    const int group = normalize_group(c, n);
-    HIPRC_TRY(c, chain_launch_normalize(group ? group : 1, c->stream, c->proj, (u32)c->proj_capacity, affine, st_comb, (u32)n));
-    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, affine, (u64*)r32, (u32)n);
-    HIP_TRY(c, hipGetLastError());
-    HIPRC_TRY(c, sig_launch_finish(c->stream, r32, pk32, m, a, r, sig64, (u32)n));
+    HIPRC_TRY(c, sig_launch_nonce(c->stream, true, sk32, m, w.a, w.r, (u32)n));
+    if ((rc = comb_encode(c, w.r, w.affine, w.st_comb, w.r32, n))) return rc;
+    HIPRC_TRY(c, sig_launch_finish(c->stream, w.r32, pk32, m, w.a, w.r, sig64, (u32)n));
     return FOURQ_OK;
 }
 FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
@@ -2083,36 +2020,36 @@ FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const u
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = ensure_proj(c, n))) return rc;
-    if ((rc = ensure_work(c, double_mul_work_bytes(n)))) return rc;        // the same size double_mul_dev asks for: it will not move the buffer
-    char* base = c->work + double_mul_rows_bytes(n);
-    uint64_t* s = (uint64_t*)base;
-    uint64_t* h = (uint64_t*)(base + n * 32);
-    uint64_t* r32 = (uint64_t*)(base + 2 * n * 32);
-    uint8_t* pre = (uint8_t*)(base + 3 * n * 32);
-    HIPRC_TRY(c, sig_launch_challenge(c->stream, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, s, h, r32, pre, (u32)n));
-    if ((rc = double_mul_dev(c, s, nullptr, h, pk32, true, COMBINE_VERIFY, (const uint8_t*)r32, nullptr, status, ok, n))) return rc;
-    HIPRC_TRY(c, sig_launch_merge(c->stream, pre, ok, status, (u32)n));
+    if ((rc = reserve_double_mul(c, n))) return rc;                         // SigVerify is DoubleMul with its tail carved: double_mul_dev below asks for the same and moves nothing
+    const fq_work::SigTail w = fq_work::SigVerify(c->work, n).sig;
+    HIPRC_TRY(c, sig_launch_challenge(c->stream, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w.s, w.h, w.r32, w.pre, (u32)n));
+    if ((rc = double_mul_dev(c, w.s, nullptr, w.h, pk32, true, COMBINE_VERIFY, (const uint8_t*)w.r32, nullptr, status, ok, n))) return rc;
+    HIPRC_TRY(c, sig_launch_merge(c->stream, w.pre, ok, status, (u32)n));
     return FOURQ_OK;
 }
 
-// host-pointer twins: a message matrix is one more array of `stride` bytes per element (left out when stride is 0), the lengths one of four
+// host-pointer twins: a message matrix is one more array of `stride` bytes per element (left out when stride is 0), the lengths one of four.
+// MsgArrays appends whichever of the two the caller gave to the call's input arrays and finds them again among a chunk's device pointers.
+struct MsgArrays {
+    int i_msg = -1, i_len = -1;
+    MsgArrays(PipeArray* in, int* n_in, const uint8_t* msgs, size_t stride, const uint32_t* lens) {
+        if (stride) { i_msg = *n_in; in[(*n_in)++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
+        if (lens) { i_len = *n_in; in[(*n_in)++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    }
+    const uint8_t* msgs(char* const* di) const { return i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg]; }
+    const uint32_t* lens(char* const* di) const { return i_len < 0 ? nullptr : (const uint32_t*)di[i_len]; }
+};
 FQ_API int fourq_sha512_batch(fourq_ctx* c, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* out64, size_t n) {
     if (!c || !out64 || n > FOURQ_MAX_BATCH || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
     PipeArray in[2];
-    int n_in = 0, i_msg = -1, i_len = -1;
-    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
-    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    int n_in = 0;
+    const MsgArrays ma(in, &n_in, msgs, stride, lens);
     PipeArray o[1] = { { nullptr, (char*)out64, 64 } };
     return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(4 * c->lanes_w4, stride), PipeRoute{ PR_SHA512, sig_kt_hash(stride, 0) }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_sha512_batch_dev(c, i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg], stride, i_len < 0 ? nullptr : (const uint32_t*)di[i_len], msg_len, (uint8_t*)dout[0], m);
+        return fourq_sha512_batch_dev(c, ma.msgs(di), stride, ma.lens(di), msg_len, (uint8_t*)dout[0], m);
     });
-}
-static int sig_reserve(fourq_ctx* c, size_t big) {
-    if (int r = ensure_proj(c, big)) return r;
-    return ensure_work(c, sig_work_bytes(big));
 }
 FQ_API int fourq_sig_keygen_batch(fourq_ctx* c, const uint8_t* sk32, const uint64_t* comb, uint8_t* pk32, size_t n) {
     if (!c || !sk32 || !pk32 || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
@@ -2123,7 +2060,7 @@ FQ_API int fourq_sig_keygen_batch(fourq_ctx* c, const uint8_t* sk32, const uint6
     PipeArray o[1] = { { nullptr, (char*)pk32, 32 } };
     return run_pipeline(c, in, 1, o, 1, n, c->lanes_w4, PipeRoute{ PR_SIG_KEYGEN, KT_COMB + KT_SHA_BLOCK + KT_ENCODE }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_sig_keygen_batch_dev(c, (const uint8_t*)di[0], nullptr, (uint8_t*)dout[0], m);
-    }, 0, [&](size_t big) { return sig_reserve(c, big); });
+    }, 0, reserve_sig);
 }
 FQ_API int fourq_sig_sign_batch(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb,
                                 const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* sig64, size_t n) {
@@ -2132,15 +2069,13 @@ FQ_API int fourq_sig_sign_batch(fourq_ctx* c, const uint8_t* sk32, const uint8_t
     CtxGuard g(c);
     if (int rc = stage_comb(c, comb)) return rc;
     PipeArray in[4] = { { (const char*)sk32, nullptr, 32 }, { (const char*)pk32, nullptr, 32 } };
-    int n_in = 2, i_msg = -1, i_len = -1;
-    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
-    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    int n_in = 2;
+    const MsgArrays ma(in, &n_in, msgs, stride, lens);
     PipeArray o[1] = { { nullptr, (char*)sig64, 64 } };
     const double kt = KT_COMB + KT_ENCODE + KT_SHA_BLOCK + sig_kt_hash(stride, 32) + sig_kt_hash(stride, 64);
     return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(c->lanes_w4, stride), PipeRoute{ PR_SIG_SIGN, kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_sig_sign_batch_dev(c, (const uint8_t*)di[0], (const uint8_t*)di[1], nullptr, i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg], stride,
-                                        i_len < 0 ? nullptr : (const uint32_t*)di[i_len], msg_len, (uint8_t*)dout[0], m);
-    }, 0, [&](size_t big) { return sig_reserve(c, big); });
+        return fourq_sig_sign_batch_dev(c, (const uint8_t*)di[0], (const uint8_t*)di[1], nullptr, ma.msgs(di), stride, ma.lens(di), msg_len, (uint8_t*)dout[0], m);
+    }, 0, reserve_sig);
 }
 FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
                                   const uint8_t* sig64, uint8_t* ok, uint8_t* status, size_t n) {
@@ -2149,14 +2084,12 @@ FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint6
     CtxGuard g(c);
     if (int rc = stage_comb(c, comb)) return rc;
     PipeArray in[4] = { { (const char*)pk32, nullptr, 32 }, { (const char*)sig64, nullptr, 64 } };
-    int n_in = 2, i_msg = -1, i_len = -1;
-    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
-    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    int n_in = 2;
+    const MsgArrays ma(in, &n_in, msgs, stride, lens);
     PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
     return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c, true), stride), PipeRoute{ PR_SIG_VERIFY, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_sig_verify_batch_dev(c, (const uint8_t*)di[0], nullptr, i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg], stride,
-                                          i_len < 0 ? nullptr : (const uint32_t*)di[i_len], msg_len, (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, [&](size_t big) { return double_mul_reserve(c, big); });
+        return fourq_sig_verify_batch_dev(c, (const uint8_t*)di[0], nullptr, ma.msgs(di), stride, ma.lens(di), msg_len, (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
+    }, 0, reserve_double_mul);
 }
 
 // ---- bytes to a point (include/fourq_amd.h, "hash to curve"): expand_message_xmd + hash_to_field in one kernel, the map, the addition, the
@@ -2190,21 +2123,15 @@ static int hash_to_curve_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, i
     if (!c || !out || n > FOURQ_MAX_BATCH || !aligned16(out) || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    if (int rc = ensure_work(c, h2c_work_bytes(n))) return rc;
+    if (int rc = reserve_h2c(c, n)) return rc;
     const int count = mode == FOURQ_H2C_RO ? 2 : 1;
-    uint64_t* u = (uint64_t*)c->work;
+    uint64_t* u = fq_work::H2c(c->work, n).u;
     HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), u, (u32)n));
     HIPRC_TRY(c, h2c_launch_ell2(c->stream, count, out_kind, u, (uint64_t*)out, (u32)n));
     return FOURQ_OK;
 }
-FQ_API int fourq_hash_to_curve_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
-                                         uint8_t* out32, size_t n) {
-    return hash_to_curve_dev(c, dst, dst_len, mode, msgs, stride, lens, msg_len, H2C_OUT_BYTES, out32, n);
-}
-FQ_API int fourq_hash_to_curve_affine_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
-                                                uint64_t* out_affine, size_t n) {
-    return hash_to_curve_dev(c, dst, dst_len, mode, msgs, stride, lens, msg_len, H2C_OUT_AFFINE, out_affine, n);
-}
+FQ_API int fourq_hash_to_curve_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint8_t* o, size_t n) { return hash_to_curve_dev(c, dst, dl, mode, m, st, ln, ml, H2C_OUT_BYTES, o, n); }
+FQ_API int fourq_hash_to_curve_affine_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint64_t* o, size_t n) { return hash_to_curve_dev(c, dst, dl, mode, m, st, ln, ml, H2C_OUT_AFFINE, o, n); }
 // host-pointer twins; what = 0: hash_to_field (out: count x 32 bytes per row), 1: 32-byte points, 2: affine words
 static int h2c_host(fourq_ctx* c, int what, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, void* out, size_t n) {
     if (!c || !out || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
@@ -2212,31 +2139,19 @@ static int h2c_host(fourq_ctx* c, int what, const uint8_t* dst, size_t dst_len, 
     CtxGuard g(c);
     const int count = mode == FOURQ_H2C_RO ? 2 : 1;
     PipeArray in[2];
-    int n_in = 0, i_msg = -1, i_len = -1;
-    if (stride) { i_msg = n_in; in[n_in++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
-    if (lens) { i_len = n_in; in[n_in++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
+    int n_in = 0;
+    const MsgArrays ma(in, &n_in, msgs, stride, lens);
     PipeArray o[1] = { { nullptr, (char*)out, what == 0 ? (size_t)32 * count : what == 1 ? (size_t)32 : (size_t)64 } };
     const double kt = h2c_kt_hash(stride, dst_len, count) + (what == 0 ? 0.0 : count * KT_ELL2 + KT_LIFT_LOWER);
     const PipeRoute route{ what == 0 ? PR_H2F : (what == 1 ? PR_H2C : PR_H2C_AFFINE) + mode, kt };
     return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(what == 0 ? 4 * c->lanes_w4 : pipe_chunk(c, true), stride), route, [&](char* const* di, char* const* dout, size_t m) {
-        const uint8_t* dm = i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg];
-        const uint32_t* dl = i_len < 0 ? nullptr : (const uint32_t*)di[i_len];
-        if (what == 0) return fourq_hash_to_field_batch_dev(c, dst, dst_len, mode, dm, stride, dl, msg_len, (uint64_t*)dout[0], m);
-        return hash_to_curve_dev(c, dst, dst_len, mode, dm, stride, dl, msg_len, what == 1 ? H2C_OUT_BYTES : H2C_OUT_AFFINE, dout[0], m);
-    }, 0, [&](size_t big) { return what == 0 ? FOURQ_OK : ensure_work(c, h2c_work_bytes(big)); });
+        if (what == 0) return fourq_hash_to_field_batch_dev(c, dst, dst_len, mode, ma.msgs(di), stride, ma.lens(di), msg_len, (uint64_t*)dout[0], m);
+        return hash_to_curve_dev(c, dst, dst_len, mode, ma.msgs(di), stride, ma.lens(di), msg_len, what == 1 ? H2C_OUT_BYTES : H2C_OUT_AFFINE, dout[0], m);
+    }, 0, what == 0 ? nullptr : reserve_h2c);
 }
-FQ_API int fourq_hash_to_field_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
-                                     uint64_t* out_u, size_t n) {
-    return h2c_host(c, 0, dst, dst_len, mode, msgs, stride, lens, msg_len, out_u, n);
-}
-FQ_API int fourq_hash_to_curve_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
-                                     uint8_t* out32, size_t n) {
-    return h2c_host(c, 1, dst, dst_len, mode, msgs, stride, lens, msg_len, out32, n);
-}
-FQ_API int fourq_hash_to_curve_affine_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
-                                            uint64_t* out_affine, size_t n) {
-    return h2c_host(c, 2, dst, dst_len, mode, msgs, stride, lens, msg_len, out_affine, n);
-}
+FQ_API int fourq_hash_to_field_batch(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint64_t* o, size_t n) { return h2c_host(c, 0, dst, dl, mode, m, st, ln, ml, o, n); }
+FQ_API int fourq_hash_to_curve_batch(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint8_t* o, size_t n) { return h2c_host(c, 1, dst, dl, mode, m, st, ln, ml, o, n); }
+FQ_API int fourq_hash_to_curve_affine_batch(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint64_t* o, size_t n) { return h2c_host(c, 2, dst, dl, mode, m, st, ln, ml, o, n); }
 FQ_API int fourq_map_to_curve_batch(fourq_ctx* c, const uint64_t* u, uint64_t* out_affine, size_t n) {
     if (!c || !u || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;

@@ -1,0 +1,23 @@
+// prints every work-buffer layout for n elements: ./work_layout_dump n  ->  lines "layout region offset" and "layout bytes total"
+#include <cstdio>
+#include <cstdlib>
+#include "work_layout.h"
+static char* const BASE = reinterpret_cast<char*>(uintptr_t(1) << 44);      // never dereferenced: the layouts only compute addresses
+static void region(const char* layout, const char* name, const void* p) { printf("%s %s %zu\n", layout, name, (size_t)(static_cast<const char*>(p) - BASE)); }
+#define REGION(layout, w, member) region(layout, #member, w.member)
+int main(int argc, char** argv) {
+    if (argc != 2) return 2;
+    const size_t n = strtoull(argv[1], 0, 10);
+    using namespace fq_work;
+    { const DhBytes w(BASE, n); REGION("dh_bytes", w, pts); REGION("dh_bytes", w, shared); REGION("dh_bytes", w, st_decode); REGION("dh_bytes", w, st_dh); }
+    { const Exchange w(BASE, n); REGION("exchange", w, base_pts); REGION("exchange", w, mid); REGION("exchange", w, st_first); }
+    { const MulRows w(BASE, n); REGION("mul_rows", w, rows_in); REGION("mul_rows", w, rows_out); REGION("mul_rows", w, unused); REGION("mul_rows", w, st_decode); }
+    { const DoubleMul w(BASE, n); REGION("double_mul", w, rows_in); REGION("double_mul", w, rows_out); REGION("double_mul", w, st_decode); REGION("double_mul", w, st_comb); REGION("double_mul", w, tail); }
+    { const SigVerify w(BASE, n); REGION("sig_verify", w, rows_in); REGION("sig_verify", w, rows_out); REGION("sig_verify", w, st_decode); REGION("sig_verify", w, st_comb);
+      REGION("sig_verify", w, sig.s); REGION("sig_verify", w, sig.h); REGION("sig_verify", w, sig.r32); REGION("sig_verify", w, sig.pre); }
+    { const Sig w(BASE, n); REGION("sig", w, a); REGION("sig", w, r); REGION("sig", w, r32); REGION("sig", w, affine); REGION("sig", w, st_comb); }
+    { const H2c w(BASE, n); REGION("h2c", w, u); }
+    printf("dh_bytes bytes %zu\nexchange bytes %zu\nmul_rows bytes %zu\ndouble_mul bytes %zu\nsig_verify bytes %zu\nsig bytes %zu\nh2c bytes %zu\n",
+           DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), DoubleMul::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n));
+    return 0;
+}
