@@ -423,6 +423,14 @@ EXPORT void fqo_r1_to_affine_batch(const u64 *points_r1, u64 *out_affine, size_t
 EXPORT void fqo_decompose_batch(const u64 *scalars, u64 *out, size_t n) {
     for (size_t i = 0; i < n; i++) decompose(scalars + 4 * i, out + 4 * i);
 }
+/* recode(decompose(m)) (curve4q.py:358-380): 65 sign bits, then 65 digits, one byte each. */
+EXPORT void fqo_recode_batch(const u64 *scalars, uint8_t *out, size_t n) {
+    for (size_t i = 0; i < n; i++) { u64 v[4]; decompose(scalars + 4 * i, v); recode(v, out + 130 * i, out + 130 * i + 65); }
+}
+/* The fixed-window digits of MUL_windowed (curve4q.py:216-226): 63 signs (1 = positive), then 63 indices (|d| - 1) / 2. */
+EXPORT void fqo_windowed_batch(const u64 *scalars, uint8_t *out, size_t n) {
+    for (size_t i = 0; i < n; i++) recode_windowed(scalars + 4 * i, out + 126 * i, out + 126 * i + 63);
+}
 EXPORT int fqo_num_threads(void) {
 #ifdef _OPENMP
     extern int omp_get_max_threads(void);

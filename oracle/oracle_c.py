@@ -31,12 +31,15 @@ def lib():
         _lib.fqo_mul_batch.argtypes = [i, vp, vp, vp, vp, sz]
         _lib.fqo_dh_batch.argtypes = [i, vp, vp, vp, vp, vp, sz]
         _lib.fqo_decompose_batch.argtypes = [vp, vp, sz]
+        _lib.fqo_recode_batch.argtypes = [vp, vp, sz]
+        _lib.fqo_windowed_batch.argtypes = [vp, vp, sz]
         _lib.fqo_r1_to_affine_batch.argtypes = [vp, vp, sz]
         _lib.fqo_r1_to_affine_batch.restype = None
         _lib.fqo_num_threads.restype = ctypes.c_int
         _lib.fqo_set_num_threads.argtypes = [i]
         _lib.fqo_set_num_threads.restype = None
-        for f in (_lib.fqo_table_windowed, _lib.fqo_table_endo, _lib.fqo_mul_batch, _lib.fqo_dh_batch, _lib.fqo_decompose_batch):
+        for f in (_lib.fqo_table_windowed, _lib.fqo_table_endo, _lib.fqo_mul_batch, _lib.fqo_dh_batch, _lib.fqo_decompose_batch,
+                  _lib.fqo_recode_batch, _lib.fqo_windowed_batch):
             f.restype = None
     return _lib
 
@@ -101,6 +104,22 @@ def decompose(scalars):
     out = np.empty_like(s)
     lib().fqo_decompose_batch(_p(s), _p(out), len(s))
     return out
+
+
+def recode(scalars):
+    """recode(decompose(m)) of every row -> ((n, 65) sign bits, (n, 65) digits), uint8."""
+    s = _u64(scalars, 4)
+    out = np.empty((len(s), 130), dtype=np.uint8)
+    lib().fqo_recode_batch(_p(s), _p(out), len(s))
+    return out[:, :65], out[:, 65:]
+
+
+def windowed(scalars):
+    """The fixed-window digits of every row -> ((n, 63) signs, (n, 63) indices), uint8, as curve4q_oracle.recode_windowed."""
+    s = _u64(scalars, 4)
+    out = np.empty((len(s), 126), dtype=np.uint8)
+    lib().fqo_windowed_batch(_p(s), _p(out), len(s))
+    return out[:, :63], out[:, 63:]
 
 
 def num_threads():
