@@ -482,8 +482,9 @@ template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename P> 
     r.Tb = H;
     return r;
 }
-// The same addition with the entry's coordinates already in registers (as loaded: N, D not yet exchanged and F not yet
-// negated for a negated entry): lets a lone wave issue its HBM gathers a whole doubling ahead of their use.
+// An entry's coordinates in registers, as loaded (N, D not yet exchanged and F not yet negated for a negated entry): the
+// operand of the generated addition (add_asm, ladder_asm.hip.h).  Loading them ahead lets a lone wave issue its HBM gathers a
+// whole doubling before their use.
 struct EntryRegs {
     Fe2<1> N, D, E, F;
 };
@@ -491,38 +492,13 @@ struct EntryRegs {
 template <typename L = LimbSlots, typename P, typename EF> FQ_DEV EntryRegs load_entry(const P* entry, u32 neg_mask, u32 digit, const EF& ef) {
     EntryRegs t;
     (void)neg_mask;
-    load_nd<L>(entry, t.N, t.D);                                    // the sign is applied by add_entry, behind the doubling
+    load_nd<L>(entry, t.N, t.D);                                    // the sign is applied by add_asm, behind the doubling
     if constexpr (EF::ON) {
         t.E = ef.get(digit, 0); t.F = ef.get(digit, 1);
     } else {
         t.E = L::load(entry + 2 * L::COORD); t.F = L::load(entry + 3 * L::COORD);
     }
     return t;
-}
-template <int CH> FQ_DEV R1 add_entry(const R1& q, const EntryRegs& t, u32 neg_mask) {
-    // The masked exchange of N and D must not be scheduled next to the gathers (hipcc does that when it may, and the lone
-    // wave then sits out the gather latency at the top of every step: measured -7 % on the headline kernel).  The mask is
-    // made to depend on the doubled point, so the twenty selects can only issue once the doubling has been computed.
-    asm("" : "+v"(neg_mask) : "v"(q.X.re.l[0]), "v"(q.Y.re.l[0]), "v"(q.Z.re.l[0]));
-    const Fe2<1> tN = fe2_bitselect(neg_mask, t.D, t.N), tD = fe2_bitselect(neg_mask, t.N, t.D);
-    Fe2<1> T = fe2_mulx<CH>(q.Ta, q.Tb);
-    Fe2<2> N1 = fe2_add(q.X, q.Y);
-    Fe2<3> D1 = fe2_subx<CH>(q.Y, q.X);
-    Fe2<1> A = fe2_mulx<CH>(D1, tD);
-    Fe2<1> B = fe2_mulx<CH>(N1, tN);
-    Fe2<1> C = fe2_mulx<CH>(fe2_cnegx<CH>(t.F, neg_mask), T);
-    Fe2<1> D = fe2_mulx<CH>(t.E, q.Z);
-    Fe2<3> E = fe2_subx<CH>(B, A);
-    Fe2<3> F = fe2_subx<CH>(D, C);
-    Fe2<2> G = fe2_add(D, C);
-    Fe2<2> H = fe2_add(B, A);
-    R1 r;
-    r.X = fe2_mulx<CH>(E, F);
-    r.Z = fe2_mulx<CH>(G, F);
-    r.Y = fe2_mulx<CH>(G, H);
-    r.Ta = widen<4>(E);
-    r.Tb = H;
-    return r;
 }
 // Q + (+-A) for a precomputed AFFINE point A = (x+y, y-x, 2d*x*y) read from `entry` (three coordinates of
 // COORD_U32 dwords): ADD_core with the table point's 2Z = 2, i.e. D = 2*Z1 costs no multiplication.  Used by
@@ -707,30 +683,7 @@ template <typename EFT> struct ScanSplit {
         return fe2_from_limbs(out);
     }
 };
-// Q + (+-T[digit]), every entry read: the constant-time form of add_table
-template <int CH, typename SRC> FQ_DEV R1 add_scan(const R1& q, const SRC& src, u32 digit_value, u32 neg_mask) {
-    const typename SRC::Bits digit(digit_value);
-    Fe2<1> T = fe2_mulx<CH>(q.Ta, q.Tb);
-    Fe2<2> N1 = fe2_add(q.X, q.Y);
-    Fe2<3> D1 = fe2_subx<CH>(q.Y, q.X);
-    Fe2<1> tN = src.coord(digit, 0), tD = src.coord(digit, 1);
-    fe2_cswap(tN, tD, neg_mask);                                   // R2neg: (D, N, E, -F)
-    Fe2<1> A = fe2_mulx<CH>(D1, tD);
-    Fe2<1> B = fe2_mulx<CH>(N1, tN);
-    Fe2<1> C = fe2_mulx<CH>(fe2_cnegx<CH>(src.coord(digit, 3), neg_mask), T);
-    Fe2<1> D = fe2_mulx<CH>(src.coord(digit, 2), q.Z);
-    Fe2<3> E = fe2_subx<CH>(B, A);
-    Fe2<3> F = fe2_subx<CH>(D, C);
-    Fe2<2> G = fe2_add(D, C);
-    Fe2<2> H = fe2_add(B, A);
-    R1 r;
-    r.X = fe2_mulx<CH>(E, F);
-    r.Z = fe2_mulx<CH>(G, F);
-    r.Y = fe2_mulx<CH>(G, H);
-    r.Ta = widen<4>(E);
-    r.Tb = H;
-    return r;
-}
+// the ladder's starting point with every entry read: the constant-time form of start_table
 template <typename SRC> FQ_DEV Proj<1, 1, 1> start_scan(const SRC& src, u32 digit_value, u32 neg_mask) {
     const typename SRC::Bits digit(digit_value);
     Fe2<1> N = src.coord(digit, 0), D = src.coord(digit, 1);

@@ -779,7 +779,7 @@ int dh_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* poin
     int group = normalize_group(c, n);
     if (!table) {                                  // the prep + ladder route always defers; the fused kernels from two generations on (K = 2, 4, 8), except
         const Route route = variable_route(c, algo, true, n, false);     // with a two-lane tail, whose kernels invert in place
-        group = route == ROUTE_SPLIT ? (group ? group : 1) : (route == ROUTE_FUSED && FQ_FUSED_DEFER ? group : 0);
+        group = route == ROUTE_SPLIT ? (group ? group : 1) : (route == ROUTE_FUSED ? group : 0);
     }
     int rc = group ? ensure_proj(c, n) : FOURQ_OK;
     if (rc) return rc;

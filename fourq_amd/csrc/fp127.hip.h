@@ -36,11 +36,6 @@ typedef int64_t i64;
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 0
 #endif
-// FQ_MUL_ASM=1: in a translation unit with FQ_CHAIN=0 the GF(p^2) products and squares of the unsigned flavour are the generated
-// instruction streams FQ_ASM_MULU / FQ_ASM_SQRU (ladder_asm.hip.h, tools/asmgen/gen_ladder_step.py): no fences, no hazard nops.
-#ifndef FQ_MUL_ASM
-#define FQ_MUL_ASM 1
-#endif
 
 constexpr u32 LIMB_BITS = 26;
 constexpr u32 LIMB_MASK = (1u << LIMB_BITS) - 1;
@@ -260,7 +255,9 @@ template <int MODE, int A, int B> FQ_DEV Fe2<1> fe2_mulx(const Fe2<A>& a, const 
     else if constexpr (MODE == 1) return fe2_mul_chain(a, b);
     else return fe2_mul_plain(a, b);
 }
-constexpr int FE2_DEFAULT_MODE = (FQ_CHAIN != 0) ? 1 : ((FQ_MUL_ASM != 0) ? 3 : 0);
+// FQ_CHAIN=0 units: the unsigned products and squares are the generated instruction streams FQ_ASM_MULU / FQ_ASM_SQRU
+// (ladder_asm.hip.h, tools/asmgen/gen_ladder_step.py): no fences, no hazard nops.  Mode 0 remains for the primitive kernels' dbl<0> / add_table<0>.
+constexpr int FE2_DEFAULT_MODE = (FQ_CHAIN != 0) ? 1 : 3;
 template <int A, int B> FQ_DEV Fe2<1> fe2_mul(const Fe2<A>& a, const Fe2<B>& b) { return fe2_mulx<FE2_DEFAULT_MODE>(a, b); }
 // (a0 + a1 i)^2 = (a0 + a1)(a0 - a1) + (2 a0 a1) i                               fields.py:176-181
 template <int A> FQ_DEV Fe2<1> fe2_sqr_chain(const Fe2<A>& a) {

@@ -49,7 +49,7 @@ struct LdsEF {
     }
     FQ_DEV void put(int k, const R2& t) const { put1(k, 0, t.E); put1(k, 1, t.F); }
     // The ten rows of an entry whose E, F are not there yet are free storage: table_endo parks its working values in them
-    // (build_table_endo_lds) instead of making round trips through the HBM slot.
+    // (build_table_endo_lds_asm) instead of making round trips through the HBM slot.
     FQ_DEV void park_nd(int k, const Fe2<1>& n, const Fe2<1>& d) const { put1(k, 0, n); put1(k, 1, d); }
     FQ_DEV void unpark_nd(int k, Fe2<1>& n, Fe2<1>& d) const { n = get((u32)k, 0); d = get((u32)k, 1); }
     FQ_DEV void park_xyz(int k, const Fe2<1>& x, const Fe2<1>& y, const Fe2<1>& z) const { put1(k, 0, x); put1(k, 1, y); put1(k + 1, 0, z); }
@@ -268,34 +268,16 @@ template <typename L = LimbSlots> FQ_DEV void build_table_endo_pipelined(const R
 }
 
 // ---- the ladders -------------------------------------------------------------------------------
-// Every ladder runs the products with chained carries on SIGNED limbs (CH = 2, fp127.hip.h "signed flavour": 5 % fewer
-// instructions per step; per-kernel A/Bs in DESIGN.md section 9 -- round 1 adopted it for the LDS and mixed-batch ladders,
-// round 2's layouts made it pay in the fused and the split ladders too).
-// The fused kernels run one wave per SIMD: their ladder preloads the entry of a step into registers a whole doubling ahead
-// (PRELOAD; measured 0.416 ms per 2^16 batch against 0.423 with plain products and 0.463 chained without the preload: hipcc
-// cannot hoist loads across the opaque partial sums).
+// Every ladder runs the products with chained carries on SIGNED limbs (fp127.hip.h "signed flavour": 5 % fewer instructions per
+// step; per-kernel A/Bs in DESIGN.md section 9), in one of two forms:
+//   CH = 3          the step as hand-scheduled asm bodies (ladder_asm.hip.h, tools/asmgen/gen_ladder_step.py), the entry in registers,
+//                   requested a doubling ahead.  The fused kernels, whose lone wave per SIMD pays for every issue slot
+//                   (profiles/r04_ladder_step.txt); the fixed-base ladders with the table in LDS and the two-kernel route's MUL ladder
+//                   (256 VGPRs, two waves per SIMD instead of four; mixed batches +3.7 %); the constant-time ladders, where the
+//                   whole-table scan (select trees, compiler code) produces the entry and the bodies consume it.
+//   CH = LADDER_CH  hipcc's step on the same limbs, the entry read inside the addition: the two-kernel route's DH ladder, whose gathers
+//                   run at the memory system's pace -- it loses 2.5-4 % with two wave slots and keeps four -- and the comb.
 constexpr int LADDER_CH = 2;
-// CH = 3: the same signed DAG as hand-scheduled asm bodies (ladder_asm.hip.h, tools/asmgen/gen_ladder_step.py): the fused
-// kernels' ladders, whose lone wave per SIMD pays for every issue slot (profiles/r04_ladder_step.txt).
-#ifndef FQ_LADDER_ASM
-#define FQ_LADDER_ASM 1
-#endif
-// the fixed-base ladders (table in LDS) on the same bodies: 256 VGPRs, two waves per SIMD instead of four
-#ifndef FQ_LDS_ASM
-#define FQ_LDS_ASM 1
-#endif
-// the two-kernel route's MUL ladder likewise (the packed entry requested a doubling ahead, unpacked behind it): mixed batches
-// +3.7 %; its DH flavour, whose gathers run at the memory system's pace, loses 2.5-4 % with two wave slots and keeps four
-#ifndef FQ_PREBUILT_ASM
-#define FQ_PREBUILT_ASM 1
-#endif
-// the constant-time ladders on the asm bodies: the whole-table scan (select trees, compiler code) produces the entry, the bodies consume it
-#ifndef FQ_CT_LDS_ASM
-#define FQ_CT_LDS_ASM 1
-#endif
-#ifndef FQ_CT_FUSED_ASM
-#define FQ_CT_FUSED_ASM 1
-#endif
 // TOUCH: the two-kernel route's ladder reads a lane's table entry (one 128-byte line of its scratch slot) inside the
 // addition, with no registers to spare for issuing the eight loads a doubling ahead (128-VGPR budget).  A one-dword load of the
 // line at the top of the step, result unused, starts the HBM / Infinity-Cache fetch early: the real loads then hit L2.
@@ -311,7 +293,7 @@ template <typename TP> FQ_DEV u32 touch_line(const TP* p) {
     return landing;
 }
 FQ_DEV void touch_done(u32 landing, u32& after) { asm volatile("" : "+v"(after) : "v"(landing)); }
-// a ladder on signed limbs (CH == 2) hands its result back with non-negative limbs
+// a ladder on signed limbs (CH >= 2) hands its result back with non-negative limbs
 template <int CH> FQ_DEV R1 ladder_result(const R1& Q) {
     if constexpr (CH >= 2) {
         R1 r;
@@ -322,26 +304,25 @@ template <int CH> FQ_DEV R1 ladder_result(const R1& Q) {
         return Q;
     }
 }
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, bool PRELOAD = false, typename L = LimbSlots, typename EF = NoEF, bool TOUCH = false, typename TP> FQ_DEV R1 ladder_endo(const EndoDigits& e, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:436-442
+// the ladder's first value: the starting entry (start_table / start_scan) as an R1 tuple, T = X * Y
+FQ_DEV R1 ladder_start(const Proj<1, 1, 1>& q4) {
+    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
+    return Q;
+}
+template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, bool TOUCH = false, typename TP> FQ_DEV R1 ladder_endo(const EndoDigits& e, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:436-442
     Proj<1, 1, 1> q4 = start_table<L>(tbl + (e.top & 7) * stride, 0u);        // s[64] = 1: the entry itself
     if constexpr (EF::ON) q4.Z = ef.get(e.top & 7, 0);
-    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
+    R1 Q = ladder_start(q4);
 #pragma unroll 1
     for (int i = 63; i >= 0; i--) {
         const u32 digit = endo_digit(e, i);
         const TP* entry = tbl + digit * stride;
         if constexpr (CH == 3) {                  // the hand-scheduled bodies (ladder_asm.hip.h); the entry is requested ahead of the doubling
-            static_assert(PRELOAD, "the asm bodies take the entry in registers");
             const u32 neg = endo_neg_mask(e, i);
             EntryRegs t = load_entry<L>(entry, neg, digit, ef);
             Fe2<1> T;
             dblt_asm(Q.X, Q.Y, Q.Z, T);
             add_asm(Q, T, t, neg);
-        } else if (PRELOAD) {
-            const u32 neg = endo_neg_mask(e, i);
-            EntryRegs t = load_entry<L>(entry, neg, digit, ef);
-            Q = dbl<CH>(Q.X, Q.Y, Q.Z);
-            Q = add_entry<CH>(Q, t, neg);
         } else {
             u32 landing = 0;
             if (TOUCH) landing = touch_line(entry);
@@ -352,26 +333,15 @@ template <int CH = (FQ_CHAIN != 0) ? 1 : 0, bool PRELOAD = false, typename L = L
     }
     return ladder_result<CH>(Q);
 }
-// The fused kernels' ladder on the nibble stream (recode_nibbles) and with the lane's entries addressed as a 32-bit dword offset on the
-// kernel's scratch pointer (`base` is wave-uniform: the loads take it as their scalar base).  Same steps, same bodies, same R1 tuple as
-// ladder_endo<3, true, L, EF>; what changes is the glue between the bodies: per step one bit-field extract, one arithmetic shift (the
-// negation mask), one shift of the stream and two multiply-adds for the two addresses, instead of four 64-bit shifts, five bit
-// operations, two multiplications and a 64-bit address addition.
-#ifndef FQ_NIBBLE_LADDER
-#define FQ_NIBBLE_LADDER 1
-#endif
-// DH batches of at least two generations on the fused kernels leave (X, Y, Z) for normalize_kernel<K> as the other routes do (round 6), instead
-// of inverting per element at one wave per SIMD
-#ifndef FQ_FUSED_DEFER
-#define FQ_FUSED_DEFER 1
-#endif
+// The MUL_endo ladder on the nibble stream (recode_nibbles): same steps, same bodies, same R1 tuple as ladder_endo<3, L, EF>; what changes
+// is the glue between the bodies: per step one bit-field extract, one arithmetic shift (the negation mask) and one shift of the stream,
+// instead of four 64-bit shifts and five bit operations.  `at(digit)` is the address of an entry.
 // SIGNED_OUT: hand the ladder's point back on signed limbs (bound 1 each) -- for store_r1_signed, which folds the bias into the canonical
 // reduction of the final store
-template <typename L, typename EF, bool SIGNED_OUT = false> FQ_DEV R1 ladder_endo_nibbles(const EndoNibbles& e, const u32* base, u32 lane_off, const EF& ef) {   // curve4q.py:436-442
-    static_assert(EF::ON, "the fused kernels' ladder: E, F in the lane's LDS rows");
-    Proj<1, 1, 1> q4 = start_table<L>(base + (size_t)(lane_off + (e.top & 7) * (u32)L::ENTRY), 0u);     // s[64] = 1: the entry itself
-    q4.Z = ef.get(e.top & 7, 0);
-    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
+template <typename L, typename EF, bool SIGNED_OUT, typename AT> FQ_DEV R1 ladder_endo_nibbles_by(const EndoNibbles& e, const AT& at, const EF& ef) {   // curve4q.py:436-442
+    Proj<1, 1, 1> q4 = start_table<L>(at(e.top & 7), 0u);                         // s[64] = 1: the entry itself
+    if constexpr (EF::ON) q4.Z = ef.get(e.top & 7, 0);
+    R1 Q = ladder_start(q4);
     u32 w[8];
 #pragma unroll
     for (int t = 0; t < 8; t++) w[t] = e.w[t];
@@ -385,7 +355,7 @@ template <typename L, typename EF, bool SIGNED_OUT = false> FQ_DEV R1 ladder_end
             const u32 digit = (cur >> 28) & 7;                                    // top nibble, bits 0..2
             const u32 neg = (u32)((int32_t)cur >> 31);                            // its bit 3, spread: ~0 when the step subtracts
             cur <<= 4;
-            EntryRegs t = load_entry<L>(base + (size_t)(lane_off + digit * (u32)L::ENTRY), neg, digit, ef);
+            EntryRegs t = load_entry<L>(at(digit), neg, digit, ef);
             Fe2<1> T;
             dblt_asm(Q.X, Q.Y, Q.Z, T);
             add_asm(Q, T, t, neg);
@@ -393,6 +363,18 @@ template <typename L, typename EF, bool SIGNED_OUT = false> FQ_DEV R1 ladder_end
     }
     if constexpr (SIGNED_OUT) return Q;
     else return ladder_result<3>(Q);
+}
+// The fused kernels: the lane's entries addressed as a 32-bit dword offset on the kernel's scratch pointer (`base` is wave-uniform: the
+// loads take it as their scalar base) -- two multiply-adds for the two addresses of a step instead of two multiplications and a 64-bit
+// address addition.
+template <typename L, typename EF, bool SIGNED_OUT = false> FQ_DEV R1 ladder_endo_nibbles(const EndoNibbles& e, const u32* base, u32 lane_off, const EF& ef) {
+    static_assert(EF::ON, "the fused kernels' ladder: E, F in the lane's LDS rows");
+    return ladder_endo_nibbles_by<L, EF, SIGNED_OUT>(e, [=](u32 d) { return base + (size_t)(lane_off + d * (u32)L::ENTRY); }, ef);
+}
+// Any table a pointer and an entry stride describe -- the shared fixed-base table in LDS (ladder_kernel<ENDO, LDS>) or in global memory
+// (the fixed-base items of mixed_queue_kernel): ladder_endo's addressing.
+template <typename L, typename EF, typename TP> FQ_DEV R1 ladder_endo_nibbles_at(const EndoNibbles& e, const TP* tbl, int stride, const EF& ef = EF()) {
+    return ladder_endo_nibbles_by<L, EF, false>(e, [=](u32 d) { return tbl + d * stride; }, ef);
 }
 // canonical words of a point the asm bodies left on SIGNED limbs (every limb of every coordinate within bound 1): bias, then fe_canon's
 // own carry -- what ladder_result<3> + store_r1 compute, with one carry chain per field element less
@@ -402,56 +384,23 @@ template <int B> FQ_DEV void store_fe2_signed(u64* w, const Fe2<B>& a) {
 FQ_DEV void store_r1_signed(u64* w, const R1& q) {
     store_fe2_signed(w, q.X); store_fe2_signed(w + 4, q.Y); store_fe2_signed(w + 8, q.Z); store_fe2_signed(w + 12, q.Ta); store_fe2_signed(w + 16, q.Tb);
 }
-// The same ladder over any table a pointer and an entry stride describe -- the shared fixed-base table in LDS (ladder_kernel<ENDO, LDS>) or in
-// global memory (the fixed-base items of mixed_queue_kernel): the nibble stream's glue with ladder_endo's addressing.
-template <typename L, typename EF, typename TP> FQ_DEV R1 ladder_endo_nibbles_at(const EndoNibbles& e, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:436-442
-    Proj<1, 1, 1> q4 = start_table<L>(tbl + (e.top & 7) * stride, 0u);
-    if constexpr (EF::ON) q4.Z = ef.get(e.top & 7, 0);
-    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
-    u32 w[8];
-#pragma unroll
-    for (int t = 0; t < 8; t++) w[t] = e.w[t];
-#pragma unroll 1
-    for (int k = 0; k < 8; k++) {
-        u32 cur = w[7];
-#pragma unroll
-        for (int t = 7; t > 0; t--) w[t] = w[t - 1];
-#pragma unroll 1
-        for (int j = 0; j < 8; j++) {
-            const u32 digit = (cur >> 28) & 7;
-            const u32 neg = (u32)((int32_t)cur >> 31);
-            cur <<= 4;
-            EntryRegs t = load_entry<L>(tbl + digit * stride, neg, digit, ef);
-            Fe2<1> T;
-            dblt_asm(Q.X, Q.Y, Q.Z, T);
-            add_asm(Q, T, t, neg);
-        }
-    }
-    return ladder_result<3>(Q);
-}
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, bool PRELOAD = false, typename L = LimbSlots, typename EF = NoEF, bool TOUCH = false, typename TP> FQ_DEV R1 ladder_windowed(const WinScalar& w, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:228-235
+template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, bool TOUCH = false, typename TP> FQ_DEV R1 ladder_windowed(const WinScalar& w, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:228-235
     u32 code = win_top_code(w);
     Proj<1, 1, 1> q4 = start_table<L>(tbl + (code & 7) * stride, (code >> 3) - 1u);
     if constexpr (EF::ON) q4.Z = ef.get(code & 7, 0);
-    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
+    R1 Q = ladder_start(q4);
 #pragma unroll 1
     for (int i = 61; i >= 0; i--) {
         code = win_code_from_window(win_window(w, i));
         const TP* entry = tbl + (code & 7) * stride;
         const u32 neg = (code >> 3) - 1u;
         if constexpr (CH == 3) {
-            static_assert(PRELOAD, "the asm bodies take the entry in registers");
             EntryRegs t = load_entry<L>(entry, neg, code & 7, ef);
 #pragma unroll 1
             for (int k = 0; k < 3; k++) dbl_asm(Q.X, Q.Y, Q.Z);
             Fe2<1> T;
             dblt_asm(Q.X, Q.Y, Q.Z, T);
             add_asm(Q, T, t, neg);
-        } else if (PRELOAD) {
-            EntryRegs t = load_entry<L>(entry, neg, code & 7, ef);
-#pragma unroll 1
-            for (int k = 0; k < 4; k++) Q = dbl<CH>(Q.X, Q.Y, Q.Z);
-            Q = add_entry<CH>(Q, t, neg);
         } else {
             u32 landing = 0;
             if (TOUCH) landing = touch_line(entry);
@@ -473,42 +422,30 @@ template <typename SRC> FQ_DEV EntryRegs scan_entry(const SRC& src, u32 digit_va
     t.N = src.coord(digit, 0); t.D = src.coord(digit, 1); t.E = src.coord(digit, 2); t.F = src.coord(digit, 3);
     return t;
 }
-template <int CH, typename SRC> FQ_DEV R1 ladder_endo_scan(const EndoDigits& e, const SRC& src) {
-    Proj<1, 1, 1> q4 = start_scan(src, e.top & 7, 0u);
-    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
+// the asm bodies: the scan's select trees hand them the entry as operands
+template <typename SRC> FQ_DEV R1 ladder_endo_scan(const EndoDigits& e, const SRC& src) {
+    R1 Q = ladder_start(start_scan(src, e.top & 7, 0u));
 #pragma unroll 1
     for (int i = 63; i >= 0; i--) {
-        if constexpr (CH == 3) {                  // the asm bodies: the scan's select trees hand them the entry as operands
-            Fe2<1> T;
-            dblt_asm(Q.X, Q.Y, Q.Z, T);
-            add_asm(Q, T, scan_entry(src, endo_digit(e, i)), endo_neg_mask(e, i));
-        } else {
-            Q = dbl<CH>(Q.X, Q.Y, Q.Z);
-            Q = add_scan<CH>(Q, src, endo_digit(e, i), endo_neg_mask(e, i));
-        }
+        Fe2<1> T;
+        dblt_asm(Q.X, Q.Y, Q.Z, T);
+        add_asm(Q, T, scan_entry(src, endo_digit(e, i)), endo_neg_mask(e, i));
     }
-    return ladder_result<CH>(Q);
+    return ladder_result<3>(Q);
 }
-template <int CH, typename SRC> FQ_DEV R1 ladder_windowed_scan(const WinScalar& w, const SRC& src) {
+template <typename SRC> FQ_DEV R1 ladder_windowed_scan(const WinScalar& w, const SRC& src) {
     u32 code = win_top_code(w);
-    Proj<1, 1, 1> q4 = start_scan(src, code & 7, (code >> 3) - 1u);
-    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
+    R1 Q = ladder_start(start_scan(src, code & 7, (code >> 3) - 1u));
 #pragma unroll 1
     for (int i = 61; i >= 0; i--) {
         code = win_code_from_window(win_window(w, i));
-        if constexpr (CH == 3) {
 #pragma unroll 1
-            for (int k = 0; k < 3; k++) dbl_asm(Q.X, Q.Y, Q.Z);
-            Fe2<1> T;
-            dblt_asm(Q.X, Q.Y, Q.Z, T);
-            add_asm(Q, T, scan_entry(src, code & 7), (code >> 3) - 1u);
-        } else {
-#pragma unroll 1
-            for (int k = 0; k < 4; k++) Q = dbl<CH>(Q.X, Q.Y, Q.Z);
-            Q = add_scan<CH>(Q, src, code & 7, (code >> 3) - 1u);
-        }
+        for (int k = 0; k < 3; k++) dbl_asm(Q.X, Q.Y, Q.Z);
+        Fe2<1> T;
+        dblt_asm(Q.X, Q.Y, Q.Z, T);
+        add_asm(Q, T, scan_entry(src, code & 7), (code >> 3) - 1u);
     }
-    return ladder_result<CH>(Q);
+    return ladder_result<3>(Q);
 }
 
 // table_endo for the fused kernels that keep E, F in LDS (LdsEF): the same DAG and the same order as above, but nothing is
@@ -520,59 +457,9 @@ template <int CH, typename SRC> FQ_DEV R1 ladder_windowed_scan(const WinScalar& 
 //                 that entry's own E, F arrive (an iteration loads its next base BEFORE it stores the previous result)
 // T[0]'s N, D stay in registers.  The HBM slot receives N, D of every entry, write-only; loads and stores share vmcnt on
 // gfx950, so a table phase without loads has nothing to wait for until the ladder's first gather.
-template <typename L, typename EF> FQ_DEV void build_table_endo_lds(const R1& P, u32* slot, const EF& ef) {
-    static_assert(EF::ON, "needs the LDS copy of E and F");
-    R2 result = r1_to_r2(P);                   // T[0]; `result` holds the one entry not stored yet
-    int result_at = 0;
-    const Fe2<1> n0 = result.N, d0 = result.D;
-    Fe2<1> X = P.X, Y = P.Y, Z = P.Z;          // step 0: P; step 1: tau(P); step 2: phi(P)
-    auto store_result = [&]() {
-        store_entry<L>(slot, result_at, result, ef);
-        if (result_at >= 1 && result_at <= 3) ef.park_nd(8 - result_at, result.N, result.D);
-    };
-#pragma unroll 1
-    for (int step = 0; step < 3; step++) {
-        store_result();
-        Proj<1, 2, 1> t;
-        if (step == 1) {                       // phi and psi share tau(P), curve4q.py:318-322
-            t.X = X; t.Y = widen<2>(Y); t.Z = Z;
-        } else {
-            t = tau(X, Y, Z);
-            if (step == 0) ef.park_xyz(6, t.X, fe2_carry(t.Y), t.Z);
-        }
-        Proj<2, 2, 2> u;
-        if (step == 0) {
-            u = upsilon(t);
-        } else {
-            Proj<1, 1, 1> c = chi(t);
-            u.X = widen<2>(c.X); u.Y = widen<2>(c.Y); u.Z = widen<2>(c.Z);
-        }
-        R1 V = tau_dual(u.X, u.Y, u.Z);
-        R3 V3 = r1_to_r3(V);
-        R2 base;
-        base.N = n0; base.D = d0; base.E = ef.get(0, 0); base.F = ef.get(0, 1);
-        const int half = 1 << step;
-#pragma unroll 1
-        for (int m = 0; m < half; m++) {
-            R2 next = base;
-            if (m + 1 < half) { ef.unpark_nd(8 - (m + 1), next.N, next.D); next.E = ef.get((u32)(m + 1), 0); next.F = ef.get((u32)(m + 1), 1); }
-            if (m > 0) store_result();
-            if (m == 0 && step == 0) ef.park_xyz(4, V.X, V.Y, V.Z);
-            if (m == half - 1 && step < 2) ef.unpark_xyz(step == 0 ? 6 : 4, X, Y, Z);   // for the next step
-            result = r1_to_r2(add_core(V3, as_signed(base)));
-            result_at = half + m;
-            base = next;
-        }
-    }
-    store_result();                            // T[7]
-}
-
-// The same construction with every formula a generated body (ladder_asm.hip.h: tau / upsilon / chi / tau_dual + R1toR3 / R1toR2 /
-// table addition, 22 500 instructions per table against hipcc's 24 400, no register shuffles between products): same parking
-// schedule in LDS, same stores, same tight non-negative entries.  FQ_TABLE_ASM selects it for the fused kernels.
-#ifndef FQ_TABLE_ASM
-#define FQ_TABLE_ASM 1
-#endif
+// Every formula is a generated body (ladder_asm.hip.h: tau / upsilon / chi / tau_dual + R1toR3 / R1toR2 / table addition, 22 500
+// instructions per table against 24 400 for hipcc's own, no register shuffles between products; cycles per body: profiles/r04_table_phases.txt);
+// the entries are tight and non-negative.
 template <typename L, typename EF> FQ_DEV void build_table_endo_lds_asm(const R1& P, u32* slot, const EF& ef) {
     static_assert(EF::ON, "needs the LDS copy of E and F");
     R2 result = r1_to_r2_asm(P);               // T[0]
@@ -621,6 +508,13 @@ FQ_DEV void load_scalar(const u64* p, u64 m[4]) {
     m[2] = (u64)b.x | ((u64)b.y << 32); m[3] = (u64)b.z | ((u64)b.w << 32);
 }
 
+// an R1 row of twenty canonical words as ten 16-byte stores
+FQ_DEV void store_row(u64* row, const u64 o[20]) {
+    uint4* dst = reinterpret_cast<uint4*>(row);
+#pragma unroll
+    for (int k = 0; k < 10; k++) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
+}
+
 namespace {   // kernels: one private copy per translation unit (their code objects differ by FQ_CHAIN)
 
 // Large variable-base batches, first half: per element, (DH: membership test, cofactor clearing,) table
@@ -651,10 +545,8 @@ __global__ __launch_bounds__(BLOCK) void prep_kernel(LadderArgs a) {
 // scans E, F in the lane's LDS rows, LDS scans the shared table where it lies (PREBUILT is not taken in this mode).
 constexpr int ladder_waves(int src, bool dh, bool ct) {       // wave slots per SIMD a ladder kernel is built for
     if (src == FUSED) return 1;                                // the endomorphisms' 256 VGPRs and the CU's whole LDS
-    if (!ct && FQ_LADDER_ASM && ((src == LDS && FQ_LDS_ASM) || (src == PREBUILT && FQ_PREBUILT_ASM && !dh))) return 2;   // the asm bodies: 256 VGPRs
-    if (ct && src == LDS && FQ_LADDER_ASM && FQ_CT_LDS_ASM) return 2;
-    if (ct && src == LDS && dh) return 3;                      // the scan's select tree + DH's epilogue spill at 128 VGPRs (52-80 bytes per lane)
-    return 4;
+    if (src == LDS || (src == PREBUILT && !dh && !ct)) return 2;   // the asm bodies: 256 VGPRs
+    return 4;                                                  // the two-kernel DH ladder: hipcc's step in 128 VGPRs, four waves to hide its gathers
 }
 template <int ALGO, int SRC, bool DH, bool DEFER = false, bool CT = false>
 __global__ __launch_bounds__(BLOCK, ladder_waves(SRC, DH, CT)) void ladder_kernel(LadderArgs a) {
@@ -703,37 +595,29 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC, DH, CT)) void ladder_kerne
                 else P = load_r1(a.points + 20 * (size_t)id);
             }
             if constexpr (SRC == FUSED) {
-                if constexpr (ALGO == ENDO && FQ_TABLE_ASM && FQ_LADDER_ASM) build_table_endo_lds_asm<L>(P, slot, ef);
-                else if (ALGO == ENDO) build_table_endo_lds<L>(P, slot, ef);
+                if constexpr (ALGO == ENDO) build_table_endo_lds_asm<L>(P, slot, ef);
                 else build_table_windowed<L>(P, slot, ef);
             }
         }
         R1 Q;
-        constexpr bool CT_ASM = CT && FQ_LADDER_ASM && ((SRC == LDS && FQ_CT_LDS_ASM) || (SRC == FUSED && FQ_CT_FUSED_ASM));
-        constexpr int CH = (((SRC == FUSED || (SRC == LDS && FQ_LDS_ASM) || (SRC == PREBUILT && FQ_PREBUILT_ASM && !DH)) && !CT && FQ_LADDER_ASM) || CT_ASM) ? 3 : LADDER_CH;
-        if constexpr (ALGO == ENDO && SRC == FUSED && !CT && CH == 3 && FQ_NIBBLE_LADDER) {
+        constexpr int CH = (SRC == PREBUILT && DH) ? LADDER_CH : 3;     // see "the ladders"
+        if constexpr (ALGO == ENDO) {
             u64 v[4];
             decompose(m, v);
-            Q = ladder_endo_nibbles<L, EF, !DH>(recode_nibbles(v), a.scratch, lane_slot * (u32)L::SLOT, ef);      // MUL_*: signed limbs, see the store
-        } else if constexpr (ALGO == ENDO && SRC == LDS && !CT && CH == 3 && FQ_NIBBLE_LADDER) {
-            u64 v[4];
-            decompose(m, v);
-            Q = ladder_endo_nibbles_at<LimbSlots, NoEF>(recode_nibbles(v), lds_table, LDS_ENTRY_U32);
-        } else if (ALGO == ENDO) {
-            u64 v[4];
-            decompose(m, v);
-            const EndoDigits e = recode(v);
             if constexpr (CT && SRC == FUSED) {
+                const EndoDigits e = recode(v);
                 ScanSplit<EF> regs;
                 regs.ef = ef;
                 regs.template load<L>(tbl);
-                Q = ladder_endo_scan<CH>(e, regs);
+                Q = ladder_endo_scan(e, regs);
             } else if constexpr (CT) {
-                Q = ladder_endo_scan<CH>(e, ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
+                Q = ladder_endo_scan(recode(v), ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
+            } else if constexpr (SRC == FUSED) {
+                Q = ladder_endo_nibbles<L, EF, !DH>(recode_nibbles(v), a.scratch, lane_slot * (u32)L::SLOT, ef);      // MUL_*: signed limbs, see the store
             } else if constexpr (SRC == LDS) {
-                Q = ladder_endo<CH, CH == 3>(e, lds_table, LDS_ENTRY_U32);
+                Q = ladder_endo_nibbles_at<LimbSlots, NoEF>(recode_nibbles(v), lds_table, LDS_ENTRY_U32);
             } else {
-                Q = ladder_endo<CH, SRC == FUSED || CH == 3, L, EF, SRC == PREBUILT && CH != 3>(e, tbl, L::ENTRY, ef);
+                Q = ladder_endo<CH, L, EF, CH != 3>(recode(v), tbl, L::ENTRY, ef);      // TOUCH with hipcc's step: the DH ladder
             }
         } else {
             const WinScalar w = win_reduce(m);
@@ -741,16 +625,18 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC, DH, CT)) void ladder_kerne
                 ScanSplit<EF> regs;
                 regs.ef = ef;
                 regs.template load<L>(tbl);
-                Q = ladder_windowed_scan<CH>(w, regs);
+                Q = ladder_windowed_scan(w, regs);
             } else if constexpr (CT) {
-                Q = ladder_windowed_scan<CH>(w, ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
+                Q = ladder_windowed_scan(w, ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
             } else if constexpr (SRC == LDS) {
-                Q = ladder_windowed<CH, CH == 3>(w, lds_table, LDS_ENTRY_U32);
+                Q = ladder_windowed<CH>(w, lds_table, LDS_ENTRY_U32);
             } else {
-                Q = ladder_windowed<CH, SRC == FUSED || CH == 3, L, EF, SRC == PREBUILT && CH != 3>(w, tbl, L::ENTRY, ef);
+                Q = ladder_windowed<CH, L, EF, CH != 3>(w, tbl, L::ENTRY, ef);
             }
         }
-        if (DH && (DEFER || (FQ_FUSED_DEFER && SRC == FUSED && a.proj != nullptr))) {     // one inversion per K elements, later (FUSED: by a wave-uniform flag, no second instance)
+        // One inversion per K elements, later (normalize_kernel).  FUSED: by a wave-uniform flag, no second instance -- DH batches of at least
+        // two generations defer like the other routes (round 6) instead of inverting per element at one wave per SIMD.
+        if (DH && (DEFER || (SRC == FUSED && a.proj != nullptr))) {
             if (live) {
                 store_proj(a.proj, a.proj_stride, id, Q.X, Q.Y, Q.Z);
                 a.status[id] = st;
@@ -773,7 +659,7 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC, DH, CT)) void ladder_kerne
             }
         } else if (live) {
             u64 o[20];
-            if constexpr (ALGO == ENDO && SRC == FUSED && !CT && CH == 3 && FQ_NIBBLE_LADDER) store_r1_signed(o, Q);
+            if constexpr (ALGO == ENDO && SRC == FUSED && !CT) store_r1_signed(o, Q);
             else store_r1(o, Q);
             const bool xyz = SRC == FUSED && (a.io & LADDER_IO_XYZ_OUT);
             uint4* dst = reinterpret_cast<uint4*>(a.out + (xyz ? 12 : 20) * (size_t)id);
@@ -917,7 +803,6 @@ __global__ __launch_bounds__(BLOCK, 1) void mixed_queue_kernel(LadderArgs a, con
     const u32 total = (n_all + 63) / 64;
     u32* slot = a.scratch + (size_t)(blockIdx.x * BLOCK + threadIdx.x) * NDSlots::SLOT;
     const u32 lane = threadIdx.x & 63;
-    constexpr int CH = (FQ_LADDER_ASM && (!CT || FQ_CT_FUSED_ASM)) ? 3 : LADDER_CH;
 #pragma unroll 1
     for (;;) {
         u32 item = 0;
@@ -936,8 +821,7 @@ __global__ __launch_bounds__(BLOCK, 1) void mixed_queue_kernel(LadderArgs a, con
         if (!all_fixed) {
             if (variable) {
                 const R1 P = load_r1(a.points + 20 * (size_t)id);
-                if constexpr (FQ_TABLE_ASM && FQ_LADDER_ASM) build_table_endo_lds_asm<NDSlots>(P, slot, ef);
-                else build_table_endo_lds<NDSlots>(P, slot, ef);
+                build_table_endo_lds_asm<NDSlots>(P, slot, ef);
             } else {                                                // a fixed-base lane of the boundary item: the shared table as its own
 #pragma unroll 1
                 for (int k = 0; k < 8; k++) store_entry<NDSlots>(slot, k, load_r2_limbs(a.table + k * R2_LIMBS), ef);
@@ -949,25 +833,20 @@ __global__ __launch_bounds__(BLOCK, 1) void mixed_queue_kernel(LadderArgs a, con
                 ScanSplit<LdsEF> regs;
                 regs.ef = ef;
                 regs.template load<NDSlots>(slot);
-                Q = ladder_endo_scan<CH>(e, regs);
-            } else if constexpr (CH == 3 && FQ_NIBBLE_LADDER) {          // the headline kernel's ladder (nibble stream, 32-bit entry offsets)
+                Q = ladder_endo_scan(e, regs);
+            } else {                                                // the headline kernel's ladder (nibble stream, 32-bit entry offsets)
                 Q = ladder_endo_nibbles<NDSlots, LdsEF>(recode_nibbles(v), a.scratch, (blockIdx.x * BLOCK + threadIdx.x) * (u32)NDSlots::SLOT, ef);
-            } else {
-                Q = ladder_endo<CH, true, NDSlots, LdsEF>(recode(v), (const u32*)slot, NDSlots::ENTRY, ef);
             }
         } else {
             u64 v[4];
             decompose(m, v);
-            if constexpr (CT) Q = ladder_endo_scan<CH>(recode(v), ScanMem<8, u32>{ a.table, R2_LIMBS });      // wave-uniform addresses
-            else if constexpr (CH == 3 && FQ_NIBBLE_LADDER) Q = ladder_endo_nibbles_at<LimbSlots, NoEF>(recode_nibbles(v), a.table, R2_LIMBS);
-            else Q = ladder_endo<CH, true, LimbSlots, NoEF>(recode(v), a.table, R2_LIMBS);
+            if constexpr (CT) Q = ladder_endo_scan(recode(v), ScanMem<8, u32>{ a.table, R2_LIMBS });      // wave-uniform addresses
+            else Q = ladder_endo_nibbles_at<LimbSlots, NoEF>(recode_nibbles(v), a.table, R2_LIMBS);
         }
         if (live) {
             u64 o[20];
             store_r1(o, Q);
-            uint4* dst = reinterpret_cast<uint4*>(a.out + 20 * (size_t)id);
-#pragma unroll
-            for (int k = 0; k < 10; k++) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
+            store_row(a.out + 20 * (size_t)id, o);
         }
     }
 }
@@ -989,14 +868,13 @@ __global__ void split_counts_kernel(u32* counts, u32 lanes, u32 limit) {        
     counts[5] = cut ? rem : 0u;
 }
 template <int UNIT_ONLY = 0>
-__global__ __launch_bounds__(BLOCK, (FQ_LADDER_ASM && FQ_CT_LDS_ASM) ? 2 : 4) void mixed_ct_tail_kernel(LadderArgs a, const u32* fix_list, const u32* var_list, const u32* counts, const u32* over_scratch) {
+__global__ __launch_bounds__(BLOCK, 2) void mixed_ct_tail_kernel(LadderArgs a, const u32* fix_list, const u32* var_list, const u32* counts, const u32* over_scratch) {
     __shared__ __attribute__((aligned(16))) u32 lds_table[8 * LDS_ENTRY_U32];
     for (int i = threadIdx.x; i < 8 * R2_LIMBS; i += BLOCK)
         lds_table[(i / R2_LIMBS) * LDS_ENTRY_U32 + (i % R2_LIMBS)] = a.table[i];
     __syncthreads();
     const u32 n_fix = counts[1], fused = counts[4], total = n_fix + counts[5];
     const u32 lanes = gridDim.x * BLOCK, n_round = (total + BLOCK - 1) / BLOCK * BLOCK;
-    constexpr int CH = (FQ_LADDER_ASM && FQ_CT_LDS_ASM) ? 3 : LADDER_CH;
 #pragma unroll 1
     for (u32 it = blockIdx.x * BLOCK + threadIdx.x; it < n_round; it += lanes) {
         const bool live = it < total;
@@ -1009,17 +887,15 @@ __global__ __launch_bounds__(BLOCK, (FQ_LADDER_ASM && FQ_CT_LDS_ASM) ? 2 : 4) vo
         const EndoDigits e = recode(v);
         R1 Q;
         if (__all(fixed)) {                                   // wave-uniform, and public
-            Q = ladder_endo_scan<CH>(e, ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
+            Q = ladder_endo_scan(e, ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
         } else {
             const u32* tbl = fixed ? a.table : over_scratch + (size_t)(pos - n_fix) * LimbSlots::SLOT;
-            Q = ladder_endo_scan<CH>(e, ScanMem<8, u32>{ tbl, LimbSlots::ENTRY });
+            Q = ladder_endo_scan(e, ScanMem<8, u32>{ tbl, LimbSlots::ENTRY });
         }
         if (live) {
             u64 o[20];
             store_r1(o, Q);
-            uint4* dst = reinterpret_cast<uint4*>(a.out + 20 * (size_t)id);
-#pragma unroll
-            for (int k = 0; k < 10; k++) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
+            store_row(a.out + 20 * (size_t)id, o);
         }
     }
 }

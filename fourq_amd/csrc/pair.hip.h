@@ -66,9 +66,6 @@ template <int CTRL, int B> FQ_DEV PF<B> pdpp(const PF<B>& a) {
 // back -- and behind every opaque partial sum hipcc pads an s_nop before the next instruction that reads it (467 per ladder step
 // measured, a third of the step's issue slots).  Each column is therefore accumulated in TWO chains that alternate (u*v in one,
 // w*z in the other; a square's products by parity) and are added once per column: +5 64-bit additions per product, -400 s_nop per step.
-#ifndef FQ_PAIR_CHAINS
-#define FQ_PAIR_CHAINS 2
-#endif
 // r = u*v + w*z (one component of a GF(p^2) product), signed limbs, carries chained: the column loop of fe2_mul_signed
 template <int U, int V> FQ_DEV PF<1> pmac2(const u32 u[5], const u32 v[5], const u32 w[5], const u32 z[5]) {
     static_assert(cols_ok_signed((u64)2 * U * V), "column overflow");
@@ -85,10 +82,9 @@ template <int U, int V> FQ_DEV PF<1> pmac2(const u32 u[5], const u32 v[5], const
         for (int i = 0; i < 5; i++) {
             const int j = K - i;
             acc += smul(u[i], j >= 0 ? v[j >= 0 ? j : 0] : v8[j >= 0 ? 0 : j + 5]); FQ_POPAQUE(acc);
-            if (FQ_PAIR_CHAINS == 2) { side += smul(w[i], j >= 0 ? z[j >= 0 ? j : 0] : z8[j >= 0 ? 0 : j + 5]); FQ_POPAQUE(side); }
-            else { acc += smul(w[i], j >= 0 ? z[j >= 0 ? j : 0] : z8[j >= 0 ? 0 : j + 5]); FQ_POPAQUE(acc); }
+            side += smul(w[i], j >= 0 ? z[j >= 0 ? j : 0] : z8[j >= 0 ? 0 : j + 5]); FQ_POPAQUE(side);
         }
-        if (FQ_PAIR_CHAINS == 2) acc += side;
+        acc += side;
         l[K] = (u32)acc & LIMB_MASK; acc >>= LIMB_BITS;
     }
     const Fe<1> f = fe_finish_signed(l[0], l[1], l[2], l[3], l[4], acc);
@@ -141,10 +137,10 @@ template <int A> FQ_DEV PF<1> psqr(const PF<A>& a, const PairLane& pl) {
         for (int i = 0; i < 5; i++) {
             const int j = K - i;
             const i64 prod = smul(j >= 0 ? u[i] : uw[i], j >= 0 ? v[j >= 0 ? j : 0] : vw[j >= 0 ? 0 : j + 5]);
-            if (FQ_PAIR_CHAINS == 2 && (i & 1)) { side += prod; FQ_POPAQUE(side); }
+            if (i & 1) { side += prod; FQ_POPAQUE(side); }
             else { acc += prod; FQ_POPAQUE(acc); }
         }
-        if (FQ_PAIR_CHAINS == 2) acc += side;
+        acc += side;
         l[K] = (u32)acc & LIMB_MASK; acc >>= LIMB_BITS;
     }
     const Fe<1> f = fe_finish_signed(l[0], l[1], l[2], l[3], l[4], acc);
@@ -434,7 +430,7 @@ template <bool QUAD = false> FQ_DEV void pair_build_table_endo(const PR1& P, con
 }
 
 // MUL_endo's ladder (curve4q.py:436-442) on the pair's table: the entry of a step is read from LDS a whole doubling ahead, its
-// sign applied by masked selects behind the doubling (as add_entry in curve.hip.h).
+// sign applied by masked selects behind the doubling (as add_asm in ladder_asm.hip.h).
 FQ_DEV PR1 pair_start(const PR2& t, u32 neg);
 FQ_DEV PR1 padd_signed_entry(const PR1& Q, const PR2& t, u32 neg, const PairLane& pl);
 template <bool CT, bool QUAD = false> FQ_DEV PR1 pair_ladder_endo(const EndoDigits& e, const PairTable& tbl, const PairLane& pl, const QuadLane& ql) {
@@ -475,7 +471,7 @@ template <int B> FQ_DEV PF<1> ptighten(const PF<B>& a) {
     for (int i = 0; i < 5; i++) { r.l[i] = f.l[i]; FQ_SIGN_UNKNOWN(r.l[i]); }
     return r;
 }
-// Q + (+-T): the entry's sign by masked selects behind whatever produced Q (as add_entry in curve.hip.h)
+// Q + (+-T): the entry's sign by masked selects behind whatever produced Q (as add_asm in ladder_asm.hip.h)
 FQ_DEV PR1 padd_signed_entry(const PR1& Q, const PR2& t, u32 neg, const PairLane& pl) {
     asm("" : "+v"(neg) : "v"(Q.X.l[0]), "v"(Q.Y.l[0]), "v"(Q.Z.l[0]));
     PR2 s;

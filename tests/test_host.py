@@ -94,6 +94,23 @@ def test_every_environment_variable_the_library_reads_is_documented():
         assert 'route_env("%s")' % v in src and 'getenv("%s")' % v not in src, v
 
 
+def test_the_kernel_sources_carry_no_build_switch_beyond_the_documented_ones():
+    """A compile-time switch (#ifndef FQ_X / #define FQ_X <default>) is how an experiment enters the kernel headers; one that has been
+    measured and settled is folded out again (tools/experiments/README.md), so that the headers say what the library runs."""
+    import glob
+    kept = {"FQ_CHAIN", "FQ_ND_PACKED", "FQ_BUILD_ID"}
+    found = set()
+    for path in glob.glob(os.path.join(ROOT, "fourq_amd", "csrc", "*")):
+        text = open(path, errors="replace").read()
+        found |= {a for a, b in re.findall(r"^\s*#\s*ifndef\s+(FQ_\w+)\s*\n\s*#\s*define\s+(FQ_\w+)", text, re.M) if a == b}
+    assert found == kept, (
+        "the build switches of fourq_amd/csrc changed (%s): a new switch needs an entry in tools/README.md (\"Build switches\") and in "
+        "this test, or has to go before merge" % ", ".join(sorted(found ^ kept)))
+    readme = open(os.path.join(ROOT, "tools", "README.md")).read()
+    for name in kept:
+        assert "| `%s` |" % name in readme, name
+
+
 def test_import_asks_for_enough_hardware_queues_and_respects_the_users_choice():
     """the host-array pipeline needs its three streams on three hardware queues (fourq_amd/_lib.py, profiles/r04_pipeline_queues.txt):
     importing the package sets GPU_MAX_HW_QUEUES=8 when the variable is unset and leaves a value of the user's alone"""

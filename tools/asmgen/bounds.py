@@ -496,8 +496,8 @@ def within(ivs, contract):
 
 # ---- the chain: every edge where one body's output feeds another body or a C++ value of a given type ---------------------------------
 # (producer, output operand) -> (consumer, input operand), or a C++ consumer given by its limb intervals.  kernels.hip.h, ladder_endo and
-# its kin (:324-505): start_table -> DBLT / DBL, DBLT -> ADD, ADD -> DBLT / DBL, DBL -> DBL / DBLT, the result -> ladder_result<3> /
-# store_r1_signed (fe_unsign / fe_unsign_wide of Fe2<1>, Ta Fe2<4>, Tb Fe2<2>).  build_table_endo_lds_asm (:576-610): R1TOR2 -> table,
+# its kin ("the ladders"): start_table -> DBLT / DBL, DBLT -> ADD, ADD -> DBLT / DBL, DBL -> DBL / DBLT, the result -> ladder_result<3> /
+# store_r1_signed (fe_unsign / fe_unsign_wide of Fe2<1>, Ta Fe2<4>, Tb Fe2<2>).  build_table_endo_lds_asm: R1TOR2 -> table,
 # TAU -> UPSILON / CHI (and parked in LDS as Fe2<1>), UPSILON / CHI -> TAUDUAL, TAUDUAL -> TAU (next step) and -> TABLEADD, TABLEADD ->
 # table -> TABLEADD / ADD / STEP.  Sources: fe_unpack of any input word, start_table's fe2_carry (bound-1 non-negative), table entries.
 def _cpp(name, ivs):

@@ -1,6 +1,6 @@
 // Two lanes per element: the only lever against one-wave-per-SIMD at 2^16 elements that DESIGN.md had
 // costed but never measured.  One ladder step (DBL + ADD of a table entry, the DAG of curve4q.py:138-171) is run
-//   A  as shipped: one lane per element, dbl<2> + add_entry<2> of curve.hip.h (signed limbs, chained carries), ONE wave per SIMD;
+//   A  as shipped: one lane per element, dbl<2> of curve.hip.h + add_entry<2> (add_entry.hip.h here) (signed limbs, chained carries), ONE wave per SIMD;
 //   B  pair-lane:  lane 2k holds the real parts, lane 2k+1 the imaginary parts of every GF(p^2) value of element k; a product
 //      r = u*v + w*z of 50 multiply-adds per lane gives the even lane its real and the odd lane its imaginary part, the partner's
 //      halves arrive by DPP quad_perm moves (no LDS, no waits), additions cost half; TWO waves per SIMD for the same elements.
@@ -12,6 +12,7 @@
 #include <cstdint>
 #define FQ_CHAIN 1
 #include "../../fourq_amd/csrc/curve.hip.h"
+#include "add_entry.hip.h"
 using namespace fq;
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 

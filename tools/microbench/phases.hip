@@ -18,12 +18,12 @@ using namespace fq;
 
 FQ_DEV uint64_t stamp() { uint64_t t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory"); return t; }
 
-// the product's MUL_endo ladder (ladder_endo<3, true, NDSlots, LdsEF> of kernels.hip.h) with the entry index of the HBM-side gather (N, D)
+// the product's MUL_endo ladder (ladder_endo<3, NDSlots, LdsEF> of kernels.hip.h) with the entry index of the HBM-side gather (N, D)
 // and of the LDS read (E, F) masked by run-time values: 7 = by digit as shipped, 0 = always entry 0 (same instructions, one address)
 FQ_DEV R1 ladder_probe(const EndoDigits& e, const u32* tbl, const LdsEF& ef, u32 gmask, u32 lmask) {
     Proj<1, 1, 1> q4 = start_table<NDSlots>(tbl + (e.top & 7) * NDSlots::ENTRY, 0u);
     q4.Z = ef.get(e.top & 7, 0);
-    R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
+    R1 Q = ladder_start(q4);
 #pragma unroll 1
     for (int i = 63; i >= 0; i--) {
         const u32 digit = endo_digit(e, i);
@@ -46,11 +46,7 @@ template <int VARIANT> __global__ __launch_bounds__(256, 1) void k(const u64* sc
     R1 P = load_r1(points + 20 * (size_t)id);
     u32* slot = scratch + (size_t)id * NDSlots::SLOT;
     uint64_t t1 = stamp();
-#if FQ_TABLE_ASM
-    if (VARIANT != 2) build_table_endo_lds_asm<NDSlots>(P, slot, ef);         // -DFQ_TABLE_ASM=1: the generated table bodies
-#else
-    if (VARIANT != 2) build_table_endo_lds<NDSlots>(P, slot, ef);
-#endif
+    if (VARIANT != 2) build_table_endo_lds_asm<NDSlots>(P, slot, ef);         // the generated table bodies
     else { for (int kk = 0; kk < 8; kk++) { R2 t = r1_to_r2(P); ef.put(kk, t); } }      // LDS filled, HBM slot left from the previous launch
     uint64_t t2 = stamp();
     u64 v[4];
@@ -59,13 +55,11 @@ template <int VARIANT> __global__ __launch_bounds__(256, 1) void k(const u64* sc
     if (VARIANT == 1) { e.d[0] = e.d[1] = e.d[2] = 0; e.top = 0; }
     uint64_t t3 = stamp();
     R1 Q = (VARIANT >= 3) ? ladder_probe(e, (const u32*)slot, ef, gmask, lmask)
-                          : ladder_endo<FQ_LADDER_ASM ? 3 : LADDER_CH, true, NDSlots>(e, (const u32*)slot, NDSlots::ENTRY, ef);      // the product kernel's ladder: the asm bodies since round 4
+                          : ladder_endo<3, NDSlots>(e, (const u32*)slot, NDSlots::ENTRY, ef);      // the asm bodies, as the product kernel's ladder since round 4
     uint64_t t4 = stamp();
     u64 o[20];
     store_r1(o, Q);
-    uint4* dst = reinterpret_cast<uint4*>(out + 20 * (size_t)id);
-#pragma unroll
-    for (int q = 0; q < 10; q++) dst[q] = make_uint4((u32)o[2 * q], (u32)(o[2 * q] >> 32), (u32)o[2 * q + 1], (u32)(o[2 * q + 1] >> 32));
+    store_row(out + 20 * (size_t)id, o);
     uint64_t t5 = stamp();
     if ((threadIdx.x & 63) == 0) {
         uint64_t* w = stamps + 8 * (size_t)(id >> 6);

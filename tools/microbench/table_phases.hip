@@ -1,12 +1,17 @@
-// s_memtime stamps INSIDE table_endo of the fused kernels (a copy of build_table_endo_lds with stamps; diagnostic only):
+// s_memtime stamps INSIDE table_endo of the fused kernels (a copy of build_table_endo_lds_asm with stamps; diagnostic only):
 // cycles per sub-formula for a lone wave, against their instruction counts.
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -o table_phases table_phases.hip
+// -DTABLE_PHASES_CPP=1 stamps the same schedule with hipcc's own formulas instead (the product's builder before round 4; the copy
+// below is all that is left of it), for the comparison in profiles/r04_table_phases.txt.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
 #include <vector>
 #include <algorithm>
 #define FQ_CHAIN 0
+#ifndef TABLE_PHASES_CPP
+#define TABLE_PHASES_CPP 0
+#endif
 #include "../../fourq_amd/csrc/kernels.hip.h"
 using namespace fq;
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
@@ -57,7 +62,7 @@ template <typename L, typename EF> FQ_DEV void build_stamped(const R1& P, u32* s
     store_result();
     ts[q++] = stamp();
 }
-// the same stamps around the GENERATED table bodies (build_table_endo_lds_asm of kernels.hip.h; -DFQ_TABLE_ASM=1): a body's instruction count is known
+// the same stamps around the GENERATED table bodies (build_table_endo_lds_asm of kernels.hip.h): a body's instruction count is known
 // exactly (tools/asmgen/gen_ladder_step.py --stats), so cycles - 4 x instructions is what the memory side and the glue cost
 template <typename L, typename EF> FQ_DEV void build_stamped_asm(const R1& P, u32* slot, const EF& ef, uint64_t* ts) {
     int q = 0;
@@ -109,10 +114,10 @@ __global__ __launch_bounds__(256, 1) void k(const u64* points, u32* scratch, uin
     R1 P = load_r1(points + 20 * (size_t)id);
     uint64_t ts[NS];
     for (int i = 0; i < NS; i++) ts[i] = 0;
-#if FQ_TABLE_ASM
-    build_stamped_asm<NDSlots>(P, scratch + (size_t)id * NDSlots::SLOT, ef, ts);
-#else
+#if TABLE_PHASES_CPP
     build_stamped<NDSlots>(P, scratch + (size_t)id * NDSlots::SLOT, ef, ts);
+#else
+    build_stamped_asm<NDSlots>(P, scratch + (size_t)id * NDSlots::SLOT, ef, ts);
 #endif
     Fe2<1> e = ef.get(7, 0);
     if (e.re.l[0] == 0x7fffffffu) sink[0] = 1;
@@ -143,7 +148,7 @@ int main() {
         total += c[512];
         printf("%-18s %8llu cycles  %5d multiply-adds  %s\n", names[i], (unsigned long long)c[512], mads[i], mads[i] ? "" : "");
         if (mads[i]) printf("                   -> %.1f cycles per multiply-add\n", (double)c[512] / mads[i]);
-#if FQ_TABLE_ASM
+#if !TABLE_PHASES_CPP
         if (asm_instr[i]) printf("                   -> %d body instructions x 4 = %d cycles; the rest (glue, LDS / HBM side, stamp): %lld\n", asm_instr[i], 4 * asm_instr[i], (long long)c[512] - 4 * asm_instr[i]);
 #endif
     }
