@@ -142,7 +142,7 @@ PRIM = {
     "PT_DBL": 32, "PT_ADD": 33, "PT_ADD_CORE": 34, "PT_R1TOR2": 35, "PT_R1TOR3": 36, "PT_R2TOR4": 37,
     "PT_TAU": 38, "PT_TAU_DUAL": 39, "PT_UPSILON": 40, "PT_CHI": 41, "PT_PHI": 42, "PT_PSI": 43,
     "PT_ON_CURVE": 44, "PT_COFACTOR392": 45, "PT_R1TOAFFINE": 46, "PT_MAP_ELL2": 47,
-    "SC_DECOMPOSE": 64, "SC_RECODE": 65, "SC_WINDOWED": 66, "SC_REDUCE512": 67, "SC_MULSUB": 68, "SC_MUL": 69,
+    "SC_DECOMPOSE": 64, "SC_RECODE": 65, "SC_WINDOWED": 66, "SC_REDUCE512": 67, "SC_MULSUB": 68, "SC_MUL": 69, "SC_RECODE_NIBBLES": 70,
 }
 
 

@@ -419,6 +419,13 @@ __global__ __launch_bounds__(64) void prim_kernel(int op, const u64* in, u64* ou
         y[0] = e.sign; y[1] = e.d[0]; y[2] = e.d[1]; y[3] = e.d[2]; y[4] = e.top;
         break;
     }
+    case FOURQ_SC_RECODE_NIBBLES: {
+        u64 v[4] = { x[0], x[1], x[2], x[3] };
+        EndoNibbles e = recode_nibbles(v);
+        for (int k = 0; k < 8; k++) y[k] = e.w[k];
+        y[8] = e.top;
+        break;
+    }
     case FOURQ_SC_WINDOWED: {
         u64 m[4] = { x[0], x[1], x[2], x[3] };
         WinScalar w = win_reduce(m);
@@ -443,7 +450,7 @@ const PrimShape PRIMS[] = {
     { FOURQ_PT_UPSILON, 12, 12 }, { FOURQ_PT_CHI, 12, 12 }, { FOURQ_PT_PHI, 20, 20 }, { FOURQ_PT_PSI, 20, 20 },
     { FOURQ_PT_ON_CURVE, 8, 1 }, { FOURQ_PT_COFACTOR392, 8, 20 }, { FOURQ_PT_R1TOAFFINE, 20, 8 },
     { FOURQ_PT_MAP_ELL2, 4, 8 },                                                             // h2c.hip.h
-    { FOURQ_SC_DECOMPOSE, 4, 4 }, { FOURQ_SC_RECODE, 4, 5 }, { FOURQ_SC_WINDOWED, 4, 8 },
+    { FOURQ_SC_DECOMPOSE, 4, 4 }, { FOURQ_SC_RECODE, 4, 5 }, { FOURQ_SC_RECODE_NIBBLES, 4, 9 }, { FOURQ_SC_WINDOWED, 4, 8 },
     { FOURQ_SC_REDUCE512, 8, 4 }, { FOURQ_SC_MULSUB, 12, 4 }, { FOURQ_SC_MUL, 8, 4 },        // sig.hip.h (scalar_n.hip.h)
 };
 const PrimShape* find_prim(int op) {

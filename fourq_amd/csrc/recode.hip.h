@@ -5,8 +5,22 @@
 //   recode(v)             curve4q.py:358-380   (65 sign bits + 65 three-bit digits)
 //
 // One lane owns one scalar; everything is straight-line 64-bit integer code.
+//
+// The functions marked FQ_HD are pure integer code in plain C++ and compile for the host as well: a stand-alone program that includes this
+// header with an ordinary C++ compiler gets exactly them (tests/c/recode_check.cpp runs the shipped recoders on the CPU, under the
+// sanitizers too).  Whatever reads the curve's constants or the field layer is device code and exists under hipcc only.
 #pragma once
+#if defined(__HIPCC__)
 #include "fp127.hip.h"
+#define FQ_HD __host__ __device__ __forceinline__
+#else
+#include <stdint.h>
+namespace fq {
+typedef uint32_t u32;
+typedef uint64_t u64;
+}
+#define FQ_HD inline
+#endif
 
 namespace fq {
 
@@ -14,7 +28,7 @@ typedef unsigned __int128 u128;
 
 // ((a * m) >> 256) mod 2^64 for 256-bit a, m: column 4 of the product with exact carries from
 // columns 0..3 (t_i of curve4q.py:344-347; only its low 64 bits matter).
-FQ_DEV u64 mul_shift256(const u64 a[4], const u64 m[4]) {
+FQ_HD u64 mul_shift256(const u64 a[4], const u64 m[4]) {
     u64 w0, w1, w2, w3, w4;
     u128 t;
     // row 0
@@ -38,6 +52,7 @@ FQ_DEV u64 mul_shift256(const u64 a[4], const u64 m[4]) {
     return w4;
 }
 
+#if defined(__HIPCC__)
 FQ_DEV void decompose(const u64 m[4], u64 v[4]) {                        // curve4q.py:339-356
     u64 t[4];
 #pragma unroll
@@ -58,6 +73,7 @@ FQ_DEV void decompose(const u64 m[4], u64 v[4]) {                        // curv
 #pragma unroll
     for (int i = 0; i < 4; i++) v[i] = acp[i] ^ (mask & (ac[i] ^ acp[i]));
 }
+#endif
 
 // recode(): sign bit of step i is bit i of `sign` (i < 64; step 64 is always positive), digit of
 // step i is bit i of the planes d[0..2]; `top` is digit 64.
@@ -66,66 +82,85 @@ struct EndoDigits {
     u64 d[3];
     u32 top;
 };
-FQ_DEV EndoDigits recode(const u64 vin[4]) {                             // curve4q.py:358-380
-    EndoDigits r;
-    r.sign = vin[0] >> 1;                       // bit(v1, i+1); bit 64 of a 64-bit value is 0
-    u64 v1 = vin[1], v2 = vin[2], v3 = vin[3];
-    u64 p1 = 0, p2 = 0, p3 = 0;
-    u64 s = r.sign;
-#pragma unroll 1
-    for (int i = 0; i < 64; i++) {
-        u64 nb1 = ~(s >> i) & 1;                // c = (b1 | bj) ^ b1 = ~b1 & bj
-        u64 b;
-        b = v1 & 1; p1 |= b << i; v1 = (v1 >> 1) + (nb1 & b);
-        b = v2 & 1; p2 |= b << i; v2 = (v2 >> 1) + (nb1 & b);
-        b = v3 & 1; p3 |= b << i; v3 = (v3 >> 1) + (nb1 & b);
+// The reference's loop runs, for each of v_1, v_2, v_3 and for i = 0..63,   b = v & 1;  v = (v >> 1) + (~s_i & b)   with s_i bit i of
+// `sign`, and emits b as digit bit i.  Write x for the original v_j, n_i = ~s_i and k_i for what the additions so far have put on top of
+// x >> i (k_0 = 0; it stays 0 or 1).  Then b_i = x_i ^ k_i and k_{i+1} = (n_i & x_i) | ((n_i | x_i) & k_i): the carry recurrence of the
+// 64-bit addition x + N with N = ~sign.  So plane j is (x + N) ^ N, and what is left of v_j after 64 rounds is the carry out of that addition.
+struct EndoPlanes {
+    u64 n;                  // N = ~sign: bit i set when step i subtracts
+    u64 d[3];
+    u32 top;
+};
+FQ_HD EndoPlanes recode_planes(const u64 vin[4]) {
+    EndoPlanes r;
+    r.n = ~(vin[0] >> 1);                       // sign = bit(v1, i+1); bit 64 of a 64-bit value is 0
+    r.top = 0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const u64 t = vin[j + 1] + r.n;
+        r.d[j] = t ^ r.n;
+        r.top |= (u32)(t < r.n) << j;           // the carry out
     }
-    r.d[0] = p1; r.d[1] = p2; r.d[2] = p3;
-    r.top = (u32)(v1 + 2 * v2 + 4 * v3);
+    return r;
+}
+FQ_HD EndoDigits recode(const u64 vin[4]) {                              // curve4q.py:358-380
+    const EndoPlanes p = recode_planes(vin);
+    EndoDigits r;
+    r.sign = ~p.n;
+    r.d[0] = p.d[0]; r.d[1] = p.d[1]; r.d[2] = p.d[2];
+    r.top = p.top;
     return r;
 }
 // The same digits as ONE stream of nibbles for the fused kernels' ladder (round 6: 19 -> 8 glue instructions per ladder step).  Step i
 // (0..63) is nibble i % 8 of word i / 8: bits 0..2 the digit, bit 3 SET when the step SUBTRACTS (sign bit 0, the negation of `sign`
 // above -- so that an arithmetic shift of the nibble's top bit is the negation mask the addition body takes).  The ladder walks the
-// steps from 63 down: it takes the top nibble of word 7 and shifts left.  Built in the same pass as the planes were: no 64-bit
-// variable shifts (`b << i` three times per round above), one 32-bit shift-and-or.
+// steps from 63 down: it takes the top nibble of word 7 and shifts left.
 struct EndoNibbles {
     u32 w[8];
     u32 top;
 };
-FQ_DEV EndoNibbles recode_nibbles(const u64 vin[4]) {                     // curve4q.py:358-380
-    EndoNibbles r;
-    u64 s = vin[0] >> 1;                        // bit(v1, i+1), consumed from the bottom
-    u64 v1 = vin[1], v2 = vin[2], v3 = vin[3];
+// One stage of the interleave below.  The 256 bits of eight words have an 8-bit address: three bits of word index, five of position.
+// This exchanges address bit RB of the word index with address bit PB of the position: in every pair of words that differ in index bit
+// RB, the fields with position bit PB set of the lower word change places with the fields with it clear of the upper one.  Two shifts and
+// two masked merges per pair; everything is a compile-time constant.
+template <int RB, int PB> FQ_HD void exchange_address_bits(u32 x[8]) {
+    constexpr u32 D = 1u << PB;
+    constexpr u32 KEEP = PB == 0 ? 0x55555555u : PB == 1 ? 0x33333333u : PB == 2 ? 0x0f0f0f0fu : PB == 3 ? 0x00ff00ffu : 0x0000ffffu;   // position bit PB clear
 #pragma unroll
-    for (int t = 0; t < 8; t++) r.w[t] = 0;
-#pragma unroll 1
-    for (int k = 0; k < 8; k++) {
-        u32 w = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const u32 nb1 = ~(u32)s & 1;        // c = (b1 | bj) ^ b1 = ~b1 & bj
-            s >>= 1;
-            const u32 b1 = (u32)v1 & 1, b2 = (u32)v2 & 1, b3 = (u32)v3 & 1;
-            v1 = (v1 >> 1) + (nb1 & b1);
-            v2 = (v2 >> 1) + (nb1 & b2);
-            v3 = (v3 >> 1) + (nb1 & b3);
-            w = (w >> 4) | ((b1 | (b2 << 1) | (b3 << 2) | (nb1 << 3)) << 28);
-        }
-#pragma unroll
-        for (int t = 0; t < 7; t++) r.w[t] = r.w[t + 1];      // word k ends up in w[k] after the eighth push
-        r.w[7] = w;
+    for (int lo = 0; lo < 8; lo++) {
+        if (lo & (1 << RB)) continue;
+        const int hi = lo | (1 << RB);
+        const u32 a = x[lo], b = x[hi];
+        x[lo] = (a & KEEP) | ((b << D) & ~KEEP);
+        x[hi] = ((a >> D) & KEEP) | (b & ~KEEP);
     }
-    r.top = (u32)(v1 + 2 * v2 + 4 * v3);
+}
+// Bit (4 i + j) of word k is bit 8 k + i of plane j, the planes being d[0], d[1], d[2], N: a 4 x 64 -> 8 x 32 interleave.  With the eight
+// halves in the order x[2 j + h] a source bit has the address (j1 j0 h | b4 b3 i2 i1 i0) and belongs at (h b4 b3 | i2 i1 i0 j1 j0).  Five
+// exchanges between a word-index bit and a position bit carry every address bit home -- the index bit serves as the free hand of two
+// cycles, (j0 i0 i2 b4) and (j1 i1 b3) -- and leave the word index as (b3 b4 h), which is a renaming.  No loop, no 64-bit shift.
+FQ_HD EndoNibbles recode_nibbles(const u64 vin[4]) {                      // curve4q.py:358-380
+    const EndoPlanes p = recode_planes(vin);
+    u32 x[8] = { (u32)p.d[0], (u32)(p.d[0] >> 32), (u32)p.d[1], (u32)(p.d[1] >> 32), (u32)p.d[2], (u32)(p.d[2] >> 32), (u32)p.n, (u32)(p.n >> 32) };
+    exchange_address_bits<1, 0>(x);             // index (j1 i0 h), position (b4 b3 i2 i1 j0)
+    exchange_address_bits<1, 2>(x);             // index (j1 i2 h), position (b4 b3 i0 i1 j0)
+    exchange_address_bits<1, 4>(x);             // index (j1 b4 h), position (i2 b3 i0 i1 j0)
+    exchange_address_bits<2, 1>(x);             // index (i1 b4 h), position (i2 b3 i0 j1 j0)
+    exchange_address_bits<2, 3>(x);             // index (b3 b4 h), position (i2 i1 i0 j1 j0)
+    EndoNibbles r;
+#pragma unroll
+    for (int k = 0; k < 8; k++) r.w[k] = x[((k & 1) << 2) | (k & 2) | (k >> 2)];
+    r.top = p.top;
     return r;
 }
-FQ_DEV u32 endo_digit(const EndoDigits& e, int i) {   // i in 0..63 (wave-uniform)
+FQ_HD u32 endo_digit(const EndoDigits& e, int i) {   // i in 0..63 (wave-uniform)
     return (u32)((e.d[0] >> i) & 1) | ((u32)((e.d[1] >> i) & 1) << 1) | ((u32)((e.d[2] >> i) & 1) << 2);
 }
-FQ_DEV u32 endo_neg_mask(const EndoDigits& e, int i) { // ~0 when the step subtracts (sign bit 0)
+FQ_HD u32 endo_neg_mask(const EndoDigits& e, int i) { // ~0 when the step subtracts (sign bit 0)
     return (u32)((e.sign >> i) & 1) - 1u;
 }
 
+#if defined(__HIPCC__)
 // ---- fixed window ---------------------------------------------------------------------------------
 // r = m mod N, made odd by adding N (curve4q.py:217-219).  Digit i is then
 //   d_i = ((r >> 4i) & 31 | 1) - 16     (the loop at :220-222 keeps r odd, so r_{i+1} = (r_i >> 4) | 1)
@@ -292,5 +327,7 @@ template <typename S> FQ_DEV void comb_point_scalar(u32 t, u64 m[4]) {
     set_bit(S::E * j);
     for (int r = 0; r < S::W - 1; r++) if ((u >> r) & 1) set_bit(S::E * j + (r + 1) * S::D);
 }
+
+#endif      // __HIPCC__
 
 }  // namespace fq

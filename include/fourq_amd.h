@@ -459,7 +459,10 @@ enum fourq_prim {
     /* arithmetic modulo N (scalar_n.hip.h): inputs ANY value of their width, outputs canonical in [0, N) */
     FOURQ_SC_REDUCE512 = 67,    /* x[8] -> [4]: x mod N */
     FOURQ_SC_MULSUB = 68,       /* r[4] a[4] h[4] -> [4]: (r - a h) mod N */
-    FOURQ_SC_MUL = 69           /* a[4] b[4] -> [4]: a b mod N */
+    FOURQ_SC_MUL = 69,          /* a[4] b[4] -> [4]: a b mod N */
+    /* the digits of FOURQ_SC_RECODE as the fused ladders read them: step i (0..63) is nibble i % 8 of word i / 8, bits 0..2 the digit,
+     * bit 3 set when the step subtracts (sign bit 0) */
+    FOURQ_SC_RECODE_NIBBLES = 70 /* v[4] = decompose(m) -> [9]: the eight 32-bit words, one per output word, then digit 64 */
 };
 int fourq_prim_words(int op, size_t *in_words, size_t *out_words);
 int fourq_prim_batch(fourq_ctx *ctx, int op, const uint64_t *in, uint64_t *out, size_t n);

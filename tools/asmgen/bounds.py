@@ -12,7 +12,7 @@ type it feeds.  fp127.hip.h's static_asserts check the C++ formulas; this checks
 
 Semantics.  A 32-bit register holds a residue mod 2^32; its interval is one integer representative set of it, and a reader may move it by
 a multiple of 2^32 to fit its own interpretation (the neg mask 0xFFFFFFFF is -1 to a v_sub_u32).  The limb mask and the neg mask are
-concrete: v_and with the mask gives [0, 2^26) (the interval itself when it lies inside one 2^26 block), v_xor / v_bitop3 with a neg mask
+concrete: v_and with the mask gives [0, 2^26) (the interval itself when it lies inside one 2^26 block), v_xor / v_xad / v_bitop3 with a neg mask
 of 0 or ~0 are exact.  A 64-bit pair written by one instruction keeps its integer interval; v_alignbit(hi, lo, k) of such a pair is
 floor(acc / 2^k).  A 64-bit read of a pair whose halves were written separately is allowed only when it is exact (high half 0, low half
 in [0, 2^32)).  Anything outside the subset raises.
@@ -256,6 +256,13 @@ class Analysis:
                 self.put(ops[0], None if a is None else (-a[1] - 1, -a[0] - 1))      # ~x == -x - 1 (mod 2^32)
             else:
                 raise ValueError("v_xor_b32 without a concrete neg mask: %r" % ln)
+        elif base == "v_xad_u32":                   # (x ^ neg mask) + c: the exact v_xor_b32 above, then v_add_u32
+            m, a, c = self.concrete(ops[2]), g(ops[1]), g(ops[3])
+            if m not in NEG_MASKS:
+                raise ValueError("v_xad_u32 without a concrete neg mask: %r" % ln)
+            if m and a is not None:
+                a = (-a[1] - 1, -a[0] - 1)
+            self.put(ops[0], None if a is None or c is None else _r32(a[0] + c[0], a[1] + c[1]))
         elif base == "v_bitop3_b32":
             if int(extra, 16) != 0xCA:
                 raise ValueError("bitop3 table " + extra)

@@ -90,6 +90,9 @@ class Prog:
     def xor(self, d, a, b):
         self.op2("v_xor_b32_e32", d, a, b)
 
+    def xad(self, d, a, b, c):          # d = (a ^ b) + c
+        self.emit("v_xad_u32", "v_xad_u32 {0}, {1}, {2}, {3}", [d], [a, b, c])
+
     def sel(self, d, m, x, y):          # d = m ? x : y  bitwise
         self.emit("v_bitop3_b32", "v_bitop3_b32 {0}, {1}, {2}, {3} bitop3:0xca", [d], [m, x, y])
 
@@ -333,7 +336,7 @@ class Body:
 
     def add(self, T):
         """ADD_core (curve4q.py:155-175) of (X, Y, Z, T) and +-entry (N, D, E, F): N and D exchanged by masked selects
-        (GFp2.select, fields.py:236-238), -F by a conditional negation; X, Y, Z in place, Ta = E, Tb = H."""
+        (GFp2.select, fields.py:236-238), -F by a conditional negation (one v_xad_u32 per limb); X, Y, Z in place, Ta = E, Tb = H."""
         g = self.g
         X2, Y2, Z2 = self.X, self.Y, self.Z
         N1 = self.fe2_add(X2, Y2, "N1")
@@ -344,11 +347,11 @@ class Body:
                 g.sel(getattr(sN, part)[i], self.neg, getattr(self.tD, part)[i], getattr(self.tN, part)[i])
             for i in range(5):
                 g.sel(getattr(sD, part)[i], self.neg, getattr(self.tN, part)[i], getattr(self.tD, part)[i])
+        neg1 = g.v("neg1")                   # 1 where the entry is subtracted: -F = (F ^ ~0) + 1, F = (F ^ 0) + 0
+        g.sub(neg1, 0, self.neg)
         for part in ("re", "im"):
             for i in range(5):
-                g.xor(getattr(Fs, part)[i], self.neg, getattr(self.tF, part)[i])
-            for i in range(5):
-                g.sub(getattr(Fs, part)[i], getattr(Fs, part)[i], self.neg)
+                g.xad(getattr(Fs, part)[i], getattr(self.tF, part)[i], self.neg, neg1)
         A2, B2 = self.side_by_side(lambda: self.mul(D1, self.neg_im(D1), sD, self.times8(sD), "A2"),
                                    lambda: self.mul(N1, self.neg_im(N1), sN, self.times8(sN), "B2"))
         C2, D2 = self.side_by_side(lambda: self.mul(Fs, self.neg_im(Fs), T, self.times8(T), "C2"),

@@ -79,6 +79,8 @@ def run(lines, regs, trace=None):
             m.put(ops[0], m.get(ops[1]) & m.get(ops[2]))
         elif base == "v_xor_b32":
             m.put(ops[0], m.get(ops[1]) ^ m.get(ops[2]))
+        elif base == "v_xad_u32":
+            m.put(ops[0], (m.get(ops[1]) ^ m.get(ops[2])) + m.get(ops[3]))
         elif base == "v_lshl_add_u32":
             m.put(ops[0], (m.get(ops[1]) << (m.get(ops[2]) & 31)) + m.get(ops[3]))
         elif base == "v_bitop3_b32":
