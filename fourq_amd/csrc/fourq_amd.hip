@@ -1424,7 +1424,7 @@ FQ_API int fourq_ctx_reserve(fourq_ctx* c, size_t n) {
     CtxGuard g(c);
     if (int rc = ensure_proj(c, n)) return rc;
     using namespace fq_work;
-    return ensure_work(c, std::max({ DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n) }));
+    return ensure_work(c, std::max({ DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n), Msm::bytes(n) }));
 }
 FQ_API int fourq_ctx_lanes(const fourq_ctx* c, size_t* lanes) {
     if (!c || !lanes) return FOURQ_ERR_INVALID;
@@ -1961,6 +1961,68 @@ FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint6
         return fourq_verify_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (const uint8_t*)di[3], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
     }, 0, reserve_double_mul);
 }
+
+// ---- grouped multi-scalar multiplication: out[g] = R1toAffine(sum_j MUL_endo(k_gj, AffineToR1(P_gj))) over groups of one length ----------
+// (1) MUL_endo through mul_rows_dev over all groups x group_size elements, projective rows of 12 or 20 words; (2) fold passes (msm.hip.h),
+// each turning m rows per group into ceil(m / MSM_FOLD), alternating between the layout's two regions until one row per group is left;
+// (3) lower_kernel over the `groups` rows, which also turns a group's largest decode code into its status.  The geometry of every launch
+// follows from (groups, group_size) on the host: nothing is staged and, once the work buffer is large enough, nothing allocated.
+static bool msm_count(size_t groups, size_t group_size, size_t* n) {
+    return !__builtin_mul_overflow(groups, group_size, n) && *n <= FOURQ_MAX_BATCH;
+}
+static int reserve_msm(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::Msm::bytes(big)); }
+static int msm_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!c || !scalars || !points || !out || (encoded && !status)) return FOURQ_ERR_INVALID;
+    if (!aligned16(scalars) || !aligned16(points) || !aligned16(out)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    int rc = reserve_msm(c, n);
+    if (rc) return rc;
+    const fq_work::Msm w(c->work, n);
+    u32 stride;
+    if ((rc = mul_rows_dev(c, ENDO, scalars, points, encoded, w.rows_in, w.rows_out, encoded ? w.st_decode : nullptr, n, &stride))) return rc;
+    const uint64_t* rows = w.rows_out;
+    const uint8_t* st = encoded ? w.st_decode : nullptr;
+    bool to_a = true;
+    for (size_t m = group_size; m > 1; to_a = !to_a) {
+        uint64_t* part = to_a ? w.part_a : w.part_b;
+        uint8_t* part_st = to_a ? w.st_a : w.st_b;
+        HIPRC_TRY(c, chain_launch_msm_fold(c->stream, rows, stride, st, part, part_st, groups, m));
+        m = (m + MSM_FOLD - 1) / MSM_FOLD;
+        rows = part; stride = 12;
+        if (encoded) st = part_st;
+    }
+    return launch_lower(c, encoded, rows, stride, st, (uint64_t*)out, status, groups);
+}
+// Host arrays: copy in, the _dev call, copy out, synchronously through the staging buffer.  No chunk overlap: run_pipeline's arrays are per
+// element, and this output is per group.
+static int msm_host(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!c || !scalars || !points || !out || (encoded && !status)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    const size_t point_bytes = encoded ? 32 : 64;
+    int rc = ensure_stage(c, n * (32 + point_bytes) + groups * (point_bytes + 1));
+    if (rc) return rc;
+    char* d_scalars = (char*)c->stage;
+    char* d_points = d_scalars + n * 32;
+    char* d_out = d_points + n * point_bytes;
+    char* d_status = d_out + groups * point_bytes;
+    HIP_TRY(c, hipMemcpyAsync(d_scalars, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_points, points, n * point_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = msm_dev(c, (const uint64_t*)d_scalars, d_points, encoded, d_out, encoded ? (uint8_t*)d_status : nullptr, groups, group_size))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, groups * point_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (encoded) HIP_TRY(c, hipMemcpyAsync(status, d_status, groups, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FOURQ_OK;
+}
+FQ_API int fourq_msm_affine_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size) { return msm_dev(c, s, p, false, o, nullptr, groups, group_size); }
+FQ_API int fourq_msm_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return msm_dev(c, s, p, true, o, st, groups, group_size); }
+FQ_API int fourq_msm_affine_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size) { return msm_host(c, s, p, false, o, nullptr, groups, group_size); }
+FQ_API int fourq_msm_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return msm_host(c, s, p, true, o, st, groups, group_size); }
 
 // ---- signatures from bytes (include/fourq_amd.h): SHA-512 and the arithmetic modulo N on the device (sig.hip.h) around the comb, the
 // ladder and the combiner.  Every intermediate -- H(sk), the nonce, the challenge, s / h / R as rows -- lives in the context's work buffer.

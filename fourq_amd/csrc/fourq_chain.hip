@@ -1,12 +1,14 @@
 // Second translation unit of libfourq_amd.so: the kernels that profit from chained carries (FQ_CHAIN=1, see
 // kernels.hip.h): fixed-base ladders (table in LDS), the two-kernel route for large variable-base batches
 // (prep_kernel + ladder_kernel<PREBUILT>), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
-// translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P.
+// translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P,
+// msm.hip.h the one that folds the ladder's rows of a group into one.
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
 #endif
 #include "kernels.hip.h"
 #include "combine.hip.h"
+#include "msm.hip.h"
 
 namespace fq {
 
@@ -79,6 +81,18 @@ int chain_launch_combine(int k, int out_kind, hipStream_t stream, const uint4* p
     if (out_kind == COMBINE_AFFINE) return launch_combine<COMBINE_AFFINE>(k, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
     if (out_kind == COMBINE_ENCODE) return launch_combine<COMBINE_ENCODE>(k, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
     return launch_combine<COMBINE_VERIFY>(k, stream, proj, proj_stride, rows, row_stride, st_decode, expect, out, status, ok, n);
+}
+// One fold pass of a grouped sum (msm.hip.h).  A team is as wide as its segment is long, up to 16 lanes: a full segment of MSM_FOLD rows
+// then costs a lane 3 + 4 dependent additions, and a group of two one.
+int chain_launch_msm_fold(hipStream_t stream, const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out, size_t groups, size_t m_in) {
+    const size_t m_out = (m_in + MSM_FOLD - 1) / MSM_FOLD, segment = m_in < MSM_FOLD ? m_in : MSM_FOLD;
+    u32 team = 1;
+    while (team < 16 && team < segment) team *= 2;
+    const u64 teams = (u64)groups * m_out, blocks = (teams * team + BLOCK - 1) / BLOCK;
+    if (blocks == 0 || blocks > 0x7fffffffu || m_in > 0xffffffffu) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(msm_fold_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, stream, rows, stride, st_in, rows_out, st_out, (u32)m_in, (u32)m_out, team,
+                       (u32)((segment + team - 1) / team), teams);
+    return (int)hipGetLastError();
 }
 
 }  // namespace fq

@@ -1164,6 +1164,10 @@ int chain_launch_normalize(int k, hipStream_t stream, const uint4* proj, u32 pro
 enum CombineOut { COMBINE_AFFINE = 0, COMBINE_ENCODE = 1, COMBINE_VERIFY = 2 };
 int chain_launch_combine(int k, int out_kind, hipStream_t stream, const uint4* proj, u32 proj_stride, const u64* rows, u32 row_stride, const uint8_t* st_decode,
                          const u64* expect, u64* out, uint8_t* status, uint8_t* ok, u32 n);
+// msm.hip.h: one fold pass of a grouped sum.  Rows of `stride` words, m_in per group, become canonical 12-word rows, ceil(m_in / MSM_FOLD) per group;
+// st_in (NULL: none) / st_out: one raw decode code per row, folded as a maximum
+constexpr u32 MSM_FOLD = 64;
+int chain_launch_msm_fold(hipStream_t stream, const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out, size_t groups, size_t m_in);
 // constant-time selection builds of the same kernels: fourq_ct_fused.hip (FQ_CHAIN=0) and fourq_ct_chain.hip (FQ_CHAIN=1)
 int ct_launch_fused(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);
 int ct_launch_pair(int algo, bool dh, bool fixed, bool quad, unsigned grid, hipStream_t stream, const LadderArgs& a);

@@ -80,5 +80,18 @@ struct H2c {                        // hash to curve
     H2c(char* base, size_t n) { Carver w(base); u = w.take<uint64_t>(n * 8); end = w.used; }
     static size_t bytes(size_t n) { return H2c(nullptr, n).end; }
 };
+// Grouped sums out[g] = sum [k]P over groups of one length; n = groups x group_size elements.  A fold pass turns m rows per group into
+// ceil(m / 64), which is at most floor(m / 2) for m >= 2: the first pass leaves at most n / 2 rows, the second at most n / 4, and later
+// passes alternate between the same two regions with fewer rows still.  392 n bytes + 1.75 n of status, below SigVerify's 416 n + 3 n:
+// fourq_ctx_reserve does not grow.
+struct Msm {
+    uint64_t *rows_in, *rows_out;   // as MulRows
+    uint8_t* st_decode;
+    uint64_t *part_a, *part_b;      // partial sums, rows of 12 words: n / 2 and n / 4 of them
+    uint8_t *st_a, *st_b;           // the largest decode code among a partial sum's elements
+    size_t end;
+    Msm(char* base, size_t n) { Carver w(base); rows_in = w.take<uint64_t>(n * 20); rows_out = w.take<uint64_t>(n * 20); st_decode = w.take_status(n); part_a = w.take<uint64_t>(n / 2 * 12); st_a = w.take_status(n / 2); part_b = w.take<uint64_t>(n / 4 * 12); st_b = w.take_status(n / 4); end = w.used; }
+    static size_t bytes(size_t n) { return Msm(nullptr, n).end; }
+};
 
 }  // namespace fq_work

@@ -374,6 +374,44 @@ class Engine:
     def verify_bytes_dev(self, k_scalars, l_scalars, keys32, expect32, ok, status, n, comb_host=None):
         self._ck(self._lib.fourq_verify_bytes_batch_dev(self._ctx, _ptr(k_scalars), _ptr(self._comb_arg(comb_host)), _ptr(l_scalars), _ptr(keys32), _ptr(expect32), _ptr(ok), _ptr(status), n))
 
+    # ---- grouped multi-scalar multiplication (fourq_msm_*): out[g] = sum_j [k_gj]P_gj over groups of one length ----------------
+    @staticmethod
+    def _groups(n, group_size):
+        group_size = int(group_size)
+        if group_size <= 0:
+            raise ValueError("group_size must be positive")
+        if n % group_size:
+            raise ValueError("%d elements are not a whole number of groups of %d" % (n, group_size))
+        return n // group_size, group_size
+
+    def msm(self, scalars, points_affine, group_size, out=None):
+        """Canonical affine sums, (n // group_size, 8) words: out[g] = sum of [k_i]P_i over the group_size elements of group g, laid out
+        group after group.  Checks nothing, like MUL_*; the neutral point (0, 1) is an ordinary result.  Ragged groups: pad with scalar 0."""
+        k, p = _host(scalars, 4), _host(points_affine, 8)
+        if len(k) != len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        groups, group_size = self._groups(len(k), group_size)
+        out = _out(out, groups, 8)
+        self._ck(self._lib.fourq_msm_affine_batch(self._ctx, _ptr(k), _ptr(p), _ptr(out), groups, group_size))
+        return out
+
+    def msm_bytes(self, scalars, points32, group_size, out=None, status=None):
+        """encode(sum of [k_i]decode(points32[i])) per group: ((n // group_size, 32) bytes, status); status[g] = 0 or BYTES_DECODE_BASE +
+        the largest DECODE_* among the group's elements (out[g] is zero then; decode() tells which element it was)."""
+        k, p = _host(scalars, 4), _host(points32, 32, np.uint8)
+        if len(k) != len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        groups, group_size = self._groups(len(k), group_size)
+        out, status = _out(out, groups, 32, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_msm_bytes_batch(self._ctx, _ptr(k), _ptr(p), _ptr(out), _ptr(status), groups, group_size))
+        return out, status
+
+    def msm_dev(self, scalars, points_affine, out_affine, groups, group_size):
+        self._ck(self._lib.fourq_msm_affine_batch_dev(self._ctx, _ptr(scalars), _ptr(points_affine), _ptr(out_affine), groups, group_size))
+
+    def msm_bytes_dev(self, scalars, points32, out32, status, groups, group_size):
+        self._ck(self._lib.fourq_msm_bytes_batch_dev(self._ctx, _ptr(scalars), _ptr(points32), _ptr(out32), _ptr(status), groups, group_size))
+
     # ---- signatures from bytes (fourq_sha512_* / fourq_sig_*): SHA-512 and the arithmetic modulo N run on the device -------------
     @staticmethod
     def _msgs(msgs, lens, n=None):

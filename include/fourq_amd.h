@@ -331,6 +331,35 @@ int fourq_verify_bytes_batch(fourq_ctx *ctx, const uint64_t *k_scalars, const ui
 int fourq_verify_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
                                  const uint8_t *points32, const uint8_t *expect32, uint8_t *ok, uint8_t *status, size_t n);
 
+/* ---- grouped multi-scalar multiplication: out[g] = sum_j [k_gj]P_gj, the only call that adds across elements ----------------------------
+ * groups x group_size = n elements laid out group after group (element i belongs to group i / group_size); every group has the same
+ * length.  A caller with ragged groups pads with scalar 0: the addition is complete, so the neutral [0]P is an ordinary operand.  The pad
+ * point is the neutral (0, 1) or any other point on the affine flavour, and any string that DECODES on the bytes flavour (a valid key;
+ * the neutral's own encoding 01 00 .. 00 is refused by decode, FOURQ_DECODE_REF_ATTRIBUTE_ERROR, and would mark its group).
+ *
+ * out_affine[g] = R1toAffine(sum over j < group_size of MUL_endo(k_gj, AffineToR1(P_gj)))  canonical, groups x 8 words, the sum taken with
+ * the complete twisted-Edwards addition; every order of folding gives the same canonical point.  Scalars: any value in [0, 2^256).
+ * Checks nothing, like MUL_* and fourq_double_mul_*; the neutral point is a result like any other ((0, 1): no status, nothing zeroed).
+ * On the device: MUL_endo over all n elements, fold passes that each turn m projective rows per group into ceil(m / 64), and one
+ * R1toAffine per group; nothing but the `groups` results leaves the device.
+ *
+ * groups == 0: FOURQ_OK, nothing touched.  group_size == 0 with groups > 0, or groups * group_size (overflow-checked) above
+ * FOURQ_MAX_BATCH: FOURQ_ERR_INVALID.  _dev: enqueues on the context's stream and returns; every array pointer 16-byte aligned
+ * (status need not be); after fourq_ctx_reserve(ctx, n) a call of at most n elements allocates and synchronises nothing.  The host-array
+ * calls are synchronous -- copy in, the _dev call, copy out -- WITHOUT the chunk overlap of the per-element calls: the pipeline's arrays
+ * are per element and this output is per group. */
+int fourq_msm_affine_batch(fourq_ctx *ctx, const uint64_t *scalars, const uint64_t *points_affine, uint64_t *out_affine, size_t groups,
+                           size_t group_size);
+int fourq_msm_affine_batch_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint64_t *points_affine, uint64_t *out_affine, size_t groups,
+                               size_t group_size);
+/* The same on 32-byte encodings: decode(points32[i]) in, encode(...) out, groups x 32 bytes.
+ * status[g]: 0 | FOURQ_BYTES_DECODE_BASE + the LARGEST FOURQ_DECODE_* among the group's elements (out32[g] is all zero then; the other
+ * groups are not affected).  A maximum folds in any order; fourq_decode_batch over the group's encodings tells which element it was. */
+int fourq_msm_bytes_batch(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status, size_t groups,
+                          size_t group_size);
+int fourq_msm_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status,
+                              size_t groups, size_t group_size);
+
 /* ---- signatures from bytes: SchnorrQ-shaped sign / verify with SHA-512 and the arithmetic modulo N on the device ---------------------
  * Nothing but byte arrays crosses the ABI -- secret keys, public keys, messages, signatures, one ok and one status byte per row -- and no
  * intermediate (the hash of the secret key, the nonce, the challenge, R as a point) is ever on the host.  With H = SHA-512, LE(x) the
