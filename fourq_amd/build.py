@@ -36,15 +36,12 @@ BUNDLE_COMPRESS = [] if os.environ.get("FOURQ_BUILD_NO_COMPRESS") == "1" else ["
 
 # (regex on the demangled kernel name, field, predicate, why).  Checked for the product build only (no extra flags).
 RESOURCE_POLICY = [
-    (r"ladder_kernel<\d, 2,", "scratch", lambda v: v == 0, "the two-kernel route's ladders must not spill"),
-    (r"ladder_kernel<\d, 2, true", "occupancy", lambda v: v >= 4, "the two-kernel route's DH ladders are sized for 4 waves per SIMD (128 VGPRs)"),
-    (r"ladder_kernel<\d, 2, false", "occupancy", lambda v: v >= 2, "the two-kernel route's MUL ladders run the asm bodies at 2 waves per SIMD"),
     (r"ladder_kernel<\d, 1, \w+, \w+, false>", "scratch", lambda v: v == 0, "the fixed-base ladders (MUL and DH) must not spill"),
     (r"ladder_kernel<\d, 1, \w+, \w+, false>", "occupancy", lambda v: v >= 2, "the fixed-base ladders run the asm bodies at 2 waves per SIMD"),
     (r"ladder_kernel<\d, 1, \w+, \w+, true>", "scratch", lambda v: v == 0, "the constant-time fixed-base ladders must not spill"),
     (r"ladder_kernel<\d, 0,", "scratch", lambda v: v == 0, "the fused variable-base kernels must not spill to memory (AGPR copies are fine)"),
     (r"pair_kernel<", "scratch", lambda v: v == 0, "the two-lanes-per-element kernel must not spill"),
-    (r"prep_kernel<0, \w+>\(", "occupancy", lambda v: v >= 2, "prep_kernel<ENDO> hides its read-backs behind a second wave per SIMD"),
+    (r"\bprep_kernel<0>\(", "scratch", lambda v: v == 0, "prep_kernel (the tables of the constant-time mixed tail) runs the endomorphisms at one wave per SIMD and must not spill"),
     (r"mixed_ct_tail_kernel<", "occupancy", lambda v: v >= 2, "the constant-time mixed-batch tail runs the asm bodies at two waves per SIMD"),
     (r"mixed_ct_tail_kernel<", "scratch", lambda v: v == 0, "the constant-time mixed-batch tail must not spill"),
     (r"comb_kernel<true, false>", "scratch", lambda v: v == 0, "the keygen comb of large batches (deferred normalisation) must not touch scratch memory"),

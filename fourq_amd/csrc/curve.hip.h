@@ -345,12 +345,8 @@ template <typename P> FQ_DEV void store_r2_limbs(P* dst, const R2& t) {
     store_fe2_limbs(dst + 2 * COORD_U32, t.E); store_fe2_limbs(dst + 3 * COORD_U32, t.F);
 }
 
-// Slot layouts of a per-lane table in HBM scratch.  A ladder step gathers one entry per lane, so the entry's size in
-// 64-byte memory sectors is the traffic of the step:
-//   LimbSlots    4 coordinates x 48 bytes, ready-to-use limbs: 192 bytes = 3 sectors (also the LDS layout)
-//   PackedSlots  4 coordinates x 32 bytes, each GF(p) element as one 128-bit word (value < 2^128, not necessarily
-//                canonical): 128 bytes = 2 sectors, at the price of 8 cheap ALU ops per element on every load.
-// (160 bytes of bare limbs would still straddle 3 sectors.)  PARK_P / PARK_Q: where table_endo parks its working points.
+// Slot layouts of a per-lane table in HBM scratch.  LimbSlots: whole entries, 4 coordinates x 48 bytes of ready-to-use limbs
+// (also the LDS layout).  PARK_P / PARK_Q: where table_endo parks its working points.
 struct LimbSlots {
     static constexpr int COORD = COORD_U32, ENTRY = R2_LIMBS, PARK_P = 8 * R2_LIMBS, PARK_Q = 8 * R2_LIMBS + 40, SLOT = 464;
     template <typename P> static FQ_DEV Fe2<1> load(const P* src) { return load_fe2_limbs(src); }
@@ -387,17 +383,6 @@ FQ_DEV Fe<1> fe_unpack128(const uint4& w) {
     r.l[4] = w.w >> 8;                                   // 24 bits
     return r;
 }
-struct PackedSlots {
-    static constexpr int COORD = 8, ENTRY = 32, PARK_P = 8 * 32, PARK_Q = 8 * 32 + 32, SLOT = 320;
-    template <typename P> static FQ_DEV Fe2<1> load(const P* src) {
-        const uint4* q = reinterpret_cast<const uint4*>(src);
-        Fe2<1> r; r.re = fe_unpack128(q[0]); r.im = fe_unpack128(q[1]); return r;
-    }
-    template <typename P> static FQ_DEV void store(P* dst, const Fe2<1>& v) {
-        uint4* q = reinterpret_cast<uint4*>(dst);
-        q[0] = fe_pack128(v.re); q[1] = fe_pack128(v.im);
-    }
-};
 template <typename L, typename P> FQ_DEV R2 load_r2(const P* src) {
     R2 t;
     t.N = L::load(src); t.D = L::load(src + L::COORD); t.E = L::load(src + 2 * L::COORD); t.F = L::load(src + 3 * L::COORD);

@@ -1,6 +1,6 @@
 // libfourq_amd.so -- first translation unit: the fused variable-base kernels, the small service kernels
 // (tables, partition, wire format, primitives) and the C ABI declared in include/fourq_amd.h.  The
-// fixed-base, two-kernel-route and comb kernels live in fourq_chain.hip; shared device code in kernels.hip.h.
+// fixed-base and comb kernels live in fourq_chain.hip; shared device code in kernels.hip.h.
 //
 // Kernel design (gfx950): one wavefront lane owns one (scalar, point) pair for the whole scalar
 // multiplication.  Lanes never communicate; a workgroup is 256 lanes; the grid is sized to the
@@ -11,8 +11,7 @@
 //   variable base : the lane builds its own 8-entry R2 table (table_endo / table_windowed): N, D of every entry into
 //                   a 768-byte slot of HBM scratch (96 bytes per entry = two memory sectors), E, F into its rows of
 //                   LDS; each ladder step then gathers the coordinates of the entry its digit selects (wavefront-
-//                   level gather, one entry per lane) a whole doubling ahead of their use.  Large batches build the
-//                   tables in a kernel of their own into packed 128-byte entries and ladder at four waves per SIMD.
+//                   level gather, one entry per lane) a whole doubling ahead of their use.
 //   fixed base    : the 8-entry table is staged once per workgroup into LDS (padded to dodge bank
 //                   conflicts) and gathered from there.
 //   selection     : as the reference's selectpt (curve4q.py:193-206): the sign of a digit is applied by masked selects
@@ -47,13 +46,9 @@ using namespace fq;
 namespace {
 
 // packed table (8 x 16 words) -> working limbs (8 x 48 u32)
-__global__ void table_unpack_kernel(const u64* packed, u32* limbs, u32* slots) {
+__global__ void table_unpack_kernel(const u64* packed, u32* limbs) {
     int k = threadIdx.x;
-    if (k < 8) {
-        const R2 t = load_r2_packed(packed + 16 * k);
-        store_r2_limbs(limbs + k * R2_LIMBS, t);
-        store_r2<PrebuiltSlots>(slots + k * PrebuiltSlots::ENTRY, t);     // what a mixed batch's per-lane pointer reads
-    }
+    if (k < 8) store_r2_limbs(limbs + k * R2_LIMBS, load_r2_packed(packed + 16 * k));
 }
 // working limbs of one lane's scratch slot -> packed table
 __global__ void table_build_kernel(int algo, const u64* p_r1, u32* scratch, u64* packed) {
@@ -63,14 +58,11 @@ __global__ void table_build_kernel(int algo, const u64* p_r1, u32* scratch, u64*
     for (int k = 0; k < 8; k++) store_r2_packed(packed + 16 * k, load_r2_limbs(scratch + k * R2_LIMBS));
 }
 // Mixed batches: compacts the ids of the variable-base elements of one round (flags[i] != 0) into var_list (any
-// order) and records, per element of the round, which scratch slot holds its table: slot_of[i] = rank in var_list,
-// or ~0 for a fixed-base element (shared table).  Sixteen flags per lane, a block scan in LDS and one atomic per
-// 4 096 elements; one atomic per element (or per wave) serialises on the counter.
+// order), counted in counter[0].  Sixteen flags per lane, a block scan in LDS and one atomic per 4 096 elements; one
+// atomic per element (or per wave) serialises on the counter.
 constexpr int PART_PER_LANE = 16;
-// fix_list (optional; constant-time mode runs the two kinds as two launches): the ids of the fixed-base elements,
-// counted in counter[1].
-__global__ __launch_bounds__(BLOCK) void partition_kernel(const uint8_t* flags, u32 n, u32 first_id, u32* var_list, u32* slot_of, u32* counter,
-                                                          u32* fix_list) {
+// fix_list (optional): the ids of the fixed-base elements, counted in counter[1].
+__global__ __launch_bounds__(BLOCK) void partition_kernel(const uint8_t* flags, u32 n, u32 first_id, u32* var_list, u32* counter, u32* fix_list) {
     __shared__ u32 scan[BLOCK], base, base_fix;
     const u32 t = threadIdx.x;
     const u32 first = (blockIdx.x * BLOCK + t) * PART_PER_LANE;
@@ -111,11 +103,8 @@ __global__ __launch_bounds__(BLOCK) void partition_kernel(const uint8_t* flags, 
 #pragma unroll
     for (int k = 0; k < PART_PER_LANE; k++) {
         if ((u32)k >= valid) break;
-        if (f[k] != 0) { var_list[rank] = first_id + first + k; slot_of[first + k] = rank++; }
-        else {
-            slot_of[first + k] = ~0u;
-            if (fix_list) fix_list[rank_fix++] = first_id + first + k;
-        }
+        if (f[k] != 0) var_list[rank++] = first_id + first + k;
+        else if (fix_list) fix_list[rank_fix++] = first_id + first + k;
     }
 }
 
@@ -474,13 +463,9 @@ struct fourq_ctx {
     int cus = 0;
     size_t lanes = 0;              // resident lanes of the fused variable-base kernels (1 wave per SIMD)
     size_t lanes_w4 = 0;           // resident lanes of the 128-VGPR kernels (4 waves per SIMD)
-    size_t split_min = 0;          // variable-base batches of at least this many elements take the prep + ladder route
-    size_t split_chunk = 0;        // elements per prep + ladder round (<= lanes_w4)
-    bool split_all = false;        // FOURQ_SPLIT_ALL=1: route plain MUL_endo through prep + ladder from split_min on (tests)
-    size_t split_endo_min = 0;     // plain MUL_endo batches of at least this many elements take prep + ladder (0: never)
-    u32* scratch = nullptr;        // per-lane / per-element table slots: the largest of the three users (fourq_ctx_create)
+    size_t mixed_round = 0;        // elements per round of a mixed batch (<= lanes_w4; FOURQ_MIXED_ROUND)
+    u32* scratch = nullptr;        // table slots: the largest of its users (fourq_ctx_create)
     u32* table_limbs = nullptr;    // 8 x 48: the staged fixed-base table as working limbs
-    u32* table_slots = nullptr;    // the same in the PrebuiltSlots layout
     u64* table_packed = nullptr;   // 128 words
     u32* comb_limbs = nullptr;     // FOURQ_COMB_POINTS x 36 working limbs of the staged comb table
     u64* comb_packed = nullptr;    // FOURQ_COMB_POINTS x 12 words
@@ -490,11 +475,11 @@ struct fourq_ctx {
     bool comb_known = false;           // comb_shadow holds a caller's table (it survives a change of stream; the device copy is staged again from it)
     hipEvent_t shadow_read = nullptr;   // recorded behind every upload from a shadow: a shadow is rewritten only after its last upload has read it
     u32* part_counter = nullptr;   // mixed batches: number of variable-base elements of the current round (device side)
-    u32* part_list = nullptr;      // their ids, split_chunk entries
-    u32* part_slot = nullptr;      // per element of the round: scratch slot of its table, ~0 = shared table
-    u32* part_fix = nullptr;       // constant-time mode: ids of the round's fixed-base elements
+    u32* part_list = nullptr;      // their ids, lanes_w4 entries
+    u32* part_fix = nullptr;       // ids of the round's fixed-base elements
     bool ct = false;               // constant-time table selection (FOURQ_CT_SELECT / fourq_ctx_set_ct_select)
-    int mixed_queue = -1;          // mixed batches through the persistent work-queue kernel: 1 always, 0 never, -1 = where it measured faster
+    int mixed_queue = -1;          // FOURQ_MIXED_QUEUE (test hook): 0 or 1 keeps a mixed batch off the pair-lane kernels; in constant-time mode 1 forces the
+                                   // work-queue kernel and 0 the fused kernel + mixed_ct_tail_kernel for every round; the default mode runs the queue kernel either way
     size_t quad_max = 0;           // ... and of at most this many, four lanes per element (a quarter generation fills the chip)
     size_t pair_max = 0;           // variable-base batches (and tails past whole generations) of at most this many elements run two lanes per element
     uint4* proj = nullptr;         // deferred normalisation of DH batches: PROJ_PLANES planes of proj_capacity uint4, grown on demand
@@ -583,29 +568,15 @@ template <int ALGO, int SRC, bool DH> int launch_ladder(fourq_ctx* c, LadderArgs
     unsigned grid = (unsigned)(blocks_needed < blocks_max ? blocks_needed : blocks_max);
     a.scratch = c->scratch;
     a.table = c->table_limbs;
-    a.table_slots = c->table_slots;
     if (c->ct) {                            // constant-time selection: fourq_ct_fused.hip / fourq_ct_chain.hip
-        if (SRC == PREBUILT) return FOURQ_ERR_INVALID;    // the two-kernel route is not taken in this mode
         HIPRC_TRY(c, SRC == FUSED ? ct_launch_fused(ALGO, DH, grid, c->stream, a) : ct_launch_lds(ALGO, DH, grid, c->stream, a));
     } else if (SRC == FUSED) {              // this translation unit's code object (FQ_CHAIN=0)
         hipLaunchKernelGGL((ladder_kernel<ALGO, FUSED, DH>), dim3(grid), dim3(BLOCK), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());
     } else {                                // fourq_chain.hip's (FQ_CHAIN=1)
-        HIPRC_TRY(c, chain_launch_ladder(ALGO, SRC, DH, grid, c->stream, a));
+        HIPRC_TRY(c, chain_launch_ladder(ALGO, DH, grid, c->stream, a));
     }
     return FOURQ_OK;
-}
-// Which variable-base batches take the two-kernel route (prep_kernel + ladder_kernel<PREBUILT>, up to 4 waves per SIMD).
-// Measured on MI355X (profiles/r02_split_route.txt, profiles/r03_cliff.txt): MUL_windowed gains 8 % and DH_* 2-3 % at 2^20, and
-// both 3-6 % from the first element past one resident generation of the fused kernels.  Plain MUL_endo, whose 64-step ladder
-// hardly amortises the second launch, lost 7 % on this route in round 1 (192-byte entries: a round's tables, 486 MB, fell out of
-// the Infinity Cache), gained 1-3 % once the entries were packed, and loses 3-4 % again at 2^20 since the fused kernel keeps E, F
-// in LDS and runs on signed limbs (5.21 ms against 5.43): it stays fused (FOURQ_SPLIT_ENDO_MIN = smallest batch that would take
-// the route, 0 = never).
-bool takes_split_route(const fourq_ctx* c, int algo, bool dh, size_t n) {
-    if (c->ct) return false;        // constant-time mode keeps the lane's table in registers: fused kernels only
-    if (algo == WINDOWED || dh || c->split_all) return n >= c->split_min;
-    return c->split_endo_min && n >= c->split_endo_min;
 }
 // The variable-base kernels with two lanes per element (pair.hip.h): 0.66 of the one-lane kernels' latency for at most half a
 // generation of elements.  A batch that small runs on them alone; a batch of q generations + r elements, 0 < r <= pair_max, on the
@@ -654,50 +625,24 @@ int launch_pair_mixed(fourq_ctx* c, LadderArgs a) {
 // of fourq_chain.hip take over above that: one lane per element, up to four waves per SIMD)
 bool fixed_takes_pair(const fourq_ctx* c, size_t n) { return c->pair_max && n <= c->pair_max; }
 // The route of a variable-base batch.  PAIR_TAIL: whole fused generations, then the remainder two lanes per element (also a batch
-// that is nothing but such a remainder).  Below two generations it beats the two-kernel route for every entry point (65 792
-// elements: DH_endo 0.69 against 0.74 ms, MUL_windowed 1.10 against 1.19); from two generations on the two-kernel route's four
-// wave slots per SIMD absorb a remainder by themselves.
-enum Route { ROUTE_FUSED, ROUTE_PAIR_TAIL, ROUTE_SPLIT };
-Route variable_route(const fourq_ctx* c, int algo, bool dh, size_t n, bool indexed) {
+// that is nothing but such a remainder).
+enum Route { ROUTE_FUSED, ROUTE_PAIR_TAIL };
+Route variable_route(const fourq_ctx* c, size_t n, bool indexed) {
     const size_t tail = n % c->lanes;
-    const bool pair_tail = !indexed && c->pair_max && tail != 0 && tail <= c->pair_max;
-    if (pair_tail && n < 2 * c->lanes) return ROUTE_PAIR_TAIL;
-    if (takes_split_route(c, algo, dh, n)) return ROUTE_SPLIT;
-    return pair_tail ? ROUTE_PAIR_TAIL : ROUTE_FUSED;
+    return !indexed && c->pair_max && tail != 0 && tail <= c->pair_max ? ROUTE_PAIR_TAIL : ROUTE_FUSED;
 }
 template <int ALGO, bool DH> int launch_variable(fourq_ctx* c, LadderArgs a) {
-    const Route route = variable_route(c, ALGO, DH, a.n, a.index != nullptr);
-    if (route == ROUTE_PAIR_TAIL) {
-        const u32 tail = (u32)(a.n % c->lanes);
-        LadderArgs whole = a, rest = a;
-        whole.n = a.n - tail;
-        rest.base = a.base + whole.n; rest.n = tail;
-        int rc = whole.n ? launch_ladder<ALGO, FUSED, DH>(c, whole) : FOURQ_OK;
-        return rc ? rc : launch_pair<ALGO, DH>(c, rest);
-    }
-    if (route == ROUTE_FUSED) return launch_ladder<ALGO, FUSED, DH>(c, a);
-    const u32 total = a.n;
-    for (u32 off = 0; off < total; off += (u32)c->split_chunk) {
-        LadderArgs part = a;
-        part.base = a.base + off;
-        part.n = total - off < (u32)c->split_chunk ? total - off : (u32)c->split_chunk;
-        part.scratch = c->scratch;
-        HIPRC_TRY(c, chain_launch_prep(ALGO, DH, (part.n + BLOCK - 1) / BLOCK, c->stream, part));
-        int rc = launch_ladder<ALGO, PREBUILT, DH>(c, part);
-        if (rc) return rc;
-    }
-    return FOURQ_OK;
+    if (variable_route(c, a.n, a.index != nullptr) == ROUTE_FUSED) return launch_ladder<ALGO, FUSED, DH>(c, a);
+    const u32 tail = (u32)(a.n % c->lanes);
+    LadderArgs whole = a, rest = a;
+    whole.n = a.n - tail;
+    rest.base = a.base + whole.n; rest.n = tail;
+    int rc = whole.n ? launch_ladder<ALGO, FUSED, DH>(c, whole) : FOURQ_OK;
+    return rc ? rc : launch_pair<ALGO, DH>(c, rest);
 }
 
-// Mixed batches: the persistent work-queue kernel where it measured faster than compaction + prep + pointer-selected ladder
-// (profiles/r03_mixed_queue.txt).  A round that fits one generation of resident lanes is one launch instead of three (2^16
-// elements: 0.39 ms against 0.42, constant-time mode 0.48 against 0.81).  Past that the queue hands a wave a third item as soon
-// as the kinds do not split evenly -- BASELINE config 5's 65 550 variable-base elements of 2^17: 0.88 ms against 0.65 -- where the
-// two-kernel route's ladder still has three free wave slots per SIMD.  FOURQ_MIXED_QUEUE=0|1 forces either.
-// Mixed rounds through the persistent work-queue kernel (BASELINE config 5's mechanism): every round in the default mode -- since its items
-// run over the two lists laid end to end it beats compaction + prep + pointer-selected ladder at every size (config 5: 0.609 against 0.630 ms,
-// 2^20 elements 4.40 against 4.53, profiles/r04_mixed_queue.txt) -- and rounds of at most one generation in constant-time mode, where the
-// fused kernel + mixed_ct_tail_kernel pair is as fast for larger ones (0.800 both).
+// Mixed rounds run on the persistent work-queue kernel (BASELINE config 5's mechanism; profiles/r04_mixed_queue.txt), except that in
+// constant-time mode a round larger than one generation takes the fused kernel + mixed_ct_tail_kernel, which is as fast there (0.800 ms both).
 bool mixed_queue_default(const fourq_ctx* c, size_t round) { return !c->ct || round <= c->lanes; }
 
 // DH outputs are affine: from two resident generations of lanes upwards each lane meets several elements, and
@@ -745,7 +690,7 @@ int stage_table(fourq_ctx* c, const uint64_t* table_host) {
     memcpy(c->table_shadow, table_host, sizeof c->table_shadow);
     HIP_TRY(c, hipMemcpyAsync(c->table_packed, c->table_shadow, FOURQ_TABLE_WORDS * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(c->shadow_read, c->stream));
-    hipLaunchKernelGGL(table_unpack_kernel, dim3(1), dim3(64), 0, c->stream, c->table_packed, c->table_limbs, c->table_slots);
+    hipLaunchKernelGGL(table_unpack_kernel, dim3(1), dim3(64), 0, c->stream, c->table_packed, c->table_limbs);
     HIP_TRY(c, hipGetLastError());
     c->table_staged = true;
     return FOURQ_OK;
@@ -760,7 +705,7 @@ int mul_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* poi
     LadderArgs a = {};
     a.scalars = scalars; a.points = points; a.out = out; a.index = index; a.n = (u32)n;
     if (io) {                                       // only the fused one-lane kernels read LadderArgs::io: the caller has checked the route (fused_io)
-        if (!points || index || variable_route(c, algo, false, n, false) != ROUTE_FUSED) return FOURQ_ERR_INVALID;
+        if (!points || index || variable_route(c, n, false) != ROUTE_FUSED) return FOURQ_ERR_INVALID;
         a.io = io;
     }
     if (points) return algo == ENDO ? launch_variable<ENDO, false>(c, a) : launch_variable<WINDOWED, false>(c, a);
@@ -784,10 +729,8 @@ int dh_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* poin
         return algo == ENDO ? launch_pair<ENDO, true, true>(c, a) : launch_pair<WINDOWED, true, true>(c, a);
     }
     int group = normalize_group(c, n);
-    if (!table) {                                  // the prep + ladder route always defers; the fused kernels from two generations on (K = 2, 4, 8), except
-        const Route route = variable_route(c, algo, true, n, false);     // with a two-lane tail, whose kernels invert in place
-        group = route == ROUTE_SPLIT ? (group ? group : 1) : (route == ROUTE_FUSED ? group : 0);
-    }
+    // variable base: the fused kernels defer from two generations on (K = 2, 4, 8), except with a two-lane tail, whose kernels invert in place
+    if (!table && variable_route(c, n, false) != ROUTE_FUSED) group = 0;
     int rc = group ? ensure_proj(c, n) : FOURQ_OK;
     if (rc) return rc;
     a.proj = group ? c->proj : nullptr;
@@ -1180,8 +1123,8 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
     return s.bytes <= ZERO_COPY_BYTES && c->host_zero_copy ? pipe_zero_copy(p, s, st) : pipe_single_chunk(p, s, st);
 }
 
-// chunk of a host-pointer batch: whole generations of the kernels that will run it
-size_t pipe_chunk(const fourq_ctx* c, bool fused_route) { return fused_route ? c->lanes : c->lanes_w4; }
+// chunk of a variable-base host-pointer batch: whole generations of the fused kernels that will run it
+size_t pipe_chunk(const fourq_ctx* c) { return c->lanes; }
 // Kernel time per element of each route in nanoseconds, device-resident at 2^20 elements (profiles/r04_perf_probe.txt, tools/perf_probe.py).
 // They only size the chunks of the host-array calls (pipeline_plan.h): a kernel slower than its figure (constant-time mode, a slower box)
 // gets chunks smaller than it could have had, one faster by more than the plan's 15 % margin a short stall on the first chunks.
@@ -1193,16 +1136,13 @@ int mul_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* po
     CtxGuard g(c);
     PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points, nullptr, 160 } };
     PipeArray o[1] = { { nullptr, (char*)out, 160 } };
-    // variable-base MUL_endo: chunks of one fused generation overlap the copies better than rounds of the two-kernel route
-    // would (16 chunks instead of 4 at 2^20 elements: 6.7 ms against ~7.8)
-    const bool fused = points && (algo == ENDO || !takes_split_route(c, algo, false, n));
     // fixed base: the LDS ladders hold two waves per SIMD, so HALF of lanes_w4 is one generation of theirs -- the unit that sizes the first
     // chunk's copy in and the last chunk's copy out (cfg3's call: 160 B out per element, 21 MB instead of 42 behind the last kernel)
-    const size_t unit = points ? pipe_chunk(c, fused) : c->lanes_w4 / 2;
+    const size_t unit = points ? pipe_chunk(c) : c->lanes_w4 / 2;
     const double kt = points ? (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) : (algo == ENDO ? KT_ENDO_FIXED : KT_WIN_FIXED);
     return run_pipeline(c, in, points ? 2 : 1, o, 1, n, unit, PipeRoute{ (points ? PR_MUL_VAR : PR_MUL_FIX) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
         return mul_dev(c, algo, (const uint64_t*)di[0], points ? (const uint64_t*)di[1] : nullptr, table, (uint64_t*)dout[0], nullptr, m);
-    }, pipe_chunk(c, fused));
+    }, points ? pipe_chunk(c) : c->lanes_w4);
 }
 int dh_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points, const uint64_t* table, uint64_t* out,
             uint8_t* status, size_t n) {
@@ -1211,12 +1151,11 @@ int dh_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* poi
     CtxGuard g(c);
     PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points, nullptr, 64 } };
     PipeArray o[2] = { { nullptr, (char*)out, 64 }, { nullptr, (char*)status, 1 } };
-    const bool fused = !table && !takes_split_route(c, algo, true, n);
-    const size_t unit = table ? c->lanes_w4 / 2 : pipe_chunk(c, fused);
+    const size_t unit = table ? c->lanes_w4 / 2 : pipe_chunk(c);
     const double kt = table ? KT_DH_FIXED : (algo == ENDO ? KT_DH_VAR : KT_WIN_VAR + 0.3);
     return run_pipeline(c, in, 2, o, 2, n, unit, PipeRoute{ (table ? PR_DH_FIX : PR_DH_VAR) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
         return dh_dev(c, algo, (const uint64_t*)di[0], (const uint64_t*)di[1], table, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    }, pipe_chunk(c, fused), ensure_proj);
+    }, table ? c->lanes_w4 : pipe_chunk(c), ensure_proj);
 }
 
 int table_host(fourq_ctx* c, int algo, const uint64_t* p_r1, uint64_t* table) {
@@ -1311,15 +1250,6 @@ FQ_API int fourq_ctx_create(int device, fourq_ctx** out) {
         if (const char* env = route_env("FOURQ_BLOCKS_PER_CU")) { int v = atoi(env); if (v > 0 && v <= 8) occ = v; }
         c->lanes = (size_t)c->cus * occ * BLOCK;
         c->lanes_w4 = (size_t)c->cus * 4 * BLOCK;
-        // The two-kernel route (prep_kernel + ladder_kernel<PREBUILT>) for MUL_windowed / DH_* past one fused generation was worth
-        // 3-8 % through round 3; since the fused kernels' ladders run on the hand-scheduled bodies (ladder_asm.hip.h) the fused route is
-        // 3-6 % ahead at every size and config 4's step 4.7 % faster on it (profiles/r04_routes.txt).  The route stays reachable for
-        // experiments (FOURQ_SPLIT_MIN = smallest batch that takes it); mixed batches keep their own use of both kernels.
-        c->split_min = ~(size_t)0;
-        if (const char* env = route_env("FOURQ_SPLIT_MIN")) { long v = atol(env); if (v > 0) c->split_min = (size_t)v; }
-        if (const char* env = route_env("FOURQ_SPLIT_ALL")) c->split_all = atoi(env) != 0;
-        c->split_endo_min = 0;
-        if (const char* env = route_env("FOURQ_SPLIT_ENDO_MIN")) { long v = atol(env); if (v >= 0) c->split_endo_min = (size_t)v; }
         if (const char* env = route_env("FOURQ_HOST_BOUNCE")) c->host_bounce = atoi(env) != 0;
         if (const char* env = route_env("FOURQ_HOST_ZERO_COPY")) c->host_zero_copy = atoi(env) != 0;
         if (const char* env = route_env("FOURQ_PIPE_SLOTS")) { int v = atoi(env); if (v >= 2 && v <= PIPE_SLOTS_MAX) c->pipe_slots = v; }
@@ -1335,21 +1265,19 @@ FQ_API int fourq_ctx_create(int device, fourq_ctx** out) {
         c->quad_max = c->pair_max < c->lanes / 4 ? c->pair_max : c->lanes / 4;
         if (const char* env = route_env("FOURQ_QUAD_MAX")) { long v = atol(env); if (v >= 0 && (size_t)v <= c->quad_max) c->quad_max = (size_t)v; }
         if (const char* env = route_env("FOURQ_NORM_K")) { int v = atoi(env); if (v == 0 || v == 2 || v == 4 || v == 8) c->norm_k = v; }
-        c->split_chunk = c->lanes_w4;
-        if (const char* env = route_env("FOURQ_SPLIT_CHUNK")) { long v = atol(env); if (v >= BLOCK && (size_t)v <= c->lanes_w4) c->split_chunk = (size_t)v; }
-        size_t scratch_u32 = c->lanes * NDSlots::SLOT;                                   // fused kernels: N, D per resident lane
-        if (c->lanes_w4 * PrebuiltSlots::SLOT > scratch_u32) scratch_u32 = c->lanes_w4 * PrebuiltSlots::SLOT;   // two-kernel route: per element of a round
-        if ((size_t)COMB_POINTS * SLOT_U32 > scratch_u32) scratch_u32 = (size_t)COMB_POINTS * SLOT_U32;         // comb_table_kernel: whole entries
-        const size_t ct_tail_u32 = c->lanes * NDSlots::SLOT + (c->lanes / 8) * LimbSlots::SLOT;                 // constant-time mixed rounds: fused slots + the overflow ids' whole entries
-        if (ct_tail_u32 > scratch_u32) scratch_u32 = ct_tail_u32;
+        c->mixed_round = c->lanes_w4;
+        if (const char* env = route_env("FOURQ_MIXED_ROUND")) { long v = atol(env); if (v >= BLOCK && (size_t)v <= c->lanes_w4) c->mixed_round = (size_t)v; }
+        const size_t scratch_u32 = std::max({
+            c->lanes * NDSlots::SLOT,                                              // fused ladders (both modes), mixed_queue_kernel: N, D per resident lane; grids of at most lanes / BLOCK blocks
+            c->lanes * NDSlots::SLOT + (c->lanes / 8) * LimbSlots::SLOT,           // constant-time mixed rounds: behind the fused slots, whole entries of at most lanes / 8 overflow ids (over_scratch)
+            (size_t)COMB_POINTS * SLOT_U32,                                        // comb_table_kernel: whole entries + two parked points per point of the comb
+            (size_t)SLOT_U32 });                                                   // table_build_kernel: one such slot
         if (hipMalloc(&c->scratch, scratch_u32 * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
         if (hipMalloc(&c->table_limbs, 8 * R2_LIMBS * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
-        if (hipMalloc(&c->table_slots, 8 * R2_LIMBS * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
         if (hipMalloc(&c->table_packed, FOURQ_TABLE_WORDS * 8) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
         if (hipMalloc(&c->part_counter, 8 * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }   // n_var, n_fix, queue head, -, fused, overflow
         if (hipMalloc(&c->part_fix, c->lanes_w4 * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
         if (hipMalloc(&c->part_list, c->lanes_w4 * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
-        if (hipMalloc(&c->part_slot, c->lanes_w4 * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
         if (hipMalloc(&c->comb_limbs, COMB_POINTS * COMB_ENTRY_U32 * sizeof(u32)) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
         if (hipMalloc(&c->comb_packed, FOURQ_COMB_WORDS * 8) != hipSuccess) { rc = FOURQ_ERR_NOMEM; break; }
     } while (0);
@@ -1363,8 +1291,8 @@ FQ_API int fourq_ctx_destroy(fourq_ctx* c) {
     { CtxGuard last(c); }                      // a call still running on another thread finishes first; the caller must not start new ones
     DeviceGuard g(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    for (void* p : { (void*)c->scratch, (void*)c->proj, (void*)c->table_limbs, (void*)c->table_slots, (void*)c->table_packed, (void*)c->part_counter, (void*)c->part_list,
-                     (void*)c->part_slot, (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, c->stage, (void*)c->work, (void*)c->pipe_dev })
+    for (void* p : { (void*)c->scratch, (void*)c->proj, (void*)c->table_limbs, (void*)c->table_packed, (void*)c->part_counter, (void*)c->part_list,
+                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, c->stage, (void*)c->work, (void*)c->pipe_dev })
         if (p) (void)hipFree(p);
     if (c->pipe_pin) (void)hipHostFree(c->pipe_pin);
     if (c->zero_copy) (void)hipHostFree(c->zero_copy);
@@ -1486,22 +1414,20 @@ FQ_API int fourq_mul_endo_mixed_batch_dev(fourq_ctx* c, const uint64_t* s, const
         a.scalars = s; a.points = p; a.out = o; a.n = (u32)n; a.flags = flags;
         return launch_pair_mixed(c, a);
     }
-    // Rounds of up to split_chunk elements.  Per round: compact the ids of both kinds (counts stay on the device), then -- the default --
-    // ONE persistent kernel whose waves pull 64-element work items off a device-side queue (mixed_queue_kernel), or, behind the test hook
-    // FOURQ_MIXED_QUEUE=0, round 2's route: the variable-base ids' tables built into scratch slots (prep_kernel over the compacted list)
-    // and ONE ladder launch over all elements of the round in their natural order, each lane reading its table through a pointer -- its
-    // own slot or the shared fixed-base table -- so that fixed and variable elements share wavefronts without divergence.
+    // Rounds of up to mixed_round elements.  Per round: compact the ids of both kinds (counts stay on the device), then ONE persistent
+    // kernel whose waves pull 64-element work items off a device-side queue (mixed_queue_kernel) or, in constant-time mode past one
+    // generation (or with FOURQ_MIXED_QUEUE=0), the fused kernel over the variable-base ids + mixed_ct_tail_kernel.
     const size_t per_block = (size_t)BLOCK * PART_PER_LANE;
-    for (size_t off = 0; off < n; off += c->split_chunk) {
-        const u32 m = (u32)(n - off < c->split_chunk ? n - off : c->split_chunk);
-        const bool queue = c->mixed_queue >= 0 ? c->mixed_queue != 0 : mixed_queue_default(c, m);
+    for (size_t off = 0; off < n; off += c->mixed_round) {
+        const u32 m = (u32)(n - off < c->mixed_round ? n - off : c->mixed_round);
+        const bool queue = c->ct && c->mixed_queue >= 0 ? c->mixed_queue != 0 : mixed_queue_default(c, m);
         HIP_TRY(c, hipMemsetAsync(c->part_counter, 0, 8 * sizeof(u32), c->stream));
         hipLaunchKernelGGL(partition_kernel, dim3((unsigned)((m + per_block - 1) / per_block)), dim3(BLOCK), 0, c->stream,
-                           flags + off, m, (u32)off, c->part_list, c->part_slot, c->part_counter, (c->ct || queue) ? c->part_fix : nullptr);
+                           flags + off, m, (u32)off, c->part_list, c->part_counter, c->part_fix);
         HIP_TRY(c, hipGetLastError());
         LadderArgs a = {};
         a.scalars = s; a.points = p; a.out = o; a.n = m;
-        a.scratch = c->scratch; a.table = c->table_limbs; a.table_slots = c->table_slots;
+        a.scratch = c->scratch; a.table = c->table_limbs;
         if (queue) {
             // BASELINE config 5's mechanism: one persistent kernel, one block per CU, every wave pulling 64-element work items
             // (variable-base first) from a device-side queue until it is empty (kernels.hip.h, mixed_queue_kernel)
@@ -1515,30 +1441,21 @@ FQ_API int fourq_mul_endo_mixed_batch_dev(fourq_ctx* c, const uint64_t* s, const
             }
             continue;
         }
-        if (c->ct) {
-            // constant-time selection: which elements are fixed-base is public, the digits are not.  The variable-base
-            // ids go through the fused kernel (table in registers), the fixed-base ids through the LDS kernel; both
-            // read their element counts on the device.
-            // A remainder of at most lanes / 8 ids past whole generations of the fused kernel is cut off on the device and
-            // runs with the fixed-base elements (kernels.hip.h, mixed_ct_tail_kernel): config 5's 65 550 variable-base ids
-            // are one fused generation + 14 riders, not two generations.
-            const u32 limit = (u32)(c->lanes / 8);
-            u32* over_scratch = c->scratch + c->lanes * NDSlots::SLOT;           // behind the fused kernels' per-lane slots
-            HIPRC_TRY(c, ct_launch_split_counts(c->stream, c->part_counter, (u32)c->lanes, limit));
-            LadderArgs av = a;
-            av.index = c->part_list; av.n_dev = c->part_counter + 4;
-            if ((rc = launch_ladder<ENDO, FUSED, false>(c, av))) return rc;
-            const size_t tail_blocks = ((size_t)m + BLOCK - 1) / BLOCK, tail_max = c->lanes_w4 / BLOCK;
-            HIPRC_TRY(c, ct_launch_mixed_tail((limit + BLOCK - 1) / BLOCK, (unsigned)(tail_blocks < tail_max ? tail_blocks : tail_max), c->stream, a,
-                                              c->part_fix, c->part_list, c->part_counter, over_scratch, (u32)c->lanes, limit));
-            continue;
-        }
-        LadderArgs ap = a;
-        ap.index = c->part_list; ap.n_dev = c->part_counter;
-        HIPRC_TRY(c, chain_launch_prep(ENDO, false, (m + BLOCK - 1) / BLOCK, c->stream, ap));
-        a.base = (u32)off; a.slot_of = c->part_slot;
-        rc = launch_ladder<ENDO, PREBUILT, false>(c, a);
-        if (rc) return rc;
+        // Constant-time mode only: which elements are fixed-base is public, the digits are not.  The variable-base
+        // ids go through the fused kernel (table in registers), the fixed-base ids through the tail kernel; both
+        // read their element counts on the device.
+        // A remainder of at most lanes / 8 ids past whole generations of the fused kernel is cut off on the device and
+        // runs with the fixed-base elements (kernels.hip.h, mixed_ct_tail_kernel): config 5's 65 550 variable-base ids
+        // are one fused generation + 14 riders, not two generations.
+        const u32 limit = (u32)(c->lanes / 8);
+        u32* over_scratch = c->scratch + c->lanes * NDSlots::SLOT;           // behind the fused kernels' per-lane slots
+        HIPRC_TRY(c, ct_launch_split_counts(c->stream, c->part_counter, (u32)c->lanes, limit));
+        LadderArgs av = a;
+        av.index = c->part_list; av.n_dev = c->part_counter + 4;
+        if ((rc = launch_ladder<ENDO, FUSED, false>(c, av))) return rc;
+        const size_t tail_blocks = ((size_t)m + BLOCK - 1) / BLOCK, tail_max = c->lanes_w4 / BLOCK;
+        HIPRC_TRY(c, ct_launch_mixed_tail((limit + BLOCK - 1) / BLOCK, (unsigned)(tail_blocks < tail_max ? tail_blocks : tail_max), c->stream, a,
+                                          c->part_fix, c->part_list, c->part_counter, over_scratch, (u32)c->lanes, limit));
     }
     return FOURQ_OK;
 }
@@ -1551,10 +1468,10 @@ FQ_API int fourq_mul_endo_mixed_batch(fourq_ctx* c, const uint64_t* s, const uin
     PipeArray out[1] = { { nullptr, (char*)o, 160 } };
     // one pass of the work-queue kernel's 4 x CUs waves over 64-element items is `lanes` elements: the unit that lets the copies of a
     // config-5-sized call (2 x lanes) overlap its kernels; raw R1 in and out keeps the chunks at that size (pipeline_plan.h)
-    const size_t unit = c->split_chunk < c->lanes ? c->split_chunk : c->lanes;
+    const size_t unit = c->mixed_round < c->lanes ? c->mixed_round : c->lanes;
     return run_pipeline(c, in, 3, out, 1, n, unit, PipeRoute{ PR_MIXED, KT_ENDO_VAR }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_mul_endo_mixed_batch_dev(c, (const uint64_t*)di[0], (const uint64_t*)di[1], (const uint8_t*)di[2], table, (uint64_t*)dout[0], m);
-    }, c->split_chunk);
+    }, c->mixed_round);
 }
 
 FQ_API int fourq_dh_endo_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) { return dh_host(c, ENDO, s, p, t, o, st, n); }
@@ -1724,12 +1641,11 @@ static int dh_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const 
     CtxGuard g(c);
     PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)keys32, nullptr, 32 } };
     PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
-    const bool fused = !table && !takes_split_route(c, algo, true, n);
-    const size_t unit = table ? c->lanes_w4 / 2 : pipe_chunk(c, fused);
+    const size_t unit = table ? c->lanes_w4 / 2 : pipe_chunk(c);
     const double kt = (table ? KT_DH_FIXED : (algo == ENDO ? KT_DH_VAR : KT_WIN_VAR + 0.3)) + KT_CODEC;
     return run_pipeline(c, in, 2, o, 2, n, unit, PipeRoute{ (table ? PR_DHB_FIX : PR_DHB_VAR) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
         return dh_bytes_dev(c, algo, (const uint64_t*)di[0], (const uint8_t*)di[1], table, (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, pipe_chunk(c, fused), reserve_dh_bytes);
+    }, table ? c->lanes_w4 : pipe_chunk(c), reserve_dh_bytes);
 }
 // ---- MUL_* with affine / encoded I/O: R1toAffine(MUL_<algo>(m, AffineToR1(P))) and encode(.) of it --------------------------
 // 160 (96) bytes per operation across the ABI instead of the raw-R1 form's 352: the host-array calls are bound by the link, not by the
@@ -1748,15 +1664,15 @@ static int launch_lower(fourq_ctx* c, bool enc, const uint64_t* r1, u32 stride, 
 }
 // Does the whole batch run on the fused one-lane-per-element kernels?  Only those take the affine-in / (X, Y, Z)-out flags (LadderArgs::io):
 // then the lane lifts its own point and leaves the three coordinates R1toAffine reads -- no lift kernel, no R1 rows.  Batches with a
-// two-lane tail or on the two-kernel route keep the separate lift and full R1 rows (FOURQ_FUSED_IO=0, a test hook, forces that everywhere).
-static bool fused_io(const fourq_ctx* c, int algo, size_t n) { return c->fused_io && variable_route(c, algo, false, n, false) == ROUTE_FUSED; }
+// two-lane tail keep the separate lift and full R1 rows (FOURQ_FUSED_IO=0, a test hook, forces that everywhere).
+static bool fused_io(const fourq_ctx* c, size_t n) { return c->fused_io && variable_route(c, n, false) == ROUTE_FUSED; }
 // The ladder half that MUL_* with affine / encoded I/O and [k]B + [l]P share: prepares the ladder's input rows and runs MUL_<algo> into rows_out.
 // Where the whole batch runs on the fused kernels the lanes lift their own points and leave (X, Y, Z): encoded points are decoded to affine rows,
 // affine ones read where they lie, and *stride, the words per row of rows_out, is 12; otherwise decode + lift / lift to full R1 rows, and 20.
 static int mul_rows_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const void* points, bool encoded, uint64_t* rows_in, uint64_t* rows_out,
                         uint8_t* st_decode, size_t n, u32* stride) {
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    const bool fused = fused_io(c, algo, n);
+    const bool fused = fused_io(c, n);
     const uint64_t* ladder_in = rows_in;
     if (encoded) {
         if (fused) hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)points, rows_in, st_decode, (u32)n);
@@ -1789,7 +1705,7 @@ static int mul_affine_host(fourq_ctx* c, int algo, const uint64_t* scalars, cons
     CtxGuard g(c);
     PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points_affine, nullptr, 64 } };
     PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
-    return run_pipeline(c, in, 2, o, 1, n, pipe_chunk(c, true), PipeRoute{ PR_AFF + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, 2, o, 1, n, pipe_chunk(c), PipeRoute{ PR_AFF + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
         return mul_affine_dev(c, algo, (const uint64_t*)di[0], (const uint64_t*)di[1], (uint64_t*)dout[0], m);
     }, 0, reserve_mul_rows);
 }
@@ -1812,7 +1728,7 @@ static int mul_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const
     CtxGuard g(c);
     PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points32, nullptr, 32 } };
     PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 2, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_BYTES + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER + KT_CODEC }, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, 2, o, 2, n, pipe_chunk(c), PipeRoute{ PR_BYTES + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER + KT_CODEC }, [&](char* const* di, char* const* dout, size_t m) {
         return mul_bytes_dev(c, algo, (const uint64_t*)di[0], (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
     }, 0, reserve_mul_rows);
 }
@@ -1934,7 +1850,7 @@ FQ_API int fourq_double_mul_affine_batch(fourq_ctx* c, const uint64_t* k, const 
     if (int rc = stage_comb(c, comb)) return rc;                            // compared once, not once per chunk
     PipeArray in[3] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points_affine, nullptr, 64 } };
     PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
-    return run_pipeline(c, in, 3, o, 1, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_AFF, KT_DOUBLE }, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, 3, o, 1, n, pipe_chunk(c), PipeRoute{ PR_DOUBLE_AFF, KT_DOUBLE }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_double_mul_affine_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint64_t*)di[2], (uint64_t*)dout[0], m);
     }, 0, reserve_double_mul);
 }
@@ -1945,7 +1861,7 @@ FQ_API int fourq_double_mul_bytes_batch(fourq_ctx* c, const uint64_t* k, const u
     if (int rc = stage_comb(c, comb)) return rc;
     PipeArray in[3] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points32, nullptr, 32 } };
     PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 3, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_BYTES, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, 3, o, 2, n, pipe_chunk(c), PipeRoute{ PR_DOUBLE_BYTES, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_double_mul_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
     }, 0, reserve_double_mul);
 }
@@ -1957,7 +1873,7 @@ FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint6
     if (int rc = stage_comb(c, comb)) return rc;
     PipeArray in[4] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points32, nullptr, 32 }, { (const char*)expect32, nullptr, 32 } };
     PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 4, o, 2, n, pipe_chunk(c, true), PipeRoute{ PR_DOUBLE_VERIFY, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, 4, o, 2, n, pipe_chunk(c), PipeRoute{ PR_DOUBLE_VERIFY, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_verify_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (const uint8_t*)di[3], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
     }, 0, reserve_double_mul);
 }
@@ -2156,7 +2072,7 @@ FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint6
     int n_in = 2;
     const MsgArrays ma(in, &n_in, msgs, stride, lens);
     PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c, true), stride), PipeRoute{ PR_SIG_VERIFY, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_SIG_VERIFY, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_sig_verify_batch_dev(c, (const uint8_t*)di[0], nullptr, ma.msgs(di), stride, ma.lens(di), msg_len, (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
     }, 0, reserve_double_mul);
 }
@@ -2213,7 +2129,7 @@ static int h2c_host(fourq_ctx* c, int what, const uint8_t* dst, size_t dst_len, 
     PipeArray o[1] = { { nullptr, (char*)out, what == 0 ? (size_t)32 * count : what == 1 ? (size_t)32 : (size_t)64 } };
     const double kt = h2c_kt_hash(stride, dst_len, count) + (what == 0 ? 0.0 : count * KT_ELL2 + KT_LIFT_LOWER);
     const PipeRoute route{ what == 0 ? PR_H2F : (what == 1 ? PR_H2C : PR_H2C_AFFINE) + mode, kt };
-    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(what == 0 ? 4 * c->lanes_w4 : pipe_chunk(c, true), stride), route, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(what == 0 ? 4 * c->lanes_w4 : pipe_chunk(c), stride), route, [&](char* const* di, char* const* dout, size_t m) {
         if (what == 0) return fourq_hash_to_field_batch_dev(c, dst, dst_len, mode, ma.msgs(di), stride, ma.lens(di), msg_len, (uint64_t*)dout[0], m);
         return hash_to_curve_dev(c, dst, dst_len, mode, ma.msgs(di), stride, ma.lens(di), msg_len, what == 1 ? H2C_OUT_BYTES : H2C_OUT_AFFINE, dout[0], m);
     }, 0, what == 0 ? nullptr : reserve_h2c);
@@ -2227,7 +2143,7 @@ FQ_API int fourq_map_to_curve_batch(fourq_ctx* c, const uint64_t* u, uint64_t* o
     CtxGuard g(c);
     PipeArray in[1] = { { (const char*)u, nullptr, 32 } };
     PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
-    return run_pipeline(c, in, 1, o, 1, n, pipe_chunk(c, true), PipeRoute{ PR_H2C_MAP, KT_ELL2 + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
+    return run_pipeline(c, in, 1, o, 1, n, pipe_chunk(c), PipeRoute{ PR_H2C_MAP, KT_ELL2 + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
         return fourq_map_to_curve_batch_dev(c, (const uint64_t*)di[0], (uint64_t*)dout[0], m);
     });
 }

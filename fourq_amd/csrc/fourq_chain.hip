@@ -1,6 +1,5 @@
 // Second translation unit of libfourq_amd.so: the kernels that profit from chained carries (FQ_CHAIN=1, see
-// kernels.hip.h): fixed-base ladders (table in LDS), the two-kernel route for large variable-base batches
-// (prep_kernel + ladder_kernel<PREBUILT>), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
+// kernels.hip.h): fixed-base ladders (table in LDS), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
 // translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P,
 // msm.hip.h the one that folds the ladder's rows of a group into one.
 #ifndef FQ_CHAIN
@@ -13,33 +12,18 @@
 namespace fq {
 
 namespace {
-template <int ALGO, int SRC, bool DH, bool DEFER> int launch(unsigned grid, hipStream_t stream, const LadderArgs& a) {
-    hipLaunchKernelGGL((ladder_kernel<ALGO, SRC, DH, DEFER>), dim3(grid), dim3(BLOCK), 0, stream, a);
+template <int ALGO, bool DH, bool DEFER> int launch(unsigned grid, hipStream_t stream, const LadderArgs& a) {
+    hipLaunchKernelGGL((ladder_kernel<ALGO, LDS, DH, DEFER>), dim3(grid), dim3(BLOCK), 0, stream, a);
     return (int)hipGetLastError();
 }
-template <int ALGO> int launch_algo(int src, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a) {
-    if (src == LDS) {
-        if (!dh) return launch<ALGO, LDS, false, false>(grid, stream, a);
-        return a.proj ? launch<ALGO, LDS, true, true>(grid, stream, a) : launch<ALGO, LDS, true, false>(grid, stream, a);
-    }
-    if (!dh) return launch<ALGO, PREBUILT, false, false>(grid, stream, a);
-    if (!a.proj) return (int)hipErrorInvalidValue;           // the PREBUILT DH ladder always defers normalisation
-    return launch<ALGO, PREBUILT, true, true>(grid, stream, a);
+template <int ALGO> int launch_algo(bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a) {
+    if (!dh) return launch<ALGO, false, false>(grid, stream, a);
+    return a.proj ? launch<ALGO, true, true>(grid, stream, a) : launch<ALGO, true, false>(grid, stream, a);
 }
 }  // namespace
 
-int chain_launch_ladder(int algo, int src, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a) {
-    return algo == ENDO ? launch_algo<ENDO>(src, dh, grid, stream, a) : launch_algo<WINDOWED>(src, dh, grid, stream, a);
-}
-int chain_launch_prep(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a) {
-    if (algo == ENDO) {
-        if (dh) hipLaunchKernelGGL((prep_kernel<ENDO, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((prep_kernel<ENDO, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
-    } else {
-        if (dh) hipLaunchKernelGGL((prep_kernel<WINDOWED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((prep_kernel<WINDOWED, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
-    }
-    return (int)hipGetLastError();
+int chain_launch_ladder(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a) {
+    return algo == ENDO ? launch_algo<ENDO>(dh, grid, stream, a) : launch_algo<WINDOWED>(dh, grid, stream, a);
 }
 // The comb's table needs more dynamic LDS than the 64 KB a kernel gets by default: raised once per device, at context creation
 // (a launch then only enqueues, so the _dev entry points stay capturable into a graph).

@@ -1,6 +1,6 @@
-// Fourth translation unit of libfourq_amd.so: the fixed-base (LDS) ladders and the comb with CONSTANT-TIME table
-// selection (FOURQ_CT_SELECT / fourq_ctx_set_ct_select).  Same build flavour as fourq_chain.hip (FQ_CHAIN=1): every
-// entry of the shared table is read by every lane at every step (same addresses across the wave: LDS broadcasts).
+// Fourth translation unit of libfourq_amd.so: the fixed-base (LDS) ladders, the comb and the tail of a mixed round (prep_kernel +
+// mixed_ct_tail_kernel) with CONSTANT-TIME table selection (FOURQ_CT_SELECT / fourq_ctx_set_ct_select).  Same build flavour as fourq_chain.hip
+// (FQ_CHAIN=1): every entry of the shared table is read by every lane at every step (same addresses across the wave: LDS broadcasts).
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
 #endif
@@ -37,7 +37,7 @@ int ct_launch_mixed_tail(unsigned prep_grid, unsigned tail_grid, hipStream_t str
     (void)lanes; (void)limit;
     LadderArgs ap = a;
     ap.index = var_list; ap.base = 0; ap.base_dev = counts + 4; ap.n_dev = counts + 5; ap.scratch = over_scratch;
-    hipLaunchKernelGGL((prep_kernel<ENDO, false, LimbSlots>), dim3(prep_grid), dim3(BLOCK), 0, stream, ap);
+    hipLaunchKernelGGL(prep_kernel<0>, dim3(prep_grid), dim3(BLOCK), 0, stream, ap);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(mixed_ct_tail_kernel<0>, dim3(tail_grid), dim3(BLOCK), 0, stream, a, fix_list, var_list, counts, over_scratch);

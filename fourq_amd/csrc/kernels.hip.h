@@ -2,9 +2,9 @@
 // built from them.  Included by four translation units; the first two differ only in FQ_CHAIN (fp127.hip.h), the last
 // two are their builds with constant-time table selection (ladder_kernel<..., CT = true>):
 //   fourq_amd.hip       FQ_CHAIN=0  fused variable-base kernels (table + ladder in one launch), primitives, C ABI
-//   fourq_chain.hip     FQ_CHAIN=1  fixed-base (LDS), two-kernel route (prep + PREBUILT ladder), comb
+//   fourq_chain.hip     FQ_CHAIN=1  fixed-base (LDS) ladders, comb, batched normalisation
 //   fourq_ct_fused.hip  FQ_CHAIN=0  fused kernels, the lane's table scanned in registers
-//   fourq_ct_chain.hip  FQ_CHAIN=1  fixed-base (LDS) ladders and comb, the whole table read at every step
+//   fourq_ct_chain.hip  FQ_CHAIN=1  fixed-base (LDS) ladders and comb, the whole table read at every step; the mixed-batch tail
 // Measured on MI355X (2^20 elements): chaining each column's carry into the next column's first multiply-add
 // gains 4-10 % for every kernel of the second group and costs the fused kernels 12-15 % when applied wholesale;
 // the fused kernels therefore use it only in their ladders, with preloaded table entries (see "the ladders").
@@ -24,12 +24,7 @@ namespace fq {
 
 constexpr int BLOCK = 256;
 constexpr int SLOT_U32 = LimbSlots::SLOT;   // a whole-entry scratch slot (table_build_kernel, comb_table_kernel): 8 x 48 dwords + two parked points
-// Layout of the slots that prep_kernel fills and ladder_kernel<PREBUILT> gathers from: 2^18 elements in flight make
-// 486 MB of 192-byte entries, past the 256 MiB Infinity Cache, and the DH ladder of BASELINE config 4 then pulled
-// 4 TB/s from HBM; packed 128-byte entries cut that by a third and let a round's tables stay in the cache.
-// (The fused kernels keep ready-to-use limbs: N, D in dense NDSlots -- 2^16 slots = 42 MB, inside the Infinity Cache --
-// and E, F in LDS, below.)
-typedef PackedSlots PrebuiltSlots;
+// (The fused kernels keep N, D in dense NDSlots -- 2^16 slots = 42 MB, inside the Infinity Cache -- and E, F in LDS, below.)
 constexpr int PROJ_PLANES = 8;            // deferred normalisation: the 30 working limbs of (X, Y, Z) in eight uint4 planes
 constexpr int LDS_ENTRY_U32 = 52;      // 48 + 4 pad: entry k starts at bank 52k mod 64 -> eight entries never share a b128 bank group
 
@@ -95,11 +90,9 @@ template <typename L, typename EF> FQ_DEV R2 load_entry_r2(const u32* slot, int 
 
 enum Algo { ENDO = 0, WINDOWED = 1 };
 // where the ladder finds its table:
-//   FUSED     built by the same lane into its scratch slot just before the ladder (small batches: one launch)
+//   FUSED     built by the same lane into its scratch slot just before the ladder (variable base: one launch)
 //   LDS       one shared table staged into LDS (fixed base)
-//   PREBUILT  built per element by prep_kernel into scratch slot `pos` (large batches: the ladder kernel then
-//             fits 128 VGPRs and runs 4 waves per SIMD instead of 1)
-enum Src { FUSED = 0, LDS = 1, PREBUILT = 2 };
+enum Src { FUSED = 0, LDS = 1 };
 
 struct LadderArgs {
     const u64* scalars;    // n x 4
@@ -107,16 +100,17 @@ struct LadderArgs {
     u64* out;              // n x 20 (R1) or n x 8 (affine, DH)
     uint8_t* status;       // DH only
     const uint8_t* flags;  // mixed batches on the two- and four-lane kernels: flags[i] != 0 = variable base (points[i]), 0 = the fixed-base table
-    const u32* index;      // optional: element ids to process (prep_kernel over the variable-base ids of a mixed batch); NULL = identity
+    const u32* index;      // optional: element ids to process (the variable-base ids of a mixed batch); NULL = identity
     u32 base;              // first position of this launch (chunked large batches)
     const u32* base_dev;   // optional: added to `base`, read on the device (the overflow part of a list whose split is decided on the device)
     const u32* n_dev;      // optional: element count read on the device (mixed batches: no host round trip)
-    const u32* slot_of;    // PREBUILT, optional (mixed batches): per position, the scratch slot of its table or ~0 = `table`
+    const void* pad_n_dev; // unused padding, as pad_table below: the kernels' code was scheduled, and measured, with the fields behind these two at
+                           // their present kernel-argument offsets; without the slots hipcc schedules mixed_queue_kernel and the LDS ladders differently
     const u32* table;      // fixed base: 8 x 48 working limbs (global), staged to LDS
-    const u32* table_slots;// the same table in the PrebuiltSlots layout (mixed batches: read through a per-lane pointer)
-    u32* scratch;          // variable base: NDSlots::SLOT dwords per resident lane (FUSED) or PrebuiltSlots::SLOT per position of the chunk (PREBUILT)
+    const void* pad_table; // unused padding
+    u32* scratch;          // variable base: NDSlots::SLOT dwords per resident lane (prep_kernel: LimbSlots::SLOT per overflow id)
     uint4* proj;           // DH, optional: PROJ_PLANES x proj_stride; non-NULL selects the kernels that leave (X, Y, Z)
-                           // there for normalize_kernel (always the case on the PREBUILT route)
+                           // there for normalize_kernel
     u32 proj_stride;       // elements per plane
     u32 n;
     u32 io;                // fused MUL_* kernels (one lane per element) only -- LADDER_IO_AFFINE_IN: `points` is n x 8 affine words and the lane lifts
@@ -272,27 +266,11 @@ template <typename L = LimbSlots> FQ_DEV void build_table_endo_pipelined(const R
 // step; per-kernel A/Bs in DESIGN.md section 9), in one of two forms:
 //   CH = 3          the step as hand-scheduled asm bodies (ladder_asm.hip.h, tools/asmgen/gen_ladder_step.py), the entry in registers,
 //                   requested a doubling ahead.  The fused kernels, whose lone wave per SIMD pays for every issue slot
-//                   (profiles/r04_ladder_step.txt); the fixed-base ladders with the table in LDS and the two-kernel route's MUL ladder
-//                   (256 VGPRs, two waves per SIMD instead of four; mixed batches +3.7 %); the constant-time ladders, where the
-//                   whole-table scan (select trees, compiler code) produces the entry and the bodies consume it.
-//   CH = LADDER_CH  hipcc's step on the same limbs, the entry read inside the addition: the two-kernel route's DH ladder, whose gathers
-//                   run at the memory system's pace -- it loses 2.5-4 % with two wave slots and keeps four -- and the comb.
+//                   (profiles/r04_ladder_step.txt); the fixed-base ladders with the table in LDS (256 VGPRs, two waves per SIMD);
+//                   the constant-time ladders, where the whole-table scan (select trees, compiler code) produces the entry and
+//                   the bodies consume it.
+//   CH = LADDER_CH  hipcc's step on the same limbs, the entry read inside the addition: the comb.
 constexpr int LADDER_CH = 2;
-// TOUCH: the two-kernel route's ladder reads a lane's table entry (one 128-byte line of its scratch slot) inside the
-// addition, with no registers to spare for issuing the eight loads a doubling ahead (128-VGPR budget).  A one-dword load of the
-// line at the top of the step, result unused, starts the HBM / Infinity-Cache fetch early: the real loads then hit L2.
-// Same-box A/B (profiles/r02_split_route.txt): cfg5 +2.2 % (two waves per SIMD), cfg4 +0..1 % (four waves hide the latency themselves).
-// The touch is an ordinary load that hipcc sees: it allocates the landing register and places the s_waitcnt that covers it
-// itself (round 2 issued the load from inline asm, where a spill of the untracked register would have corrupted a live limb).
-// touch_done() after the addition is its only consumer; `after` is a limb of the sum's X, which depends on all four coordinates
-// of the entry, so the consumer -- and with it the wait -- cannot move up in front of the addition's own loads, and the
-// scheduling barrier behind the load keeps the load itself at the top of the step.
-template <typename TP> FQ_DEV u32 touch_line(const TP* p) {
-    const u32 landing = *reinterpret_cast<const u32*>(p);
-    __builtin_amdgcn_sched_barrier(0);
-    return landing;
-}
-FQ_DEV void touch_done(u32 landing, u32& after) { asm volatile("" : "+v"(after) : "v"(landing)); }
 // a ladder on signed limbs (CH >= 2) hands its result back with non-negative limbs
 template <int CH> FQ_DEV R1 ladder_result(const R1& Q) {
     if constexpr (CH >= 2) {
@@ -309,7 +287,7 @@ FQ_DEV R1 ladder_start(const Proj<1, 1, 1>& q4) {
     R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
     return Q;
 }
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, bool TOUCH = false, typename TP> FQ_DEV R1 ladder_endo(const EndoDigits& e, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:436-442
+template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, typename TP> FQ_DEV R1 ladder_endo(const EndoDigits& e, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:436-442
     Proj<1, 1, 1> q4 = start_table<L>(tbl + (e.top & 7) * stride, 0u);        // s[64] = 1: the entry itself
     if constexpr (EF::ON) q4.Z = ef.get(e.top & 7, 0);
     R1 Q = ladder_start(q4);
@@ -324,11 +302,8 @@ template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF 
             dblt_asm(Q.X, Q.Y, Q.Z, T);
             add_asm(Q, T, t, neg);
         } else {
-            u32 landing = 0;
-            if (TOUCH) landing = touch_line(entry);
             Q = dbl<CH>(Q.X, Q.Y, Q.Z);
             Q = add_table<CH, L>(Q, entry, endo_neg_mask(e, i));
-            if (TOUCH) touch_done(landing, Q.X.re.l[0]);
         }
     }
     return ladder_result<CH>(Q);
@@ -384,7 +359,7 @@ template <int B> FQ_DEV void store_fe2_signed(u64* w, const Fe2<B>& a) {
 FQ_DEV void store_r1_signed(u64* w, const R1& q) {
     store_fe2_signed(w, q.X); store_fe2_signed(w + 4, q.Y); store_fe2_signed(w + 8, q.Z); store_fe2_signed(w + 12, q.Ta); store_fe2_signed(w + 16, q.Tb);
 }
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, bool TOUCH = false, typename TP> FQ_DEV R1 ladder_windowed(const WinScalar& w, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:228-235
+template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, typename TP> FQ_DEV R1 ladder_windowed(const WinScalar& w, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:228-235
     u32 code = win_top_code(w);
     Proj<1, 1, 1> q4 = start_table<L>(tbl + (code & 7) * stride, (code >> 3) - 1u);
     if constexpr (EF::ON) q4.Z = ef.get(code & 7, 0);
@@ -402,12 +377,9 @@ template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF 
             dblt_asm(Q.X, Q.Y, Q.Z, T);
             add_asm(Q, T, t, neg);
         } else {
-            u32 landing = 0;
-            if (TOUCH) landing = touch_line(entry);
 #pragma unroll 1
             for (int k = 0; k < 4; k++) Q = dbl<CH>(Q.X, Q.Y, Q.Z);
             Q = add_table<CH, L>(Q, entry, neg);
-            if (TOUCH) touch_done(landing, Q.X.re.l[0]);
         }
     }
     return ladder_result<CH>(Q);
@@ -517,45 +489,21 @@ FQ_DEV void store_row(u64* row, const u64 o[20]) {
 
 namespace {   // kernels: one private copy per translation unit (their code objects differ by FQ_CHAIN)
 
-// Large variable-base batches, first half: per element, (DH: membership test, cofactor clearing,) table
-// construction into scratch slot `pos`.  Kept apart from the ladder so that the endomorphisms' register
-// appetite (256 VGPRs) does not set the ladder's occupancy.
-template <int ALGO, bool DH, typename SL = PrebuiltSlots>
-__global__ __launch_bounds__(BLOCK) void prep_kernel(LadderArgs a) {
-    const u32 pos = blockIdx.x * BLOCK + threadIdx.x;
-    if (pos >= (a.n_dev ? *a.n_dev : a.n)) return;
-    const u32 first = a.base + (a.base_dev ? *a.base_dev : 0u);
-    const u32 id = a.index ? a.index[first + pos] : first + pos;
-    R1 P;
-    if (DH) {
-        Fe2<1> x = load_fe2(a.points + 8 * (size_t)id), y = load_fe2(a.points + 8 * (size_t)id + 4);
-        a.status[id] = point_on_curve(x, y) ? FOURQ_DH_OK : FOURQ_DH_NOT_ON_CURVE;
-        P = clear_cofactor_392(x, y);
-    } else {
-        P = load_r1(a.points + 20 * (size_t)id);
-    }
-    u32* slot = a.scratch + (size_t)pos * SL::SLOT;
-    if (ALGO == ENDO) build_table_endo_pipelined<SL>(P, slot);
-    else build_table_windowed<SL>(P, slot);
-}
-
 // ALGO: ENDO / WINDOWED.  SRC: where the table is.  DH: affine in, cofactor clearing, affine out + status.
 // DEFER (DH only): leave (X, Y, Z) in a.proj for normalize_kernel instead of inverting Z here.
 // CT: constant-time table selection (every entry read at every step); FUSED keeps N, D of the lane's table in registers and
-// scans E, F in the lane's LDS rows, LDS scans the shared table where it lies (PREBUILT is not taken in this mode).
-constexpr int ladder_waves(int src, bool dh, bool ct) {       // wave slots per SIMD a ladder kernel is built for
+// scans E, F in the lane's LDS rows, LDS scans the shared table where it lies.
+constexpr int ladder_waves(int src) {                          // wave slots per SIMD a ladder kernel is built for
     if (src == FUSED) return 1;                                // the endomorphisms' 256 VGPRs and the CU's whole LDS
-    if (src == LDS || (src == PREBUILT && !dh && !ct)) return 2;   // the asm bodies: 256 VGPRs
-    return 4;                                                  // the two-kernel DH ladder: hipcc's step in 128 VGPRs, four waves to hide its gathers
+    return 2;                                                  // the asm bodies: 256 VGPRs
 }
 template <int ALGO, int SRC, bool DH, bool DEFER = false, bool CT = false>
-__global__ __launch_bounds__(BLOCK, ladder_waves(SRC, DH, CT)) void ladder_kernel(LadderArgs a) {
+__global__ __launch_bounds__(BLOCK, ladder_waves(SRC)) void ladder_kernel(LadderArgs a) {
     static_assert(!DEFER || DH, "only DH outputs are normalised");
-    static_assert(!(CT && SRC == PREBUILT), "the constant-time mode does not take the two-kernel route");
     constexpr bool USE_EF = SRC == FUSED;                      // LdsEF: the CU's whole LDS for one block of a fused kernel
-    __shared__ __attribute__((aligned(16))) u32 lds_table[SRC == LDS ? 8 * LDS_ENTRY_U32 : (USE_EF ? EF_LDS_U32 : 4)];
+    __shared__ __attribute__((aligned(16))) u32 lds_table[SRC == LDS ? 8 * LDS_ENTRY_U32 : EF_LDS_U32];
     using EF = typename std::conditional<USE_EF, LdsEF, NoEF>::type;
-    using L = typename std::conditional<SRC == PREBUILT, PrebuiltSlots, NDSlots>::type;      // slot layout (unused with SRC == LDS)
+    using L = NDSlots;                                         // the lane's slot (unused with SRC == LDS)
     EF ef;
     if constexpr (USE_EF) ef.lane = reinterpret_cast<uint2*>(lds_table) + threadIdx.x;
     if (SRC == LDS) {
@@ -574,33 +522,23 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC, DH, CT)) void ladder_kerne
         const u32 id = a.index ? a.index[a.base + pos] : a.base + pos;
         u64 m[4];
         load_scalar(a.scalars + 4 * (size_t)id, m);
-        u32* slot = SRC == LDS ? nullptr : a.scratch + (size_t)(SRC == FUSED ? lane_slot : pos) * L::SLOT;
-        const u32* tbl = slot;
-        if (SRC == PREBUILT && a.slot_of) {                              // mixed batch: own table or the shared one
-            const u32 own = a.slot_of[pos];
-            tbl = own == ~0u ? a.table_slots : a.scratch + (size_t)own * L::SLOT;
-        }
+        u32* slot = SRC == LDS ? nullptr : a.scratch + (size_t)lane_slot * L::SLOT;
 
         uint8_t st = FOURQ_DH_OK;
-        if (SRC == PREBUILT) {
-            if (DH) st = a.status[id];                                  // membership verdict of prep_kernel
-        } else {
-            R1 P;
-            if (DH) {
-                Fe2<1> x = load_fe2(a.points + 8 * (size_t)id), y = load_fe2(a.points + 8 * (size_t)id + 4);
-                if (!point_on_curve(x, y)) st = FOURQ_DH_NOT_ON_CURVE;  // keep going branch-free; masked at the end
-                if (SRC == FUSED) P = clear_cofactor_392(x, y);         // with a table the reference discards [392]P (curve4q.py:209)
-            } else if (SRC == FUSED) {
-                if (a.io & LADDER_IO_AFFINE_IN) P = affine_to_r1(load_fe2(a.points + 8 * (size_t)id), load_fe2(a.points + 8 * (size_t)id + 4));
-                else P = load_r1(a.points + 20 * (size_t)id);
-            }
-            if constexpr (SRC == FUSED) {
-                if constexpr (ALGO == ENDO) build_table_endo_lds_asm<L>(P, slot, ef);
-                else build_table_windowed<L>(P, slot, ef);
-            }
+        R1 P;
+        if (DH) {
+            Fe2<1> x = load_fe2(a.points + 8 * (size_t)id), y = load_fe2(a.points + 8 * (size_t)id + 4);
+            if (!point_on_curve(x, y)) st = FOURQ_DH_NOT_ON_CURVE;      // keep going branch-free; masked at the end
+            if (SRC == FUSED) P = clear_cofactor_392(x, y);             // with a table the reference discards [392]P (curve4q.py:209)
+        } else if (SRC == FUSED) {
+            if (a.io & LADDER_IO_AFFINE_IN) P = affine_to_r1(load_fe2(a.points + 8 * (size_t)id), load_fe2(a.points + 8 * (size_t)id + 4));
+            else P = load_r1(a.points + 20 * (size_t)id);
         }
-        R1 Q;
-        constexpr int CH = (SRC == PREBUILT && DH) ? LADDER_CH : 3;     // see "the ladders"
+        if constexpr (SRC == FUSED) {
+            if constexpr (ALGO == ENDO) build_table_endo_lds_asm<L>(P, slot, ef);
+            else build_table_windowed<L>(P, slot, ef);
+        }
+        R1 Q;                                                           // every ladder below runs the asm bodies (CH = 3, see "the ladders")
         if constexpr (ALGO == ENDO) {
             u64 v[4];
             decompose(m, v);
@@ -608,34 +546,32 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC, DH, CT)) void ladder_kerne
                 const EndoDigits e = recode(v);
                 ScanSplit<EF> regs;
                 regs.ef = ef;
-                regs.template load<L>(tbl);
+                regs.template load<L>(slot);
                 Q = ladder_endo_scan(e, regs);
             } else if constexpr (CT) {
                 Q = ladder_endo_scan(recode(v), ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
             } else if constexpr (SRC == FUSED) {
                 Q = ladder_endo_nibbles<L, EF, !DH>(recode_nibbles(v), a.scratch, lane_slot * (u32)L::SLOT, ef);      // MUL_*: signed limbs, see the store
-            } else if constexpr (SRC == LDS) {
-                Q = ladder_endo_nibbles_at<LimbSlots, NoEF>(recode_nibbles(v), lds_table, LDS_ENTRY_U32);
             } else {
-                Q = ladder_endo<CH, L, EF, CH != 3>(recode(v), tbl, L::ENTRY, ef);      // TOUCH with hipcc's step: the DH ladder
+                Q = ladder_endo_nibbles_at<LimbSlots, NoEF>(recode_nibbles(v), lds_table, LDS_ENTRY_U32);
             }
         } else {
             const WinScalar w = win_reduce(m);
             if constexpr (CT && SRC == FUSED) {
                 ScanSplit<EF> regs;
                 regs.ef = ef;
-                regs.template load<L>(tbl);
+                regs.template load<L>(slot);
                 Q = ladder_windowed_scan(w, regs);
             } else if constexpr (CT) {
                 Q = ladder_windowed_scan(w, ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
             } else if constexpr (SRC == LDS) {
-                Q = ladder_windowed<CH>(w, lds_table, LDS_ENTRY_U32);
+                Q = ladder_windowed<3>(w, lds_table, LDS_ENTRY_U32);
             } else {
-                Q = ladder_windowed<CH, L, EF, CH != 3>(w, tbl, L::ENTRY, ef);
+                Q = ladder_windowed<3, L, EF>(w, slot, L::ENTRY, ef);
             }
         }
         // One inversion per K elements, later (normalize_kernel).  FUSED: by a wave-uniform flag, no second instance -- DH batches of at least
-        // two generations defer like the other routes (round 6) instead of inverting per element at one wave per SIMD.
+        // two generations defer like the fixed-base ladders (round 6) instead of inverting per element at one wave per SIMD.
         if (DH && (DEFER || (SRC == FUSED && a.proj != nullptr))) {
             if (live) {
                 store_proj(a.proj, a.proj_stride, id, Q.X, Q.Y, Q.Z);
@@ -854,7 +790,7 @@ __global__ __launch_bounds__(BLOCK, 1) void mixed_queue_kernel(LadderArgs a, con
 // Mixed batches in CONSTANT-TIME mode, rounds larger than one generation.  The variable-base ids run through the fused constant-
 // time kernel (table in registers + LDS, one wave per SIMD), whose generations hold exactly `lanes` elements: config 5's 65 550
 // ids would cost a second generation of the whole chip for 14 elements.  split_counts_kernel therefore cuts a small remainder
-// (at most `limit` ids) off the list on the device; prep_kernel<ENDO, false, LimbSlots> builds those ids' tables into scratch, and
+// (at most `limit` ids) off the list on the device; prep_kernel builds those ids' tables into scratch, and
 // this kernel -- 128 registers, 1.6 KB of LDS, up to four waves per SIMD -- runs them TOGETHER with the round's fixed-base
 // elements: a wave whose 64 elements are all fixed-base scans the shared table in LDS (as ladder_kernel<ENDO, LDS, CT>), any other
 // wave scans each lane's own table through a per-lane pointer in global memory (every entry read at every step: no address depends
@@ -866,6 +802,17 @@ __global__ void split_counts_kernel(u32* counts, u32 lanes, u32 limit) {        
     const bool cut = whole > 0 && rem > 0 && rem <= limit;
     counts[4] = cut ? whole : n_var;
     counts[5] = cut ? rem : 0u;
+}
+// The overflow ids' tables for mixed_ct_tail_kernel: per id, table_endo into scratch slot `pos` as whole entries of working limbs
+// (what ScanMem reads).  A kernel of its own so that the endomorphisms' register appetite does not set the tail's occupancy.
+template <int UNIT_ONLY = 0>
+__global__ __launch_bounds__(BLOCK) void prep_kernel(LadderArgs a) {
+    const u32 pos = blockIdx.x * BLOCK + threadIdx.x;
+    if (pos >= (a.n_dev ? *a.n_dev : a.n)) return;
+    const u32 first = a.base + (a.base_dev ? *a.base_dev : 0u);
+    const u32 id = a.index ? a.index[first + pos] : first + pos;
+    const R1 P = load_r1(a.points + 20 * (size_t)id);
+    build_table_endo_pipelined<LimbSlots>(P, a.scratch + (size_t)pos * LimbSlots::SLOT);
 }
 template <int UNIT_ONLY = 0>
 __global__ __launch_bounds__(BLOCK, 2) void mixed_ct_tail_kernel(LadderArgs a, const u32* fix_list, const u32* var_list, const u32* counts, const u32* over_scratch) {
@@ -1154,8 +1101,7 @@ __global__ __launch_bounds__(BLOCK) void normalize_kernel(const uint4* proj, u32
 }  // namespace
 
 // launchers implemented in fourq_chain.hip (FQ_CHAIN=1 code objects)
-int chain_launch_ladder(int algo, int src, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);
-int chain_launch_prep(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);
+int chain_launch_ladder(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);   // the fixed-base (LDS) ladders; defers when a.proj != NULL
 int chain_setup_device();       // per-device function attributes (the comb's dynamic LDS); called by fourq_ctx_create
 int chain_launch_comb(unsigned grid, hipStream_t stream, const u64* scalars, const u32* comb_limbs, u64* out, uint8_t* status, uint4* proj, u32 proj_stride, u32 n);
 int chain_launch_normalize(int k, hipStream_t stream, const uint4* proj, u32 proj_stride, u64* out, uint8_t* status, u32 n);   // k in {1, 2, 4, 8}

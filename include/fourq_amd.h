@@ -102,7 +102,7 @@ int fourq_ctx_sync(fourq_ctx *ctx);
  * keeps the wanted entry by masks; per-lane tables live in registers; signs are applied arithmetically.  Results are
  * bit-identical in both modes; the price of ON is in DESIGN.md section 10.
  * Environment: FOURQ_CT_SELECT is the ONE variable the library reads as a product option.  The variables that steer batches onto
- * particular kernels (FOURQ_SPLIT_*, FOURQ_PAIR_MAX, FOURQ_QUAD_MAX, FOURQ_MIXED_QUEUE, FOURQ_NORM_K, FOURQ_BLOCKS_PER_CU,
+ * particular kernels (FOURQ_MIXED_ROUND, FOURQ_PAIR_MAX, FOURQ_QUAD_MAX, FOURQ_MIXED_QUEUE, FOURQ_NORM_K, FOURQ_BLOCKS_PER_CU,
  * FOURQ_HOST_BOUNCE, FOURQ_HOST_ZERO_COPY, FOURQ_PIPE_SLOTS, FOURQ_PIPE_GENS, FOURQ_PIPE_HOST_WAIT, FOURQ_PIPE_HOST_POLL, FOURQ_PIPE_MEASURE, FOURQ_FUSED_IO) are test hooks: they are ignored unless FOURQ_DEBUG_ROUTES=1 is set (tools/README.md).
  * One variable of the HIP RUNTIME matters to the host-pointer calls: they overlap copy-in, kernels and copy-out on three streams,
  * and the runtime shares GPU_MAX_HW_QUEUES hardware queues (default 4) among all streams the process uses -- in a process with two

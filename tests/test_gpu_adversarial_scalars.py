@@ -1,5 +1,5 @@
 """The adversarial scalar families (tests/adversarial_scalars.py) through the device's integer code on every route that compiles it in:
-the primitives, the variable- and fixed-base ladders with four, two and one lane per element and on the prep + ladder route, the mixed
+the primitives, the variable- and fixed-base ladders with four, two and one lane per element, the mixed
 batches, DH, the comb's three kernels in both shapes, its deferred flavour under [k]B + [l]P, and the exchange.
 
 tests/test_adversarial_scalars.py shows on the CPU what each family is for (the last rounds of comb_recode's plane iteration, the floor
@@ -26,11 +26,10 @@ G1_WORDS = codec.pack_point(G1)
 G_AFF = codec.pack_point((o.Gx, o.Gy))
 FAM = adv.families256()
 MS = [m for _, m in FAM]
-PAD = 640                                 # every batch: the families and seeded padding up to the prep + ladder route's minimum and past it
-HOOKS = ("FOURQ_PAIR_MAX", "FOURQ_QUAD_MAX", "FOURQ_SPLIT_MIN", "FOURQ_SPLIT_ALL", "FOURQ_MIXED_QUEUE")
-LADDER_ROUTES = {"four lanes": {}, "two lanes": {"FOURQ_QUAD_MAX": "0"}, "one lane": {"FOURQ_PAIR_MAX": "0"},
-                 "prep + ladder (constant-time mode: one lane again)": {"FOURQ_PAIR_MAX": "0", "FOURQ_SPLIT_MIN": "512", "FOURQ_SPLIT_ALL": "1"}}
-COMB_ROUTES = {k: LADDER_ROUTES[k] for k in ("four lanes", "two lanes", "one lane")}
+PAD = 640                                 # every batch: the families and seeded padding up to this many elements (several blocks of every kernel)
+HOOKS = ("FOURQ_PAIR_MAX", "FOURQ_QUAD_MAX", "FOURQ_MIXED_QUEUE")
+LADDER_ROUTES = {"four lanes": {}, "two lanes": {"FOURQ_QUAD_MAX": "0"}, "one lane": {"FOURQ_PAIR_MAX": "0"}}
+COMB_ROUTES = LADDER_ROUTES
 
 _cache = {}
 
@@ -161,9 +160,7 @@ def test_arithmetic_modulo_n(eng):
 # ---- ladders ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("route", list(LADDER_ROUTES))
 def test_ladders_on_every_route(eng, route, monkeypatch):
-    """MUL_* on G and on a seeded point, fixed base, mixed batches with either flag on every scalar, DH with and without a table.
-    The prep + ladder route exists in the default mode only: under the constant-time `eng` the same hooks lead to the fused one-lane
-    kernels once more, as the case's id says."""
+    """MUL_* on G and on a seeded point, fixed base, mixed batches with either flag on every scalar, DH with and without a table."""
     c = shared()
     S = c["S"]
     with fresh_engine(eng, LADDER_ROUTES[route], monkeypatch) as e:

@@ -143,12 +143,12 @@ def test_reference_self_test_sequence_on_the_gpu():
 @pytest.mark.parametrize("n", [1, 7, 1000, 2049])
 def test_batched_normalisation_groups(group, n, monkeypatch, golden):
     """R1toAffine with one inversion per `group` elements (Montgomery's trick): FOURQ_NORM_K forces the
-    group size that large batches pick by themselves and FOURQ_SPLIT_MIN=512 sends n >= 512 down the prep + ladder route
-    (which always defers; group 0 there means one inversion per element in normalize_kernel).  Rejected elements
+    group size that large batches pick by themselves and FOURQ_PAIR_MAX=0 keeps the variable-base calls on the one-lane fused
+    kernels, which defer for every forced group of 2, 4, 8 (LadderArgs::proj) and invert in the kernel for 0.  Rejected elements
     (off-curve, 392-torsion) sit inside the groups; every output and status must equal the C oracle's."""
     from fourq_amd import Engine
     monkeypatch.setenv("FOURQ_NORM_K", str(group))
-    monkeypatch.setenv("FOURQ_SPLIT_MIN", "512")
+    monkeypatch.setenv("FOURQ_PAIR_MAX", "0")
     e = Engine(0)
     try:
         s = seeded_scalars(4242 + n, n)

@@ -3,8 +3,7 @@
 from canonical inputs, takes the expected result from the C oracle on those, and gives the GPU twins with the same residues: x + p for any
 coordinate and x + 2p for x in {0, 1}, chosen per coordinate; for MUL_* (whose formulas need no curve point, as in
 test_gpu_mul.py::test_special_base_points) also R1 tuples of extreme words.  Both selection modes (the `eng` fixture); the routes by
-size and through the library's test hooks (FOURQ_PAIR_MAX, FOURQ_QUAD_MAX, FOURQ_MIXED_QUEUE, FOURQ_SPLIT_MIN, FOURQ_FUSED_IO); the
-prep + ladder route in the default mode only, as the constant-time mode never takes it."""
+size and through the library's test hooks (FOURQ_PAIR_MAX, FOURQ_QUAD_MAX, FOURQ_MIXED_QUEUE, FOURQ_FUSED_IO)."""
 import random
 
 import numpy as np
@@ -251,27 +250,3 @@ def test_constant_time_mixed_tail_twins(data):
         fix = np.flatnonzero(flags == 0)
         want[fix] = oc.mul(oc.ENDO, sc[fix], None, data["te"])
         assert np.array_equal(e.mul_endo_mixed(sc, twin(pts, 60), flags, twin(data["te"], 61)), want)
-
-
-def test_prep_and_ladder_route_twins(monkeypatch):
-    """the prep + ladder route (prep_kernel builds the table from the input words): FOURQ_PAIR_MAX=0 turns off the two-lane tail, which
-    variable_route (fourq_amd.hip) prefers below two generations, and FOURQ_SPLIT_MIN=512 sends MUL_windowed and DH_* batches of 512
-    or more down the route.  Default selection mode only: the constant-time mode never takes it."""
-    from fourq_amd import Engine
-    monkeypatch.setenv("FOURQ_PAIR_MAX", "0")
-    monkeypatch.setenv("FOURQ_SPLIT_MIN", "512")
-    n = 3000
-    with Engine(0) as e:
-        assert not e.ct_select
-        sc = seeded_scalars(7401, n)
-        pts = e.mul_endo_fixed(seeded_scalars(7402, n), oc.table(oc.ENDO, codec.pack_point(G1)))
-        aff = oc.r1_to_affine(pts)
-        aff[7, 0] ^= 1                                                    # not on the curve
-        from conftest import load_golden, unhex
-        aff[11] = codec.pack_point(unhex(load_golden("kat.json", raw=True)["P392"]))
-        assert np.array_equal(e.mul_windowed(sc, twin(pts, 62)), oc.mul(oc.WINDOWED, sc, pts))
-        tw = twin(aff, 63)
-        for kind, fn in ((oc.ENDO, e.dh_endo), (oc.WINDOWED, e.dh_windowed)):
-            want, wst = oc.dh(kind, sc, aff)
-            got, st = fn(sc, tw)
-            assert wst[7] == 1 and wst[11] == 2 and np.array_equal(st, wst) and np.array_equal(got, want), kind

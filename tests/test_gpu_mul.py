@@ -352,12 +352,11 @@ def test_constant_time_mixed_round_cuts_a_small_remainder_off_the_fused_generati
 
 
 @pytest.mark.parametrize("n", [131071, 131072, 262144 + 77])
-def test_prep_plus_ladder_route_boundaries(n, monkeypatch):
-    """Large variable-base MUL_windowed / DH batches take the two-kernel route (prep_kernel +
-    ladder_kernel<PREBUILT>) in chunks of the resident lane count; FOURQ_SPLIT_ALL=1 sends MUL_endo through it
-    too.  Sizes just below / at the switch and just past one chunk; outputs vs the C oracle."""
+def test_generation_boundaries(n):
+    """131071, 131072 and 262144 + 77 elements on the default routes.  With 65 536 resident lanes (256 CUs) that is one element short of
+    two generations of the fused kernels, exactly two, and four generations + a two-lane tail of 77.  MUL_endo in full and the last
+    20 000 elements of MUL_windowed against the C oracle."""
     from fourq_amd import Engine
-    monkeypatch.setenv("FOURQ_SPLIT_ALL", "1")
     with Engine(0) as eng:
         s = seeded_scalars(4100 + n % 97, n)
         pts = torsion_points(eng, 4200 + n % 89, n)

@@ -136,7 +136,7 @@ def test_dh_exchange_on_device(eng, golden):
     eng.comb_stage(comb)
     out_c, st_c = eng.dh_exchange_comb(a[:100], b[:100])            # None = the staged comb
     assert np.array_equal(st_c, ws[:100]) and np.array_equal(out_c, want[:100])
-    m = 2 * eng.lanes + 321                                          # several pipeline chunks, the two-kernel route in the second half
+    m = 2 * eng.lanes + 321                                          # several pipeline chunks; the second half runs two fused generations + a two-lane tail
     a2, b2 = seeded_scalars(33, m), seeded_scalars(34, m)
     out_c, st_c = eng.dh_exchange_comb(a2, b2)
     mid, s1 = oc.dh(oc.ENDO, b2, np.repeat(codec.pack_point(G).reshape(1, 8), m, axis=0))

@@ -1,6 +1,6 @@
 """The closed-form recoders (fourq_amd/csrc/recode.hip.h) on the device.  tests/test_recode_host.py holds the same code, compiled for the
 host, against the bit-serial loop on a million rows; here the compiled gfx950 code is asked directly -- the primitives SC_RECODE (the
-planes: the constant-time and two-kernel ladders) and SC_RECODE_NIBBLES (the nibble stream of the fused ladders) on a grid of edge words
+planes: the constant-time and pair-lane ladders) and SC_RECODE_NIBBLES (the nibble stream of the fused ladders) on a grid of edge words
 against the Python oracle's signs and digits -- and then through the one-lane fused kernels, whose ladders read those digits: MUL_endo, DH
 and a mixed batch of 640 elements against the C oracle.  Their scalars are picked from a seeded pool so that every value the top digit CAN take
 in a multiplication occurs at least 40 times: that is 1, 3, 4, 5, 6 and 7.  The top digit is c1 + 2 c2 + 4 c3 with c_j the carry out of
@@ -26,7 +26,7 @@ V0 = (1, 3, M64, A5, (A5 << 1) | 1)
 N = 640
 REACHABLE_TOPS = (1, 3, 4, 5, 6, 7)
 G1_WORDS = codec.pack_point(o.AffineToR1(o.Gx, o.Gy))
-HOOKS = ("FOURQ_PAIR_MAX", "FOURQ_QUAD_MAX", "FOURQ_SPLIT_MIN", "FOURQ_SPLIT_ALL", "FOURQ_MIXED_QUEUE")
+HOOKS = ("FOURQ_PAIR_MAX", "FOURQ_QUAD_MAX", "FOURQ_MIXED_QUEUE")
 
 _cache = {}
 

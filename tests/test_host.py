@@ -81,7 +81,7 @@ def test_every_environment_variable_the_library_reads_is_documented():
     in_lib = {m.decode() for m in re.findall(rb"FOURQ_[A-Z][A-Z0-9_]+", blob)}
     header = open(os.path.join(ROOT, "include", "fourq_amd.h")).read()
     readme = open(os.path.join(ROOT, "tools", "README.md")).read()
-    hooks = {"FOURQ_BLOCKS_PER_CU", "FOURQ_SPLIT_MIN", "FOURQ_SPLIT_ALL", "FOURQ_SPLIT_ENDO_MIN", "FOURQ_SPLIT_CHUNK", "FOURQ_PAIR_MAX",
+    hooks = {"FOURQ_BLOCKS_PER_CU", "FOURQ_MIXED_ROUND", "FOURQ_PAIR_MAX",
              "FOURQ_QUAD_MAX", "FOURQ_MIXED_QUEUE", "FOURQ_NORM_K", "FOURQ_HOST_BOUNCE", "FOURQ_HOST_ZERO_COPY",
              "FOURQ_PIPE_SLOTS", "FOURQ_PIPE_GENS", "FOURQ_PIPE_HOST_WAIT", "FOURQ_PIPE_HOST_POLL", "FOURQ_PIPE_MEASURE", "FOURQ_FUSED_IO"}
     env_like = {v for v in in_lib if not v.startswith(("FOURQ_ERR", "FOURQ_OK", "FOURQ_DH_", "FOURQ_DECODE", "FOURQ_FP", "FOURQ_PT", "FOURQ_MAX", "FOURQ_TABLE", "FOURQ_COMB_", "FOURQ_R"))}

@@ -40,19 +40,14 @@ rounds = 0
 while time.time() < t_end:
     knobs = {}
     if rng.random() < 0.7:
-        knobs["FOURQ_SPLIT_MIN"] = str(rng.choice([1, 256, 1000, 70000]))
-        knobs["FOURQ_SPLIT_CHUNK"] = str(rng.choice([256, 4096, 65536, 262144]))
+        knobs["FOURQ_MIXED_ROUND"] = str(rng.choice([256, 4096, 65536, 262144]))
         knobs["FOURQ_NORM_K"] = str(rng.choice([0, 2, 4, 8]))
-        if rng.random() < 0.3:
-            knobs["FOURQ_SPLIT_ALL"] = "1"
-        if rng.random() < 0.3:
-            knobs["FOURQ_SPLIT_ENDO_MIN"] = str(rng.choice([0, 300, 70000]))
     if rng.random() < 0.35:
         knobs["FOURQ_CT_SELECT"] = "1"
     if rng.random() < 0.3:
         knobs["FOURQ_HOST_BOUNCE"] = "0"
     if rng.random() < 0.4:
-        knobs["FOURQ_MIXED_QUEUE"] = rng.choice(["0", "1"])          # round 3: the persistent work-queue kernel forced on / off
+        knobs["FOURQ_MIXED_QUEUE"] = rng.choice(["0", "1"])          # constant-time mode: the work-queue kernel / the fused kernel + tail forced for every round; both modes: no pair-lane route
     if rng.random() < 0.3:
         knobs["FOURQ_PAIR_MAX"] = rng.choice(["0", "100", "5000"])     # round 3: the two-lanes-per-element kernel off / for tiny tails only
     if rng.random() < 0.3:
@@ -68,7 +63,7 @@ while time.time() < t_end:
         knobs["FOURQ_FUSED_IO"] = "0"
     if rng.random() < 0.25:                                            # ... and chunk plans from the compiled-in guesses instead of the context's measurements
         knobs["FOURQ_PIPE_MEASURE"] = "0"
-    for k in ("FOURQ_FUSED_IO", "FOURQ_PIPE_MEASURE", "FOURQ_PIPE_SLOTS", "FOURQ_PIPE_GENS", "FOURQ_PIPE_HOST_WAIT", "FOURQ_PAIR_MAX", "FOURQ_QUAD_MAX", "FOURQ_HOST_ZERO_COPY", "FOURQ_SPLIT_MIN", "FOURQ_SPLIT_CHUNK", "FOURQ_NORM_K", "FOURQ_SPLIT_ALL", "FOURQ_SPLIT_ENDO_MIN", "FOURQ_CT_SELECT", "FOURQ_HOST_BOUNCE", "FOURQ_MIXED_QUEUE"):
+    for k in ("FOURQ_FUSED_IO", "FOURQ_PIPE_MEASURE", "FOURQ_PIPE_SLOTS", "FOURQ_PIPE_GENS", "FOURQ_PIPE_HOST_WAIT", "FOURQ_PAIR_MAX", "FOURQ_QUAD_MAX", "FOURQ_HOST_ZERO_COPY", "FOURQ_MIXED_ROUND", "FOURQ_NORM_K", "FOURQ_CT_SELECT", "FOURQ_HOST_BOUNCE", "FOURQ_MIXED_QUEUE"):
         os.environ.pop(k, None)
     os.environ.update(knobs)
     with Engine(0) as eng:

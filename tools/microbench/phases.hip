@@ -70,7 +70,7 @@ int main() {
     const int n = 1 << 16;
     u64 *s, *p, *o; u32* scr; uint64_t* st;
     CHECK(hipMalloc(&s, n * 32)); CHECK(hipMalloc(&p, n * 160)); CHECK(hipMalloc(&o, n * 160));
-    CHECK(hipMalloc(&scr, (size_t)n * PackedSlots::SLOT * 4)); CHECK(hipMalloc(&st, 1024 * 64));
+    CHECK(hipMalloc(&scr, (size_t)n * NDSlots::SLOT * 4)); CHECK(hipMalloc(&st, 1024 * 64));
     std::vector<u64> hs(n * 4), hp(n * 20);
     uint64_t x = 88172645463325252ull;
     auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
