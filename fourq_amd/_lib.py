@@ -27,6 +27,7 @@ COMB_WORDS = COMB_POINTS * 12        # FOURQ_COMB_WORDS
 BYTES_DECODE_BASE = 16
 SIG_S_RANGE, SIG_MSG_CLAMPED, SIG_MAX_MSG = 32, 64, 1 << 20   # FOURQ_SIG_*
 H2C_RO, H2C_NU, H2C_MAX_DST = 0, 1, 255                       # FOURQ_H2C_*
+OPRF_BLIND_ZERO = 48                                          # FOURQ_OPRF_BLIND_ZERO
 
 
 class HostStats(ctypes.Structure):
@@ -131,6 +132,17 @@ PROTOTYPES = {
     "fourq_hash_to_curve_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_hash_to_curve_affine_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_hash_to_curve_affine_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "fourq_oprf_blind_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_oprf_blind_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_oprf_evaluate_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_oprf_evaluate_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_oprf_finalize_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_oprf_finalize_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_oprf_eval_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    "fourq_oprf_eval_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    "fourq_scalar_inv_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_scalar_inv_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_ctx_set_scinv_group": (c_int, [c_void_p, c_int]),
     "fourq_encode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_decode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
@@ -146,7 +158,7 @@ PRIM = {
     "PT_DBL": 32, "PT_ADD": 33, "PT_ADD_CORE": 34, "PT_R1TOR2": 35, "PT_R1TOR3": 36, "PT_R2TOR4": 37,
     "PT_TAU": 38, "PT_TAU_DUAL": 39, "PT_UPSILON": 40, "PT_CHI": 41, "PT_PHI": 42, "PT_PSI": 43,
     "PT_ON_CURVE": 44, "PT_COFACTOR392": 45, "PT_R1TOAFFINE": 46, "PT_MAP_ELL2": 47,
-    "SC_DECOMPOSE": 64, "SC_RECODE": 65, "SC_WINDOWED": 66, "SC_REDUCE512": 67, "SC_MULSUB": 68, "SC_MUL": 69, "SC_RECODE_NIBBLES": 70,
+    "SC_DECOMPOSE": 64, "SC_RECODE": 65, "SC_WINDOWED": 66, "SC_REDUCE512": 67, "SC_MULSUB": 68, "SC_MUL": 69, "SC_RECODE_NIBBLES": 70, "SC_INV": 71,
 }
 
 

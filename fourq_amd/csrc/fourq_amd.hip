@@ -40,6 +40,7 @@
 #include "work_layout.h"
 #include "sig.hip.h"
 #include "h2c.hip.h"
+#include "oprf.hip.h"
 
 using namespace fq;
 
@@ -440,7 +441,7 @@ const PrimShape PRIMS[] = {
     { FOURQ_PT_ON_CURVE, 8, 1 }, { FOURQ_PT_COFACTOR392, 8, 20 }, { FOURQ_PT_R1TOAFFINE, 20, 8 },
     { FOURQ_PT_MAP_ELL2, 4, 8 },                                                             // h2c.hip.h
     { FOURQ_SC_DECOMPOSE, 4, 4 }, { FOURQ_SC_RECODE, 4, 5 }, { FOURQ_SC_RECODE_NIBBLES, 4, 9 }, { FOURQ_SC_WINDOWED, 4, 8 },
-    { FOURQ_SC_REDUCE512, 8, 4 }, { FOURQ_SC_MULSUB, 12, 4 }, { FOURQ_SC_MUL, 8, 4 },        // sig.hip.h (scalar_n.hip.h)
+    { FOURQ_SC_REDUCE512, 8, 4 }, { FOURQ_SC_MULSUB, 12, 4 }, { FOURQ_SC_MUL, 8, 4 }, { FOURQ_SC_INV, 4, 4 },        // sig.hip.h (scalar_n.hip.h)
 };
 const PrimShape* find_prim(int op) {
     for (const PrimShape& p : PRIMS) if (p.op == op) return &p;
@@ -453,7 +454,8 @@ const PrimShape* find_prim(int op) {
 // Which host-array call this is, for the measured planner inputs (fourq_ctx::plan_kt)
 enum PipeRouteId { PR_MUL_VAR = 0, PR_MUL_FIX = 2, PR_DH_VAR = 4, PR_DH_FIX = 6, PR_MIXED = 8, PR_COMB = 9, PR_ENCODE = 10, PR_DECODE = 11, PR_DHB_VAR = 12,
                    PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25,
-                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_H2F = 30, PR_H2C_MAP = 31, PR_H2C = 32, PR_H2C_AFFINE = 34, PR_COUNT = 36 };       // + algo or mode (0 / 1) where two follow each other
+                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_H2F = 30, PR_H2C_MAP = 31, PR_H2C = 32, PR_H2C_AFFINE = 34, PR_OPRF_BLIND = 36,
+                   PR_OPRF_EVALUATE = 37, PR_OPRF_FINALIZE = 38, PR_OPRF_EVAL = 39, PR_SC_INV = 40, PR_COUNT = 41 };       // + algo or mode (0 / 1) where two follow each other
 static_assert(PR_H2C_AFFINE + FOURQ_H2C_NU < PR_COUNT && FOURQ_H2C_RO == 0 && FOURQ_H2C_NU == 1, "the highest route id plus its mode offset must fit fourq_ctx::plan_kt");
 constexpr int PIPE_SLOTS_MAX = 6;
 struct fourq_ctx {
@@ -484,6 +486,7 @@ struct fourq_ctx {
     size_t pair_max = 0;           // variable-base batches (and tails past whole generations) of at most this many elements run two lanes per element
     uint4* proj = nullptr;         // deferred normalisation of DH batches: PROJ_PLANES planes of proj_capacity uint4, grown on demand
     size_t proj_capacity = 0;
+    int scinv_k = 0;               // fourq_ctx_set_scinv_group (test hook): 1 / 8 / 16 = that many elements per inversion modulo N whatever the batch size; 0 = by batch size
     int norm_k = -1;               // FOURQ_NORM_K: 0 = always invert per element, 2/4/8 = always batch; -1 = by batch size
     void* stage = nullptr;         // staging for the small host-pointer calls (tables, primitives)
     size_t stage_bytes = 0;
@@ -1352,7 +1355,8 @@ FQ_API int fourq_ctx_reserve(fourq_ctx* c, size_t n) {
     CtxGuard g(c);
     if (int rc = ensure_proj(c, n)) return rc;
     using namespace fq_work;
-    return ensure_work(c, std::max({ DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n), Msm::bytes(n) }));
+    return ensure_work(c, std::max({ DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n), Msm::bytes(n),
+                                     OprfBlind::bytes(n), OprfEvaluate::bytes(n), OprfFinalize::bytes(n), OprfEval::bytes(n) }));
 }
 FQ_API int fourq_ctx_lanes(const fourq_ctx* c, size_t* lanes) {
     if (!c || !lanes) return FOURQ_ERR_INVALID;
@@ -2148,6 +2152,170 @@ FQ_API int fourq_map_to_curve_batch(fourq_ctx* c, const uint64_t* u, uint64_t* o
     });
 }
 
+// ---- oblivious PRF (include/fourq_amd.h, "oblivious PRF"): the hash-to-curve stages, the ladders with affine / encoded I/O, DH_endo and the
+// lowering above, strung together with the inversion modulo N, the key broadcast and the finalisation hash of oprf.hip.h.  Every
+// intermediate -- G(msg), the inverted blind, the unblinded element -- lives in the context's work buffer (work_layout.h, Oprf*).
+// Elements per inversion: one while the batch is at most one wave per SIMD (the chain's latency is the time either way), 8 up to eight
+// times that, 16 beyond (the chain is shared by more elements once there are lanes enough to fill the chip).  fourq_ctx_set_scinv_group (a test hook) forces it.
+static int scinv_group(const fourq_ctx* c, size_t n) {
+    if (c->scinv_k) return c->scinv_k;
+    const size_t wave_per_simd = (size_t)c->cus * BLOCK;
+    return n <= wave_per_simd ? 1 : n <= 8 * wave_per_simd ? OPRF_SCINV_K_MID : OPRF_SCINV_K_BIG;
+}
+static int reserve_oprf_blind(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::OprfBlind::bytes(big)); }
+static int reserve_oprf_evaluate(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::OprfEvaluate::bytes(big)); }
+static int reserve_oprf_finalize(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::OprfFinalize::bytes(big)); }
+static int reserve_oprf_eval(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::OprfEval::bytes(big)); }
+// first-call guesses like the other KT_*: a Fermat chain is about 1.2 ladders' worth of instructions, shared by 8 elements
+constexpr double KT_SCINV = 0.70;
+
+// Test hook, gated like the routing variables (route_env): refused unless FOURQ_DEBUG_ROUTES=1 is set.  It is a call and not one more variable:
+// the set of variables the library reads is pinned (tests/test_host.py).  k: 1, 8 or 16 elements per inversion, 0 = by batch size again.
+FQ_API int fourq_ctx_set_scinv_group(fourq_ctx* c, int k) {
+    const char* gate = getenv("FOURQ_DEBUG_ROUTES");
+    if (!c || !gate || atoi(gate) == 0 || (k != 0 && k != 1 && k != OPRF_SCINV_K_MID && k != OPRF_SCINV_K_BIG)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    c->scinv_k = k;
+    return FOURQ_OK;
+}
+FQ_API int fourq_scalar_inv_batch_dev(fourq_ctx* c, const uint64_t* scalars, uint64_t* out, size_t n) {
+    if (!c || !scalars || !out || n > FOURQ_MAX_BATCH || !aligned16(scalars) || !aligned16(out)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    HIPRC_TRY(c, oprf_launch_sc_inv(c->stream, scinv_group(c, n), scalars, out, nullptr, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_scalar_inv_batch(fourq_ctx* c, const uint64_t* scalars, uint64_t* out, size_t n) {
+    if (!c || !scalars || !out || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    PipeArray in[1] = { { (const char*)scalars, nullptr, 32 } };
+    PipeArray o[1] = { { nullptr, (char*)out, 32 } };
+    return run_pipeline(c, in, 1, o, 1, n, 16 * (size_t)c->cus * BLOCK, PipeRoute{ PR_SC_INV, KT_SCINV }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_scalar_inv_batch_dev(c, (const uint64_t*)di[0], (uint64_t*)dout[0], m);
+    });
+}
+
+FQ_API int fourq_oprf_blind_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                      const uint64_t* blinds, uint8_t* out32, uint8_t* status, size_t n) {
+    if (!c || !blinds || !out32 || !status || n > FOURQ_MAX_BATCH || !aligned16(blinds) || !aligned16(out32)) return FOURQ_ERR_INVALID;
+    if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = reserve_oprf_blind(c, n);
+    if (rc) return rc;
+    const fq_work::OprfBlind w(c->work, n);
+    const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w.u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w.u, w.pts, (u32)n));
+    HIP_TRY(c, hipMemsetAsync(w.st_decode, 0, n, c->stream));              // the lowering reads a decode code per row: these points were never decoded
+    u32 row_words;
+    if ((rc = mul_rows_dev(c, ENDO, blinds, w.pts, false, w.rows_in, w.rows_out, nullptr, n, &row_words))) return rc;
+    if ((rc = launch_lower(c, true, w.rows_out, row_words, w.st_decode, (uint64_t*)out32, status, n))) return rc;
+    HIPRC_TRY(c, oprf_launch_blind_merge(c->stream, blinds, m, out32, status, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_oprf_evaluate_batch_dev(fourq_ctx* c, const uint64_t* key, const uint8_t* blinded32, uint8_t* out32, uint8_t* status, size_t n) {
+    if (!c || !key || !blinded32 || !out32 || !status || n > FOURQ_MAX_BATCH || !aligned16(blinded32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = ensure_work(c, fq_work::OprfEvaluate::bytes(n));               // the planes only if dh_dev defers, as dh_bytes_dev
+    if (rc) return rc;
+    const fq_work::OprfEvaluate w(c->work, n);
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w.keys, (u32)n));
+    return dh_bytes_dev(c, ENDO, w.keys, blinded32, nullptr, out32, status, n);     // carves DhBytes at the buffer's start: w.dh
+}
+FQ_API int fourq_oprf_finalize_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                         const uint64_t* blinds, const uint8_t* evaluated32, uint8_t* out64, uint8_t* status, size_t n) {
+    if (!c || !blinds || !evaluated32 || !out64 || !status || n > FOURQ_MAX_BATCH || !aligned16(blinds) || !aligned16(evaluated32) || !aligned16(out64)) return FOURQ_ERR_INVALID;
+    if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = reserve_oprf_finalize(c, n);
+    if (rc) return rc;
+    const fq_work::OprfFinalize w(c->work, n);
+    HIPRC_TRY(c, oprf_launch_sc_inv(c->stream, scinv_group(c, n), blinds, w.inv, w.st_zero, (u32)n));
+    u32 row_words;
+    if ((rc = mul_rows_dev(c, ENDO, w.inv, evaluated32, true, w.rows_in, w.rows_out, w.st_decode, n, &row_words))) return rc;
+    if ((rc = launch_lower(c, true, w.rows_out, row_words, w.st_decode, w.e32, w.st_lower, n))) return rc;
+    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w.e32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, oprf_make_tail(dst, dst_len), w.st_lower, w.st_zero,
+                                   out64, status, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_oprf_eval_batch_dev(fourq_ctx* c, const uint64_t* key, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens,
+                                     size_t msg_len, uint8_t* out64, uint8_t* status, size_t n) {
+    if (!c || !key || !out64 || !status || n > FOURQ_MAX_BATCH || !aligned16(out64)) return FOURQ_ERR_INVALID;
+    if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = ensure_work(c, fq_work::OprfEval::bytes(n));
+    if (rc) return rc;
+    const fq_work::OprfEval w(c->work, n);
+    const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w.u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w.u, w.pts, (u32)n));
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w.keys, (u32)n));
+    if ((rc = dh_dev(c, ENDO, w.keys, w.pts, nullptr, w.shared, w.st_dh, n))) return rc;
+    if ((rc = fourq_encode_batch_dev(c, w.shared, (uint8_t*)w.e32, n))) return rc;
+    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w.e32, m, oprf_make_tail(dst, dst_len), w.st_dh, nullptr, out64, status, (u32)n));
+    return FOURQ_OK;
+}
+// host-pointer twins
+static double oprf_kt_final(size_t stride, size_t dst_len) { return KT_SHA_BLOCK * (double)((32 + stride + 9 + dst_len + 17 + 127) / 128); }
+FQ_API int fourq_oprf_blind_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                  const uint64_t* blinds, uint8_t* out32, uint8_t* status, size_t n) {
+    if (!c || !blinds || !out32 || !status || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    PipeArray in[3] = { { (const char*)blinds, nullptr, 32 } };
+    int n_in = 1;
+    const MsgArrays ma(in, &n_in, msgs, stride, lens);
+    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
+    const double kt = h2c_kt_hash(stride, dst_len, 2) + 2 * KT_ELL2 + KT_ENDO_VAR + 2 * KT_LIFT_LOWER;
+    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_OPRF_BLIND, kt }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_oprf_blind_batch_dev(c, dst, dst_len, ma.msgs(di), stride, ma.lens(di), msg_len, (const uint64_t*)di[0], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
+    }, 0, reserve_oprf_blind);
+}
+FQ_API int fourq_oprf_evaluate_batch(fourq_ctx* c, const uint64_t* key, const uint8_t* blinded32, uint8_t* out32, uint8_t* status, size_t n) {
+    if (!c || !key || !blinded32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    PipeArray in[1] = { { (const char*)blinded32, nullptr, 32 } };
+    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
+    return run_pipeline(c, in, 1, o, 2, n, pipe_chunk(c), PipeRoute{ PR_OPRF_EVALUATE, KT_DH_VAR + KT_CODEC }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_oprf_evaluate_batch_dev(c, key, (const uint8_t*)di[0], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
+    }, 0, reserve_oprf_evaluate);
+}
+FQ_API int fourq_oprf_finalize_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                     const uint64_t* blinds, const uint8_t* evaluated32, uint8_t* out64, uint8_t* status, size_t n) {
+    if (!c || !blinds || !evaluated32 || !out64 || !status || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    PipeArray in[4] = { { (const char*)blinds, nullptr, 32 }, { (const char*)evaluated32, nullptr, 32 } };
+    int n_in = 2;
+    const MsgArrays ma(in, &n_in, msgs, stride, lens);
+    PipeArray o[2] = { { nullptr, (char*)out64, 64 }, { nullptr, (char*)status, 1 } };
+    const double kt = KT_SCINV + KT_ENDO_VAR + KT_LIFT_LOWER + KT_CODEC + oprf_kt_final(stride, dst_len);
+    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_OPRF_FINALIZE, kt }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_oprf_finalize_batch_dev(c, dst, dst_len, ma.msgs(di), stride, ma.lens(di), msg_len, (const uint64_t*)di[0], (const uint8_t*)di[1], (uint8_t*)dout[0],
+                                             (uint8_t*)dout[1], m);
+    }, 0, reserve_oprf_finalize);
+}
+FQ_API int fourq_oprf_eval_batch(fourq_ctx* c, const uint64_t* key, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens,
+                                 size_t msg_len, uint8_t* out64, uint8_t* status, size_t n) {
+    if (!c || !key || !out64 || !status || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    PipeArray in[2];
+    int n_in = 0;
+    const MsgArrays ma(in, &n_in, msgs, stride, lens);
+    PipeArray o[2] = { { nullptr, (char*)out64, 64 }, { nullptr, (char*)status, 1 } };
+    const double kt = h2c_kt_hash(stride, dst_len, 2) + 2 * KT_ELL2 + KT_LIFT_LOWER + KT_DH_VAR + KT_ENCODE + oprf_kt_final(stride, dst_len);
+    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_OPRF_EVAL, kt }, [&](char* const* di, char* const* dout, size_t m) {
+        return fourq_oprf_eval_batch_dev(c, key, dst, dst_len, ma.msgs(di), stride, ma.lens(di), msg_len, (uint8_t*)dout[0], (uint8_t*)dout[1], m);
+    }, 0, reserve_oprf_eval);
+}
+
 // ---- pinned host memory and transfer statistics of the host-pointer calls ---------------------------------------
 FQ_API int fourq_host_alloc(fourq_ctx* c, size_t bytes, void** out) {
     if (!c || !out) return FOURQ_ERR_INVALID;
@@ -2319,7 +2487,7 @@ FQ_API int fourq_prim_batch(fourq_ctx* c, int op, const uint64_t* in, uint64_t* 
     if (rc) return rc;
     char* base = (char*)c->stage;
     HIP_TRY(c, hipMemcpyAsync(base, in, ib, hipMemcpyHostToDevice, c->stream));
-    if (op == FOURQ_SC_REDUCE512 || op == FOURQ_SC_MULSUB || op == FOURQ_SC_MUL) {
+    if (op == FOURQ_SC_REDUCE512 || op == FOURQ_SC_MULSUB || op == FOURQ_SC_MUL || op == FOURQ_SC_INV) {
         HIPRC_TRY(c, sig_launch_scalar_prim(c->stream, op, (const uint64_t*)base, (uint64_t*)(base + ib), (u32)n));
     } else if (op == FOURQ_PT_MAP_ELL2) {
         HIPRC_TRY(c, h2c_launch_ell2(c->stream, 1, H2C_OUT_MAP, (const uint64_t*)base, (uint64_t*)(base + ib), (u32)n));

@@ -164,6 +164,10 @@ __global__ __launch_bounds__(64) void scalar_prim_kernel(int op, const u64* in, 
         const u64* x = in + 8 * (size_t)i;
         const u64 a[4] = { x[0], x[1], x[2], x[3] }, b[4] = { x[4], x[5], x[6], x[7] };
         sc_mul(a, b, r);
+    } else if (op == FOURQ_SC_INV) {
+        const u64* x = in + 4 * (size_t)i;
+        const u64 a[4] = { x[0], x[1], x[2], x[3] };
+        sc_inv(a, r);
     } else {
         const u64* x = in + 12 * (size_t)i;
         const u64 rr[4] = { x[0], x[1], x[2], x[3] }, a[4] = { x[4], x[5], x[6], x[7] }, h[4] = { x[8], x[9], x[10], x[11] };

@@ -93,5 +93,43 @@ struct Msm {
     Msm(char* base, size_t n) { Carver w(base); rows_in = w.take<uint64_t>(n * 20); rows_out = w.take<uint64_t>(n * 20); st_decode = w.take_status(n); part_a = w.take<uint64_t>(n / 2 * 12); st_a = w.take_status(n / 2); part_b = w.take<uint64_t>(n / 4 * 12); st_b = w.take_status(n / 4); end = w.used; }
     static size_t bytes(size_t n) { return Msm(nullptr, n).end; }
 };
+// ---- the oblivious PRF (oprf.hip.h).  Each of the four totals is below SigVerify's 416 n + 3 n (blind and finalize: 384 n + n and
+// 384 n + 3 n of status; evaluate: DhBytes + 32 n; eval: 192 n + n): fourq_ctx_reserve does not grow.
+struct OprfBlind {                  // hash to curve -> MUL_endo by the blind -> encode
+    uint64_t* pts;                  // G(msg) as affine words: n x 8
+    uint64_t *rows_in, *rows_out;   // as MulRows
+    uint64_t* u;                    // u_0, u_1: n x 8 words ON rows_in -- u is dead once the map has run, and the lift that fills rows_in comes after it
+    uint8_t* st_decode;             // all zero (the points come from the map, not from a decode): what lower_kernel<K, true> reads
+    size_t end;
+    OprfBlind(char* base, size_t n) { Carver w(base); pts = w.take<uint64_t>(n * 8); rows_in = w.take<uint64_t>(n * 20); u = rows_in; rows_out = w.take<uint64_t>(n * 20); st_decode = w.take_status(n); end = w.used; }
+    static size_t bytes(size_t n) { return OprfBlind(nullptr, n).end; }
+};
+struct OprfEvaluate {               // the key on n scalar rows -> decode -> DH_endo -> encode
+    char* dh;                       // DhBytes, carved by the DH call itself: it asks for less than this layout's total and moves nothing
+    uint64_t* keys;                 // n x 4 words
+    size_t end;
+    OprfEvaluate(char* base, size_t n) { Carver w(base); dh = w.take<char>(DhBytes::bytes(n)); keys = w.take<uint64_t>(n * 4); end = w.used; }
+    static size_t bytes(size_t n) { return OprfEvaluate(nullptr, n).end; }
+};
+struct OprfFinalize {               // 1 / blind -> decode -> MUL_endo -> encode -> hash
+    uint64_t* inv;                  // the inverted blinds: n x 4 words
+    uint64_t *rows_in, *rows_out;   // as MulRows
+    uint64_t* e32;                  // the unblinded element as 32 bytes: n x 4 words
+    uint8_t *st_decode, *st_lower;  // decode's codes, and 16 + code as the lowering reports them
+    uint8_t* st_zero;               // FOURQ_OPRF_BLIND_ZERO where the blind is 0 mod N
+    size_t end;
+    OprfFinalize(char* base, size_t n) { Carver w(base); inv = w.take<uint64_t>(n * 4); rows_in = w.take<uint64_t>(n * 20); rows_out = w.take<uint64_t>(n * 20); e32 = w.take<uint64_t>(n * 4); st_decode = w.take_status(n); st_lower = w.take_status(n); st_zero = w.take_status(n); end = w.used; }
+    static size_t bytes(size_t n) { return OprfFinalize(nullptr, n).end; }
+};
+struct OprfEval {                   // hash to curve -> DH_endo by the key -> encode -> hash
+    uint64_t* pts;                  // G(msg) as affine words: n x 8
+    uint64_t* shared;               // DH_endo's affine result: n x 8
+    uint64_t* u;                    // n x 8 words ON shared: dead once the map has run, before DH_endo writes there
+    uint64_t *keys, *e32;           // the key on n scalar rows, the evaluated element as 32 bytes: n x 4 words each
+    uint8_t* st_dh;
+    size_t end;
+    OprfEval(char* base, size_t n) { Carver w(base); pts = w.take<uint64_t>(n * 8); shared = w.take<uint64_t>(n * 8); u = shared; keys = w.take<uint64_t>(n * 4); e32 = w.take<uint64_t>(n * 4); st_dh = w.take_status(n); end = w.used; }
+    static size_t bytes(size_t n) { return OprfEval(nullptr, n).end; }
+};
 
 }  // namespace fq_work

@@ -529,6 +529,85 @@ class Engine:
         fn = self._lib.fourq_hash_to_curve_affine_batch_dev if affine else self._lib.fourq_hash_to_curve_batch_dev
         self._ck(fn(self._ctx, buf, dst_len, mode, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(out), n))
 
+    # ---- oblivious PRF (fourq_oprf_*: blind, evaluate, finalize and the key holder's direct evaluation, include/fourq_amd.h) -------
+    @staticmethod
+    def _key(key):
+        k = _host(key, None).ravel()
+        if k.size != 4:
+            raise ValueError("a key is one scalar of 4 words")
+        return k
+
+    def scalar_inv(self, scalars, out=None):
+        """1 / m_i mod N of every scalar (n, 4) -- any value below 2^256 -- as canonical words (n, 4); 0 where m_i = 0 mod N."""
+        s = _host(scalars, 4)
+        out = _out(out, len(s), 4)
+        self._ck(self._lib.fourq_scalar_inv_batch(self._ctx, _ptr(s), _ptr(out), len(s)))
+        return out
+
+    def set_scinv_group(self, k):
+        """TEST HOOK (fourq_ctx_set_scinv_group; needs FOURQ_DEBUG_ROUTES=1): 1, 8 or 16 elements per inversion chain, 0 = by batch size."""
+        self._ck(self._lib.fourq_ctx_set_scinv_group(self._ctx, int(k)))
+
+    def scalar_inv_dev(self, scalars, out, n):
+        self._ck(self._lib.fourq_scalar_inv_batch_dev(self._ctx, _ptr(scalars), _ptr(out), n))
+
+    def oprf_blind(self, msgs, blinds, lens=None, dst=b"", out=None, status=None):
+        """encode([r_i]G(msg_i)), G = hash_to_curve(mode "ro") under `dst`: ((n, 32) uint8, status).  status: 0 ok,
+        _lib.OPRF_BLIND_ZERO where r_i = 0 mod N (the row is zero then)."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        r = _host(blinds, 4)
+        m, stride, lens, msg_len = self._msgs(msgs, lens, len(r))
+        out, status = _out(out, len(r), 32, np.uint8), _out(status, len(r), None, np.uint8)
+        self._ck(self._lib.fourq_oprf_blind_batch(self._ctx, buf, dst_len, _ptr(m) if stride else None, stride, _ptr(lens), msg_len, _ptr(r), _ptr(out), _ptr(status), len(r)))
+        return out, status
+
+    def oprf_blind_dev(self, msgs, stride, lens, msg_len, blinds, out32, status, n, dst=b""):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_oprf_blind_batch_dev(self._ctx, buf, dst_len, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(blinds), _ptr(out32), _ptr(status), n))
+
+    def oprf_evaluate(self, key, blinded32, out=None, status=None):
+        """encode(DH_endo(key, decode(B_i))) with ONE key (4 words) for the batch: ((n, 32) uint8, status) -- dh_bytes with the key on
+        every row, status as dh_bytes."""
+        k, b = self._key(key), _host(blinded32, 32, np.uint8)
+        out, status = _out(out, len(b), 32, np.uint8), _out(status, len(b), None, np.uint8)
+        self._ck(self._lib.fourq_oprf_evaluate_batch(self._ctx, _ptr(k), _ptr(b), _ptr(out), _ptr(status), len(b)))
+        return out, status
+
+    def oprf_evaluate_dev(self, key_host, blinded32, out32, status, n):
+        self._ck(self._lib.fourq_oprf_evaluate_batch_dev(self._ctx, _ptr(self._key(key_host)), _ptr(blinded32), _ptr(out32), _ptr(status), n))
+
+    def oprf_finalize(self, msgs, blinds, evaluated32, lens=None, dst=b"", out=None, status=None):
+        """The PRF output of every row: SHA-512(E || msg || "Finalize" || dst || len(dst)) with E = encode([1 / r_i]decode(Z_i)):
+        ((n, 64) uint8, status).  status: 0 ok, 16 + decode status, _lib.OPRF_BLIND_ZERO."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        r, z = _host(blinds, 4), _host(evaluated32, 32, np.uint8)
+        if len(r) != len(z):
+            raise ValueError("blinds and evaluated elements differ in length")
+        m, stride, lens, msg_len = self._msgs(msgs, lens, len(r))
+        out, status = _out(out, len(r), 64, np.uint8), _out(status, len(r), None, np.uint8)
+        self._ck(self._lib.fourq_oprf_finalize_batch(self._ctx, buf, dst_len, _ptr(m) if stride else None, stride, _ptr(lens), msg_len, _ptr(r), _ptr(z), _ptr(out), _ptr(status),
+                                                     len(r)))
+        return out, status
+
+    def oprf_finalize_dev(self, msgs, stride, lens, msg_len, blinds, evaluated32, out64, status, n, dst=b""):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_oprf_finalize_batch_dev(self._ctx, buf, dst_len, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(blinds), _ptr(evaluated32), _ptr(out64),
+                                                         _ptr(status), n))
+
+    def oprf_eval(self, key, msgs, lens=None, dst=b"", out=None, status=None):
+        """The key holder's own evaluation, equal to oprf_finalize(oprf_blind, oprf_evaluate) for every blind: ((n, 64) uint8, status).
+        status: 0 ok, _lib.DH_NEUTRAL where key = 0 mod N."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        k = self._key(key)
+        m, stride, lens, msg_len = self._msgs(msgs, lens)
+        out, status = _out(out, len(m), 64, np.uint8), _out(status, len(m), None, np.uint8)
+        self._ck(self._lib.fourq_oprf_eval_batch(self._ctx, _ptr(k), buf, dst_len, _ptr(m) if stride else None, stride, _ptr(lens), msg_len, _ptr(out), _ptr(status), len(m)))
+        return out, status
+
+    def oprf_eval_dev(self, key_host, msgs, stride, lens, msg_len, out64, status, n, dst=b""):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_oprf_eval_batch_dev(self._ctx, _ptr(self._key(key_host)), buf, dst_len, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(out64), _ptr(status), n))
+
     def dh_exchange_dev(self, a_scalars, b_scalars, base_affine_host, table392_host, out_affine, status, n):
         base = _host(base_affine_host, None).ravel()
         t = None if table392_host is None else _host(table392_host, None).ravel()

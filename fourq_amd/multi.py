@@ -201,6 +201,36 @@ class MultiEngine:
         out = _out(out, len(m), 8) if affine else _out(out, len(m), 32, np.uint8)
         return self._sharded(lambda e, m, ln, o: e.hash_to_curve(m, ln, dst, mode, affine, out=o), [m, ln], [out])
 
+    # ---- oblivious PRF: rows are independent, the key and dst are replicated ------------------------------------------
+    @staticmethod
+    def _msg_rows(msgs, lens):
+        m = np.ascontiguousarray(msgs, dtype=np.uint8)
+        ln = np.full(len(m), m.shape[1], dtype=np.uint32) if lens is None else np.ascontiguousarray(lens, dtype=np.uint32).ravel()
+        return m, ln
+
+    def oprf_blind(self, msgs, blinds, lens=None, dst=b"", out=None, status=None):
+        (m, ln), r = self._msg_rows(msgs, lens), _host(blinds, 4)
+        self._same_len(m, ln, r)
+        return self._sharded(lambda e, m, ln, r, o, st: e.oprf_blind(m, r, ln, dst, out=o, status=st), [m, ln, r],
+                             [_out(out, len(r), 32, np.uint8), _out(status, len(r), None, np.uint8)])
+
+    def oprf_evaluate(self, key, blinded32, out=None, status=None):
+        b = _host(blinded32, 32, np.uint8)
+        return self._sharded(lambda e, b, o, st: e.oprf_evaluate(key, b, out=o, status=st), [b],
+                             [_out(out, len(b), 32, np.uint8), _out(status, len(b), None, np.uint8)])
+
+    def oprf_finalize(self, msgs, blinds, evaluated32, lens=None, dst=b"", out=None, status=None):
+        (m, ln), r, z = self._msg_rows(msgs, lens), _host(blinds, 4), _host(evaluated32, 32, np.uint8)
+        self._same_len(m, ln, r, z)
+        return self._sharded(lambda e, m, ln, r, z, o, st: e.oprf_finalize(m, r, z, ln, dst, out=o, status=st), [m, ln, r, z],
+                             [_out(out, len(r), 64, np.uint8), _out(status, len(r), None, np.uint8)])
+
+    def oprf_eval(self, key, msgs, lens=None, dst=b"", out=None, status=None):
+        m, ln = self._msg_rows(msgs, lens)
+        self._same_len(m, ln)
+        return self._sharded(lambda e, m, ln, o, st: e.oprf_eval(key, m, ln, dst, out=o, status=st), [m, ln],
+                             [_out(out, len(m), 64, np.uint8), _out(status, len(m), None, np.uint8)])
+
     # ---- wire format ----------------------------------------------------------------------------------------------
     def encode(self, points_affine, out=None):
         p = _host(points_affine, 8)

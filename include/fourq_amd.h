@@ -449,6 +449,62 @@ int fourq_hash_to_curve_affine_batch(fourq_ctx *ctx, const uint8_t *dst, size_t 
 int fourq_hash_to_curve_affine_batch_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, int mode,
                                          const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint64_t *out_affine, size_t n);
 
+/* ---- oblivious PRF: blind, evaluate, finalize -- what a caller does with a password hashed to a point ---------------------------------------
+ * The 2HashDH construction (the core of OPAQUE, Privacy Pass and PSI) on top of "bytes to a point" above.  With G(msg) = hash to curve in
+ * RO mode under `dst` as an affine point, N the group order, r the client's blind and k the server's key (scalars: 4 words, ANY value
+ * in [0, 2^256), as MUL_endo and DH_endo take them):
+ *   blind(msg, r)             out32 = encode(R1toAffine(MUL_endo(r, AffineToR1(G(msg)))))                                     client
+ *   evaluate(k, blinded32)    out32 = encode(DH_endo(k, decode(blinded32)))  = fourq_dh_endo_bytes_batch with k on every row  server
+ *   finalize(msg, r, ev32)    E = encode(R1toAffine(MUL_endo(1 / r mod N, AffineToR1(decode(ev32)))));  out64 = F(E, msg)     client
+ *   eval(k, msg)              out64 = F(encode(DH_endo(k, G(msg))), msg)            the key holder's own evaluation; equals
+ *                             finalize(msg, r, evaluate(k, blind(msg, r))) for every r that is not 0 mod N
+ *   F(E, msg) = SHA-512(E || msg || "Finalize" || dst || I2OSP(len(dst), 1))        E: 32 bytes
+ * Suite.  The suite is this library's own: RFC 9497 registers no FourQ suite, and no other implementation was available to check against;
+ * the yardstick is the CPU restatement tests/oprf_ref.py and the fixture tests/golden/oprf.json made with the reference's point functions.
+ * Field order of F.  RFC 9497's Finalize hashes I2OSP(len(input), 2) || input || I2OSP(len(E), 2) || E || "Finalize".  Ours puts the
+ * fixed-size per-row field first -- it sits in registers as a 32-byte prefix and the row behind it keeps its alignment for vector loads --
+ * and the part that is the same for every row last, where it travels by value in the kernel arguments.  The encoding is still injective:
+ * the first 32 bytes are E, the LAST byte gives the length of dst and so of the whole tail, and what lies between is msg.
+ * Server multiplication.  DH_endo multiplies by 392 k (its cofactor clearing, curve4q.py:446-462): a blinded element with a small-order
+ * component is therefore harmless, and the x392 commutes with the blind because G(msg) already lies in the subgroup of order N.
+ * Finalize checks nothing beyond decoding, like MUL_*.  There is no RNG in this library: blinds come from the caller, uniformly random
+ * in [1, N) for the protocol to hide anything.  The blind and its inverse meet no branch and no address that depends on their value in
+ * the inversion (fixed public exponent N - 2, masked selects); in the ladder that holds under fourq_ctx_set_ct_select, as everywhere.
+ * Messages and `dst` follow fourq_sha512_batch and fourq_hash_to_curve_batch exactly: rows of `stride` bytes, lens or msg_len,
+ * FOURQ_SIG_MAX_MSG on the host-pointer calls (FOURQ_ERR_INVALID above it), the _dev calls clamp a length to `stride`; dst is
+ * 1..FOURQ_H2C_MAX_DST bytes and, like `key`, a HOST pointer in both flavours (both travel in kernel arguments: nothing is staged, and
+ * after fourq_ctx_reserve(ctx, n) the _dev calls of at most n rows only enqueue and can be captured).  _dev array pointers are 16-byte
+ * aligned (status need not be).
+ * status, one byte per row; the row of out32 / out64 is all zero unless it is 0.  A bad row never affects its neighbours.
+ *   blind      FOURQ_OPRF_BLIND_ZERO when r = 0 (mod N); else FOURQ_SIG_MSG_CLAMPED (_dev only) when the row's length was clamped
+ *   evaluate   exactly what fourq_dh_endo_bytes_batch reports (FOURQ_DH_*, FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_*)
+ *   finalize   FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_* when ev32 does not decode; else FOURQ_OPRF_BLIND_ZERO; else FOURQ_SIG_MSG_CLAMPED
+ *   eval       FOURQ_DH_NEUTRAL when k = 0 (mod N); else FOURQ_SIG_MSG_CLAMPED
+ * Work buffer: each call's intermediates (work_layout.h, Oprf*) stay below the signature check's, so fourq_ctx_reserve does not grow. */
+#define FOURQ_OPRF_BLIND_ZERO 48      /* status: the blind is 0 mod N (it has no inverse; [0]G is the neutral point for every msg) */
+int fourq_oprf_blind_batch(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *msgs, size_t stride, const uint32_t *lens,
+                           size_t msg_len, const uint64_t *blinds, uint8_t *out32, uint8_t *status, size_t n);
+int fourq_oprf_blind_batch_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *msgs, size_t stride, const uint32_t *lens,
+                               size_t msg_len, const uint64_t *blinds, uint8_t *out32, uint8_t *status, size_t n);
+/* key: HOST pointer, 4 words, one key for the whole batch */
+int fourq_oprf_evaluate_batch(fourq_ctx *ctx, const uint64_t *key, const uint8_t *blinded32, uint8_t *out32, uint8_t *status, size_t n);
+int fourq_oprf_evaluate_batch_dev(fourq_ctx *ctx, const uint64_t *key, const uint8_t *blinded32, uint8_t *out32, uint8_t *status, size_t n);
+int fourq_oprf_finalize_batch(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *msgs, size_t stride, const uint32_t *lens,
+                              size_t msg_len, const uint64_t *blinds, const uint8_t *evaluated32, uint8_t *out64, uint8_t *status, size_t n);
+int fourq_oprf_finalize_batch_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *msgs, size_t stride, const uint32_t *lens,
+                                  size_t msg_len, const uint64_t *blinds, const uint8_t *evaluated32, uint8_t *out64, uint8_t *status, size_t n);
+int fourq_oprf_eval_batch(fourq_ctx *ctx, const uint64_t *key, const uint8_t *dst, size_t dst_len, const uint8_t *msgs, size_t stride,
+                          const uint32_t *lens, size_t msg_len, uint8_t *out64, uint8_t *status, size_t n);
+int fourq_oprf_eval_batch_dev(fourq_ctx *ctx, const uint64_t *key, const uint8_t *dst, size_t dst_len, const uint8_t *msgs, size_t stride,
+                              const uint32_t *lens, size_t msg_len, uint8_t *out64, uint8_t *status, size_t n);
+/* out[i] = 1 / scalars[i] mod N, n x 4 words in and out, canonical; scalars: ANY value in [0, 2^256).  No status: a scalar that is
+ * 0 mod N gives 0 (and touches no neighbour, although one Fermat chain a^(N-2) serves up to 16 elements: Montgomery's trick inside a lane). */
+int fourq_scalar_inv_batch(fourq_ctx *ctx, const uint64_t *scalars, uint64_t *out, size_t n);
+int fourq_scalar_inv_batch_dev(fourq_ctx *ctx, const uint64_t *scalars, uint64_t *out, size_t n);
+/* TEST HOOK: k = 1, 8 or 16 elements per Fermat chain in fourq_scalar_inv_* and fourq_oprf_finalize_* whatever the batch size, 0 = chosen
+ * by batch size again (results do not depend on it).  FOURQ_ERR_INVALID unless the process runs with FOURQ_DEBUG_ROUTES=1. */
+int fourq_ctx_set_scinv_group(fourq_ctx *ctx, int k);
+
 /* ---- primitives (one reference function per op, batched) --------------------------------------
  * Used by the Python mirror of the reference's helper API (GFp.*, GFp2.*, DBL, ADD, phi, ...) and by
  * the parity tests to check every layer of the path on the GPU.  in/out are HOST pointers;
@@ -491,7 +547,8 @@ enum fourq_prim {
     FOURQ_SC_MUL = 69,          /* a[4] b[4] -> [4]: a b mod N */
     /* the digits of FOURQ_SC_RECODE as the fused ladders read them: step i (0..63) is nibble i % 8 of word i / 8, bits 0..2 the digit,
      * bit 3 set when the step subtracts (sign bit 0) */
-    FOURQ_SC_RECODE_NIBBLES = 70 /* v[4] = decompose(m) -> [9]: the eight 32-bit words, one per output word, then digit 64 */
+    FOURQ_SC_RECODE_NIBBLES = 70, /* v[4] = decompose(m) -> [9]: the eight 32-bit words, one per output word, then digit 64 */
+    FOURQ_SC_INV = 71           /* a[4] -> [4]: 1 / a mod N, canonical; 0 when a = 0 (mod N) */
 };
 int fourq_prim_words(int op, size_t *in_words, size_t *out_words);
 int fourq_prim_batch(fourq_ctx *ctx, int op, const uint64_t *in, uint64_t *out, size_t n);
