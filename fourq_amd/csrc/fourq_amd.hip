@@ -451,12 +451,11 @@ const PrimShape* find_prim(int op) {
 }  // namespace
 
 // ====================================================================================== C ABI
-// Which host-array call this is, for the measured planner inputs (fourq_ctx::plan_kt)
-enum PipeRouteId { PR_MUL_VAR = 0, PR_MUL_FIX = 2, PR_DH_VAR = 4, PR_DH_FIX = 6, PR_MIXED = 8, PR_COMB = 9, PR_ENCODE = 10, PR_DECODE = 11, PR_DHB_VAR = 12,
-                   PR_DHB_FIX = 14, PR_AFF = 16, PR_BYTES = 18, PR_EXCH = 20, PR_EXCH_COMB = 22, PR_DOUBLE_AFF = 23, PR_DOUBLE_BYTES = 24, PR_DOUBLE_VERIFY = 25,
-                   PR_SHA512 = 26, PR_SIG_KEYGEN = 27, PR_SIG_SIGN = 28, PR_SIG_VERIFY = 29, PR_H2F = 30, PR_H2C_MAP = 31, PR_H2C = 32, PR_H2C_AFFINE = 34, PR_OPRF_BLIND = 36,
-                   PR_OPRF_EVALUATE = 37, PR_OPRF_FINALIZE = 38, PR_OPRF_EVAL = 39, PR_SC_INV = 40, PR_COUNT = 41 };       // + algo or mode (0 / 1) where two follow each other
-static_assert(PR_H2C_AFFINE + FOURQ_H2C_NU < PR_COUNT && FOURQ_H2C_RO == 0 && FOURQ_H2C_NU == 1, "the highest route id plus its mode offset must fit fourq_ctx::plan_kt");
+// Which host-array call this is, for the measured planner inputs (fourq_ctx::plan_kt).  A call with two flavours that are timed apart
+// (ENDO / WINDOWED, RO / NU, without / with table392) names the flavour in PipeRoute::variant, 0 or 1.
+enum PipeRouteId { PR_MUL_VAR, PR_MUL_FIX, PR_DH_VAR, PR_DH_FIX, PR_MIXED, PR_COMB, PR_ENCODE, PR_DECODE, PR_DHB_VAR, PR_DHB_FIX, PR_AFF, PR_BYTES, PR_EXCH, PR_EXCH_COMB,
+                   PR_DOUBLE_AFF, PR_DOUBLE_BYTES, PR_DOUBLE_VERIFY, PR_SHA512, PR_SIG_KEYGEN, PR_SIG_SIGN, PR_SIG_VERIFY, PR_H2F, PR_H2C_MAP, PR_H2C, PR_H2C_AFFINE,
+                   PR_OPRF_BLIND, PR_OPRF_EVALUATE, PR_OPRF_FINALIZE, PR_OPRF_EVAL, PR_SC_INV, PR_COUNT };
 constexpr int PIPE_SLOTS_MAX = 6;
 struct fourq_ctx {
     int device = 0;
@@ -503,9 +502,9 @@ struct fourq_ctx {
     bool pipe_host_wait = false;   // FOURQ_PIPE_HOST_WAIT=1 (test hook): the host waits for a slot's last use before refilling it, as rounds 2-4 did
     bool host_timing = false;      // fourq_ctx_set_host_timing: time the chunk copies with HIP events (h2d_ms / d2h_ms of fourq_host_stats)
     // Measured planner inputs (round 6): every multi-chunk host-array call times ONE middle chunk (six events, `probe_ticks`) and leaves the
-    // kernel time per element of its route -- per selection mode -- and the link's rate each way here; the next call of that route is planned
-    // with them.  0 = not measured yet: the first call plans with the KT_* guesses (x KT_CT_GUESS in constant-time mode) and 48 GB/s.
-    double plan_kt[PR_COUNT][2] = {};
+    // kernel time per element of its route -- per variant and selection mode -- and the link's rate each way here; the next call of that route
+    // is planned with them.  0 = not measured yet: the first call plans with the KT_* guesses (x KT_CT_GUESS in constant-time mode) and 48 GB/s.
+    double plan_kt[PR_COUNT][2][2] = {};
     double plan_link_in = 0, plan_link_out = 0;     // bytes per nanosecond
     hipEvent_t probe_ticks[6] = {};
     bool fused_io = true;          // FOURQ_FUSED_IO=0 (test hook): the affine / encoded flavours of MUL_* always through lift + full R1 rows, as round 5
@@ -816,17 +815,11 @@ int grow(fourq_ctx* c, char** buf, size_t* have, size_t want, bool pinned) {
 // Intermediates of the protocol-level calls: each call carves c->work by its layout in work_layout.h and asks for that layout's bytes(n)
 int ensure_work(fourq_ctx* c, size_t bytes) { return grow(c, &c->work, &c->work_bytes, bytes + bytes / 4, false); }
 // What a host-array call sizes for its largest chunk BEFORE the first chunk is enqueued (PipeReserve; ensure_proj is one of them as it stands):
-// the projective planes where the _dev call behind it defers a normalisation, and that call's layout of the work buffer
-int reserve_work(fourq_ctx* c, size_t big, bool proj, size_t bytes) {
-    if (int r = proj ? ensure_proj(c, big) : FOURQ_OK) return r;
-    return ensure_work(c, bytes);
+// the projective planes where the _dev call behind it defers a normalisation (Layout::planes), and that call's layout of the work buffer
+template <class Layout> int reserve_for(fourq_ctx* c, size_t big) {
+    if (int r = Layout::planes ? ensure_proj(c, big) : FOURQ_OK) return r;
+    return ensure_work(c, Layout::bytes(big));
 }
-int reserve_dh_bytes(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::DhBytes::bytes(big)); }
-int reserve_exchange(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::Exchange::bytes(big)); }
-int reserve_mul_rows(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::MulRows::bytes(big)); }
-int reserve_double_mul(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::DoubleMul::bytes(big)); }      // also the signature check's
-int reserve_sig(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::Sig::bytes(big)); }
-int reserve_h2c(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::H2c::bytes(big)); }
 
 int ensure_ticks(fourq_ctx* c, size_t count) {
     while (c->ticks.size() < count) {
@@ -839,13 +832,23 @@ int ensure_ticks(fourq_ctx* c, size_t count) {
 
 using ChunkLaunch = std::function<int(char* const* in_dev, char* const* out_dev, size_t m)>;
 
-// Which call this is (PipeRouteId), and the guess of its kernel time per element for the context's first call of it
-struct PipeRoute { int id; double kt_guess; };
+// Which call this is (PipeRouteId and its variant, 0 or 1), and the guess of its kernel time per element for the context's first call of it
+struct PipeRoute { int id, variant; double kt_guess; };
+// Kernel time per element of each route in nanoseconds, device-resident at 2^20 elements (profiles/r04_perf_probe.txt, tools/perf_probe.py).
+// They only size the chunks of the host-array calls (pipeline_plan.h): a kernel slower than its figure (constant-time mode, a slower box)
+// gets chunks smaller than it could have had, one faster by more than the plan's 15 % margin a short stall on the first chunks.
+constexpr double KT_ENDO_VAR = 4.63, KT_WIN_VAR = 8.18, KT_DH_VAR = 4.90, KT_ENDO_FIXED = 3.58, KT_WIN_FIXED = 7.65, KT_DH_FIXED = 3.65, KT_COMB = 1.09,
+                 KT_LIFT_LOWER = 0.10, KT_CODEC = 0.30, KT_DECODE = 0.25, KT_ENCODE = 0.05;
+constexpr double KT_DOUBLE = KT_COMB + KT_ENDO_VAR + KT_LIFT_LOWER;
+// ... and first-call guesses without a measurement behind them: one 128-byte block of SHA-512 per element (~5 000 VALU instructions); one
+// Elligator map (four GF(p) exponentiations' worth); one inversion modulo N (a Fermat chain is about 1.2 ladders' worth of instructions,
+// shared by 8 elements)
+constexpr double KT_SHA_BLOCK = 0.05, KT_ELL2 = 0.20, KT_SCINV = 0.70;
 constexpr double KT_CT_GUESS = 1.3;                 // constant-time selection: x 1.07 - 1.5 by route until the context has measured it
 using PipeReserve = int (*)(fourq_ctx* c, size_t big);  // sizes the context's intermediates for the largest chunk BEFORE the first chunk is enqueued
 int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch, size_t chunk_bounce, PipeReserve reserve);
 // `chunk`: elements of one kernel generation of the route the call takes; `ns_per_elem`: that route's kernel time per element (the
-// KT_* constants below: what sizes the chunks is the ratio of kernel time to copy time, pipeline_plan.h).  `chunk_bounce` (0 = `chunk`):
+// KT_* constants above: what sizes the chunks is the ratio of kernel time to copy time, pipeline_plan.h).  `chunk_bounce` (0 = `chunk`):
 // the uniform chunk of a call from PAGEABLE arrays -- its pace is the host's bounce copies (and, where the call allocates its result, the
 // page faults of 160 fresh bytes per element), not the link: such calls keep the chunk shape they were measured with in rounds 2-4
 // (cfg3's call, result array reused: 10.3-10.4 ms at 2^20 then and now; profiles/r02_host_api.txt, profiles/r05_pipeline.txt).
@@ -939,8 +942,8 @@ int pipe_single_chunk(const PipeCall& p, const SlotLayout& s, fourq_host_stats s
 fq_plan::Rates plan_rates(const fourq_ctx* c, PipeRoute route, fourq_host_stats* st) {
     const int mode = c->ct ? 1 : 0;
     fq_plan::Rates rates;
-    const bool measured = c->plan_measure && c->plan_kt[route.id][mode] > 0;
-    rates.ns_per_elem = measured ? c->plan_kt[route.id][mode] : route.kt_guess * (c->ct ? KT_CT_GUESS : 1.0);
+    const bool measured = c->plan_measure && c->plan_kt[route.id][route.variant][mode] > 0;
+    rates.ns_per_elem = measured ? c->plan_kt[route.id][route.variant][mode] : route.kt_guess * (c->ct ? KT_CT_GUESS : 1.0);
     rates.link_in = c->plan_measure && c->plan_link_in > 0 ? c->plan_link_in : fq_plan::LINK_BYTES_PER_NS;
     rates.link_out = c->plan_measure && c->plan_link_out > 0 ? c->plan_link_out : fq_plan::LINK_BYTES_PER_NS;
     st->planned_kernel_ns_per_elem = rates.ns_per_elem; st->planned_link_in_gbs = rates.link_in; st->planned_link_out_gbs = rates.link_out;
@@ -956,12 +959,12 @@ int read_probe(fourq_ctx* c, PipeRoute route, double m, bool link, size_t bytes_
     HIP_TRY(c, hipEventElapsedTime(&t_in, c->probe_ticks[0], c->probe_ticks[1]));
     HIP_TRY(c, hipEventElapsedTime(&t_k, c->probe_ticks[2], c->probe_ticks[3]));
     HIP_TRY(c, hipEventElapsedTime(&t_out, c->probe_ticks[4], c->probe_ticks[5]));
-    if (t_k > 0) c->plan_kt[route.id][mode] = (double)t_k * 1e6 / m;
+    if (t_k > 0) c->plan_kt[route.id][route.variant][mode] = (double)t_k * 1e6 / m;
     if (link) {
         if (t_in > 0 && bytes_in) c->plan_link_in = m * (double)bytes_in / ((double)t_in * 1e6);
         if (t_out > 0 && bytes_out) c->plan_link_out = m * (double)bytes_out / ((double)t_out * 1e6);
     }
-    st->measured_kernel_ns_per_elem = c->plan_kt[route.id][mode];
+    st->measured_kernel_ns_per_elem = c->plan_kt[route.id][route.variant][mode];
     return FOURQ_OK;
 }
 // Timing (on request): six events per chunk -- around its copy in, its kernels, its copy out -- for the first TIMED_MAX chunks; a call of
@@ -1106,7 +1109,7 @@ int pipe_chunked(const PipeCall& p, size_t chunk, PipeRoute route, PipeReserve r
     return FOURQ_OK;
 }
 int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeArray* out, int n_out, size_t n, size_t chunk, PipeRoute route, const ChunkLaunch& launch, size_t chunk_bounce, PipeReserve reserve) {
-    if (n_in > PIPE_MAX_ARRAYS || n_out > PIPE_MAX_ARRAYS || chunk == 0 || route.id < 0 || route.id >= PR_COUNT) return FOURQ_ERR_INVALID;
+    if (n_in > PIPE_MAX_ARRAYS || n_out > PIPE_MAX_ARRAYS || chunk == 0 || route.id < 0 || route.id >= PR_COUNT || (route.variant & ~1)) return FOURQ_ERR_INVALID;
     bool is_pin_in[PIPE_MAX_ARRAYS], is_pin_out[PIPE_MAX_ARRAYS], any_pageable = false;
     for (int i = 0; i < n_in; i++) { is_pin_in[i] = is_pinned(in[i].src); any_pageable |= !is_pin_in[i]; }
     for (int i = 0; i < n_out; i++) { is_pin_out[i] = is_pinned(out[i].dst); any_pageable |= !is_pin_out[i]; }
@@ -1126,39 +1129,95 @@ int run_pipeline_inner(fourq_ctx* c, const PipeArray* in, int n_in, const PipeAr
     return s.bytes <= ZERO_COPY_BYTES && c->host_zero_copy ? pipe_zero_copy(p, s, st) : pipe_single_chunk(p, s, st);
 }
 
-// chunk of a variable-base host-pointer batch: whole generations of the fused kernels that will run it
-size_t pipe_chunk(const fourq_ctx* c) { return c->lanes; }
-// Kernel time per element of each route in nanoseconds, device-resident at 2^20 elements (profiles/r04_perf_probe.txt, tools/perf_probe.py).
-// They only size the chunks of the host-array calls (pipeline_plan.h): a kernel slower than its figure (constant-time mode, a slower box)
-// gets chunks smaller than it could have had, one faster by more than the plan's 15 % margin a short stall on the first chunks.
-constexpr double KT_ENDO_VAR = 4.63, KT_WIN_VAR = 8.18, KT_DH_VAR = 4.90, KT_ENDO_FIXED = 3.58, KT_WIN_FIXED = 7.65, KT_DH_FIXED = 3.65, KT_COMB = 1.09,
-                 KT_LIFT_LOWER = 0.10, KT_CODEC = 0.30, KT_DECODE = 0.25, KT_ENCODE = 0.05;
-int mul_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points, const uint64_t* table, uint64_t* out, size_t n) {
-    if (!c || !scalars || !out || (!points && !table) || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+// ---- one host-array call, described once ------------------------------------------------------------------------------------------
+// A call states its arrays as (pointer, bytes per element), its route and first-call guess, its chunk unit, what it reserves, and what to
+// launch on one chunk; host_call owns the argument contract (include/fourq_amd.h), the lock and the pipeline.
+// An input that is absent from the chunks: one of stride 0 (the message matrix of empty messages), and a NULL one that MAY_BE_NULL (lens).
+constexpr bool MAY_BE_NULL = true;
+struct HostIn { const void* p; size_t stride; bool may_be_null = false; };
+struct HostOut { void* p; size_t stride; };
+// The chunk units are functions of the context: host_call evaluates them once it has refused a NULL one.
+using ChunkUnit = size_t (*)(const fourq_ctx*);
+size_t pipe_chunk(const fourq_ctx* c) { return c->lanes; }              // variable base: whole generations of the fused kernels that will run it
+size_t unit_w4(const fourq_ctx* c) { return c->lanes_w4; }              // one generation of the 128-VGPR kernels
+// fixed base: the LDS ladders hold two waves per SIMD, so HALF of lanes_w4 is one generation of theirs -- the unit that sizes the first
+// chunk's copy in and the last chunk's copy out (cfg3's call: 160 B out per element, 21 MB instead of 42 behind the last kernel)
+size_t unit_w4_half(const fourq_ctx* c) { return c->lanes_w4 / 2; }
+size_t unit_w4_x4(const fourq_ctx* c) { return 4 * c->lanes_w4; }       // the kernels that only stream: encode, SHA-512, hash to field
+// one pass of the work-queue kernel's 4 x CUs waves over 64-element items is `lanes` elements: the unit that lets the copies of a
+// config-5-sized call (2 x lanes) overlap its kernels; raw R1 in and out keeps the chunks at that size (pipeline_plan.h)
+size_t unit_mixed(const fourq_ctx* c) { return c->mixed_round < c->lanes ? c->mixed_round : c->lanes; }
+size_t unit_mixed_round(const fourq_ctx* c) { return c->mixed_round; }
+size_t unit_scinv(const fourq_ctx* c) { return 16 * (size_t)c->cus * BLOCK; }
+// chunk of a call that carries a message matrix: the route's own chunk, cut down (to no less than one block's worth of rows) where rows of
+// `stride` bytes would make a pipeline slot larger than 64 MiB
+size_t sig_chunk(size_t chunk, size_t stride) {
+    const size_t cap = stride ? (size_t)(64u << 20) / stride : chunk;
+    if (cap < chunk) chunk = cap < (size_t)BLOCK ? (size_t)BLOCK : cap;
+    return chunk;
+}
+struct HostCall {
+    HostIn in[PIPE_MAX_ARRAYS];
+    HostOut out[PIPE_MAX_ARRAYS];
+    PipeRoute route;
+    ChunkUnit unit, unit_pageable;      // unit_pageable (or nullptr): run_pipeline's chunk_bounce
+    PipeReserve reserve;                // reserve_for<the work layout of the _dev call>, ensure_proj, or nullptr
+    bool ok = true;                     // the call's own predicates: a required pointer that is no array, sig_msgs_host_ok, h2c_args_ok
+    size_t msg_stride = 0;              // the row of a message matrix: caps the chunk (sig_chunk)
+};
+// One chunk as the launch sees it: the arrays by their position in HostCall::in / ::out, nullptr for an absent input
+struct Chunk {
+    char* const* din; char* const* dout; const int* slot; size_t m;
+    template <class T> const T* in(int i) const { return slot[i] < 0 ? nullptr : (const T*)din[slot[i]]; }
+    template <class T> T* out(int i) const { return (T*)dout[i]; }
+};
+struct HostArrays { PipeArray in[PIPE_MAX_ARRAYS] = {}, out[PIPE_MAX_ARRAYS] = {}; int n_in = 0, n_out = 0, slot[PIPE_MAX_ARRAYS]; };
+// The argument contract: FOURQ_ERR_INVALID for a NULL context, a NULL array that may not be, a failed predicate or n > FOURQ_MAX_BATCH
+int host_arrays(const fourq_ctx* c, size_t n, const HostCall& d, HostArrays* a) {
+    if (!c || !d.ok || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    for (int i = 0; i < PIPE_MAX_ARRAYS; i++) {
+        const HostIn& x = d.in[i];
+        const bool present = x.stride && (x.p || !x.may_be_null);
+        if (present && !x.p) return FOURQ_ERR_INVALID;
+        a->slot[i] = present ? a->n_in : -1;
+        if (present) { a->in[a->n_in].src = (const char*)x.p; a->in[a->n_in++].stride = x.stride; }
+    }
+    for (; a->n_out < PIPE_MAX_ARRAYS && d.out[a->n_out].stride; a->n_out++) {
+        if (!d.out[a->n_out].p) return FOURQ_ERR_INVALID;
+        a->out[a->n_out].dst = (char*)d.out[a->n_out].p; a->out[a->n_out].stride = d.out[a->n_out].stride;
+    }
+    return FOURQ_OK;
+}
+// In this order: argument errors; n == 0 is FOURQ_OK with nothing touched; the lock; `prepare` once per call (stage_comb: the chunks
+// then pass comb == NULL, "the staged one", and the table is compared once, not once per chunk); the chunks.
+template <class Prepare, class Launch> int host_call(fourq_ctx* c, size_t n, const HostCall& d, Prepare&& prepare, Launch&& launch) {
+    HostArrays a;
+    if (int rc = host_arrays(c, n, d, &a)) return rc;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points, nullptr, 160 } };
-    PipeArray o[1] = { { nullptr, (char*)out, 160 } };
-    // fixed base: the LDS ladders hold two waves per SIMD, so HALF of lanes_w4 is one generation of theirs -- the unit that sizes the first
-    // chunk's copy in and the last chunk's copy out (cfg3's call: 160 B out per element, 21 MB instead of 42 behind the last kernel)
-    const size_t unit = points ? pipe_chunk(c) : c->lanes_w4 / 2;
-    const double kt = points ? (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) : (algo == ENDO ? KT_ENDO_FIXED : KT_WIN_FIXED);
-    return run_pipeline(c, in, points ? 2 : 1, o, 1, n, unit, PipeRoute{ (points ? PR_MUL_VAR : PR_MUL_FIX) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return mul_dev(c, algo, (const uint64_t*)di[0], points ? (const uint64_t*)di[1] : nullptr, table, (uint64_t*)dout[0], nullptr, m);
-    }, points ? pipe_chunk(c) : c->lanes_w4);
+    if (int rc = prepare()) return rc;
+    return run_pipeline(c, a.in, a.n_in, a.out, a.n_out, n, sig_chunk(d.unit(c), d.msg_stride), d.route,
+                        [&](char* const* din, char* const* dout, size_t m) { return launch(Chunk{ din, dout, a.slot, m }); },
+                        d.unit_pageable ? d.unit_pageable(c) : 0, d.reserve);
+}
+template <class Launch> int host_call(fourq_ctx* c, size_t n, const HostCall& d, Launch&& launch) {
+    return host_call(c, n, d, [] { return FOURQ_OK; }, launch);
+}
+
+int mul_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points, const uint64_t* table, uint64_t* out, size_t n) {
+    const int v = algo == ENDO ? 0 : 1;
+    const HostCall variable = { { { scalars, 32 }, { points, 160 } }, { { out, 160 } }, { PR_MUL_VAR, v, v ? KT_WIN_VAR : KT_ENDO_VAR }, pipe_chunk, pipe_chunk };
+    const HostCall fixed = { { { scalars, 32 } }, { { out, 160 } }, { PR_MUL_FIX, v, v ? KT_WIN_FIXED : KT_ENDO_FIXED }, unit_w4_half, unit_w4, nullptr, table != nullptr };
+    return host_call(c, n, points ? variable : fixed, [&](const Chunk& k) {
+        return mul_dev(c, algo, k.in<uint64_t>(0), k.in<uint64_t>(1), table, k.out<uint64_t>(0), nullptr, k.m);
+    });
 }
 int dh_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points, const uint64_t* table, uint64_t* out,
             uint8_t* status, size_t n) {
-    if (!c || !scalars || !points || !out || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points, nullptr, 64 } };
-    PipeArray o[2] = { { nullptr, (char*)out, 64 }, { nullptr, (char*)status, 1 } };
-    const size_t unit = table ? c->lanes_w4 / 2 : pipe_chunk(c);
-    const double kt = table ? KT_DH_FIXED : (algo == ENDO ? KT_DH_VAR : KT_WIN_VAR + 0.3);
-    return run_pipeline(c, in, 2, o, 2, n, unit, PipeRoute{ (table ? PR_DH_FIX : PR_DH_VAR) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return dh_dev(c, algo, (const uint64_t*)di[0], (const uint64_t*)di[1], table, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    }, table ? c->lanes_w4 : pipe_chunk(c), ensure_proj);
+    const int v = algo == ENDO ? 0 : 1;
+    HostCall d = { { { scalars, 32 }, { points, 64 } }, { { out, 64 }, { status, 1 } }, { PR_DH_VAR, v, v ? KT_WIN_VAR + 0.3 : KT_DH_VAR }, pipe_chunk, pipe_chunk, ensure_proj };
+    if (table) { d.route = { PR_DH_FIX, v, KT_DH_FIXED }; d.unit = unit_w4_half; d.unit_pageable = unit_w4; }
+    return host_call(c, n, d, [&](const Chunk& k) { return dh_dev(c, algo, k.in<uint64_t>(0), k.in<uint64_t>(1), table, k.out<uint64_t>(0), k.out<uint8_t>(1), k.m); });
 }
 
 int table_host(fourq_ctx* c, int algo, const uint64_t* p_r1, uint64_t* table) {
@@ -1354,9 +1413,7 @@ FQ_API int fourq_ctx_reserve(fourq_ctx* c, size_t n) {
     if (!c || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
     CtxGuard g(c);
     if (int rc = ensure_proj(c, n)) return rc;
-    using namespace fq_work;
-    return ensure_work(c, std::max({ DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n), Msm::bytes(n),
-                                     OprfBlind::bytes(n), OprfEvaluate::bytes(n), OprfFinalize::bytes(n), OprfEval::bytes(n) }));
+    return ensure_work(c, fq_work::All::max_bytes(n));
 }
 FQ_API int fourq_ctx_lanes(const fourq_ctx* c, size_t* lanes) {
     if (!c || !lanes) return FOURQ_ERR_INVALID;
@@ -1465,17 +1522,10 @@ FQ_API int fourq_mul_endo_mixed_batch_dev(fourq_ctx* c, const uint64_t* s, const
 }
 FQ_API int fourq_mul_endo_mixed_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint8_t* flags,
                                       const uint64_t* table, uint64_t* o, size_t n) {
-    if (!c || !s || !p || !flags || !table || !o || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[3] = { { (const char*)s, nullptr, 32 }, { (const char*)p, nullptr, 160 }, { (const char*)flags, nullptr, 1 } };
-    PipeArray out[1] = { { nullptr, (char*)o, 160 } };
-    // one pass of the work-queue kernel's 4 x CUs waves over 64-element items is `lanes` elements: the unit that lets the copies of a
-    // config-5-sized call (2 x lanes) overlap its kernels; raw R1 in and out keeps the chunks at that size (pipeline_plan.h)
-    const size_t unit = c->mixed_round < c->lanes ? c->mixed_round : c->lanes;
-    return run_pipeline(c, in, 3, out, 1, n, unit, PipeRoute{ PR_MIXED, KT_ENDO_VAR }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_mul_endo_mixed_batch_dev(c, (const uint64_t*)di[0], (const uint64_t*)di[1], (const uint8_t*)di[2], table, (uint64_t*)dout[0], m);
-    }, c->mixed_round);
+    const HostCall d = { { { s, 32 }, { p, 160 }, { flags, 1 } }, { { o, 160 } }, { PR_MIXED, 0, KT_ENDO_VAR }, unit_mixed, unit_mixed_round, nullptr, table != nullptr };
+    return host_call(c, n, d, [&](const Chunk& k) {
+        return fourq_mul_endo_mixed_batch_dev(c, k.in<uint64_t>(0), k.in<uint64_t>(1), k.in<uint8_t>(2), table, k.out<uint64_t>(0), k.m);
+    });
 }
 
 FQ_API int fourq_dh_endo_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, const uint64_t* t, uint64_t* o, uint8_t* st, size_t n) { return dh_host(c, ENDO, s, p, t, o, st, n); }
@@ -1571,15 +1621,9 @@ FQ_API int fourq_comb_mul_batch_dev(fourq_ctx* c, const uint64_t* scalars, const
     return FOURQ_OK;
 }
 FQ_API int fourq_comb_mul_batch(fourq_ctx* c, const uint64_t* scalars, const uint64_t* comb, uint64_t* out, uint8_t* status, size_t n) {
-    if (!c || !scalars || !out || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;                                        // compared once, not once per chunk
-    comb = nullptr;
-    PipeArray in[1] = { { (const char*)scalars, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)out, 64 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 1, o, 2, n, c->lanes_w4, PipeRoute{ PR_COMB, KT_COMB }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_comb_mul_batch_dev(c, (const uint64_t*)di[0], comb, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
+    const HostCall d = { { { scalars, 32 } }, { { out, 64 }, { status, 1 } }, { PR_COMB, 0, KT_COMB }, unit_w4 };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
+        return fourq_comb_mul_batch_dev(c, k.in<uint64_t>(0), nullptr, k.out<uint64_t>(0), k.out<uint8_t>(1), k.m);
     });
 }
 
@@ -1600,24 +1644,12 @@ FQ_API int fourq_decode_batch_dev(fourq_ctx* c, const uint8_t* in32, uint64_t* a
     return FOURQ_OK;
 }
 FQ_API int fourq_encode_batch(fourq_ctx* c, const uint64_t* affine, uint8_t* out32, size_t n) {
-    if (!c || !affine || !out32 || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[1] = { { (const char*)affine, nullptr, 64 } };
-    PipeArray o[1] = { { nullptr, (char*)out32, 32 } };
-    return run_pipeline(c, in, 1, o, 1, n, 4 * c->lanes_w4, PipeRoute{ PR_ENCODE, KT_ENCODE }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_encode_batch_dev(c, (const uint64_t*)di[0], (uint8_t*)dout[0], m);
-    });
+    const HostCall d = { { { affine, 64 } }, { { out32, 32 } }, { PR_ENCODE, 0, KT_ENCODE }, unit_w4_x4 };
+    return host_call(c, n, d, [&](const Chunk& k) { return fourq_encode_batch_dev(c, k.in<uint64_t>(0), k.out<uint8_t>(0), k.m); });
 }
 FQ_API int fourq_decode_batch(fourq_ctx* c, const uint8_t* in32, uint64_t* affine, uint8_t* status, size_t n) {
-    if (!c || !in32 || !affine || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[1] = { { (const char*)in32, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)affine, 64 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 1, o, 2, n, c->lanes_w4, PipeRoute{ PR_DECODE, KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_decode_batch_dev(c, (const uint8_t*)di[0], (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    });
+    const HostCall d = { { { in32, 32 } }, { { affine, 64 }, { status, 1 } }, { PR_DECODE, 0, KT_DECODE }, unit_w4 };
+    return host_call(c, n, d, [&](const Chunk& k) { return fourq_decode_batch_dev(c, k.in<uint8_t>(0), k.out<uint64_t>(0), k.out<uint8_t>(1), k.m); });
 }
 
 // ---- protocol-level calls: every intermediate stays on the device -------------------------------------------
@@ -1628,7 +1660,7 @@ static int dh_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const u
     if (!aligned16(scalars) || !aligned16(keys32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::DhBytes::bytes(n));       // the planes only if dh_dev defers: not reserve_dh_bytes
+    int rc = ensure_work(c, fq_work::DhBytes::bytes(n));       // the planes only if dh_dev defers: not reserve_for<DhBytes>
     if (rc) return rc;
     const fq_work::DhBytes w(c->work, n);
     if ((rc = fourq_decode_batch_dev(c, keys32, w.pts, w.st_decode, n))) return rc;
@@ -1640,16 +1672,11 @@ static int dh_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const u
 }
 static int dh_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint8_t* keys32, const uint64_t* table, uint8_t* out32,
                          uint8_t* status, size_t n) {
-    if (!c || !scalars || !keys32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)keys32, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
-    const size_t unit = table ? c->lanes_w4 / 2 : pipe_chunk(c);
-    const double kt = (table ? KT_DH_FIXED : (algo == ENDO ? KT_DH_VAR : KT_WIN_VAR + 0.3)) + KT_CODEC;
-    return run_pipeline(c, in, 2, o, 2, n, unit, PipeRoute{ (table ? PR_DHB_FIX : PR_DHB_VAR) + (algo == ENDO ? 0 : 1), kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return dh_bytes_dev(c, algo, (const uint64_t*)di[0], (const uint8_t*)di[1], table, (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, table ? c->lanes_w4 : pipe_chunk(c), reserve_dh_bytes);
+    const int v = algo == ENDO ? 0 : 1;
+    HostCall d = { { { scalars, 32 }, { keys32, 32 } }, { { out32, 32 }, { status, 1 } }, { PR_DHB_VAR, v, (v ? KT_WIN_VAR + 0.3 : KT_DH_VAR) + KT_CODEC }, pipe_chunk, pipe_chunk,
+                   reserve_for<fq_work::DhBytes> };
+    if (table) { d.route = { PR_DHB_FIX, v, KT_DH_FIXED + KT_CODEC }; d.unit = unit_w4_half; d.unit_pageable = unit_w4; }
+    return host_call(c, n, d, [&](const Chunk& k) { return dh_bytes_dev(c, algo, k.in<uint64_t>(0), k.in<uint8_t>(1), table, k.out<uint8_t>(0), k.out<uint8_t>(1), k.m); });
 }
 // ---- MUL_* with affine / encoded I/O: R1toAffine(MUL_<algo>(m, AffineToR1(P))) and encode(.) of it --------------------------
 // 160 (96) bytes per operation across the ABI instead of the raw-R1 form's 352: the host-array calls are bound by the link, not by the
@@ -1696,7 +1723,7 @@ static int mul_affine_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const
     if (!aligned16(scalars) || !aligned16(points_affine) || !aligned16(out_affine)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_mul_rows(c, n);
+    int rc = reserve_for<fq_work::MulRows>(c, n);
     if (rc) return rc;
     const fq_work::MulRows w(c->work, n);
     u32 stride;
@@ -1704,14 +1731,10 @@ static int mul_affine_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const
     return launch_lower(c, false, w.rows_out, stride, nullptr, out_affine, nullptr, n);
 }
 static int mul_affine_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
-    if (!c || !scalars || !points_affine || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points_affine, nullptr, 64 } };
-    PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
-    return run_pipeline(c, in, 2, o, 1, n, pipe_chunk(c), PipeRoute{ PR_AFF + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
-        return mul_affine_dev(c, algo, (const uint64_t*)di[0], (const uint64_t*)di[1], (uint64_t*)dout[0], m);
-    }, 0, reserve_mul_rows);
+    const int v = algo == ENDO ? 0 : 1;
+    const HostCall d = { { { scalars, 32 }, { points_affine, 64 } }, { { out_affine, 64 } }, { PR_AFF, v, (v ? KT_WIN_VAR : KT_ENDO_VAR) + KT_LIFT_LOWER }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::MulRows> };
+    return host_call(c, n, d, [&](const Chunk& k) { return mul_affine_dev(c, algo, k.in<uint64_t>(0), k.in<uint64_t>(1), k.out<uint64_t>(0), k.m); });
 }
 // decode -> MUL_<algo> -> encode.  status: 0 ok | 16 + FOURQ_DECODE_* (out32 is zero then); MUL_* itself cannot fail.
 static int mul_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
@@ -1719,7 +1742,7 @@ static int mul_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const 
     if (!aligned16(scalars) || !aligned16(points32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_mul_rows(c, n);
+    int rc = reserve_for<fq_work::MulRows>(c, n);
     if (rc) return rc;
     const fq_work::MulRows w(c->work, n);
     u32 stride;
@@ -1727,14 +1750,10 @@ static int mul_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const 
     return launch_lower(c, true, w.rows_out, stride, w.st_decode, (uint64_t*)out32, status, n);
 }
 static int mul_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
-    if (!c || !scalars || !points32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[2] = { { (const char*)scalars, nullptr, 32 }, { (const char*)points32, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 2, o, 2, n, pipe_chunk(c), PipeRoute{ PR_BYTES + (algo == ENDO ? 0 : 1), (algo == ENDO ? KT_ENDO_VAR : KT_WIN_VAR) + KT_LIFT_LOWER + KT_CODEC }, [&](char* const* di, char* const* dout, size_t m) {
-        return mul_bytes_dev(c, algo, (const uint64_t*)di[0], (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, reserve_mul_rows);
+    const int v = algo == ENDO ? 0 : 1;
+    const HostCall d = { { { scalars, 32 }, { points32, 32 } }, { { out32, 32 }, { status, 1 } }, { PR_BYTES, v, (v ? KT_WIN_VAR : KT_ENDO_VAR) + KT_LIFT_LOWER + KT_CODEC }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::MulRows> };
+    return host_call(c, n, d, [&](const Chunk& k) { return mul_bytes_dev(c, algo, k.in<uint64_t>(0), k.in<uint8_t>(1), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m); });
 }
 FQ_API int fourq_mul_endo_affine_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return mul_affine_dev(c, ENDO, s, p, o, n); }
 FQ_API int fourq_mul_windowed_affine_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t n) { return mul_affine_dev(c, WINDOWED, s, p, o, n); }
@@ -1757,7 +1776,7 @@ FQ_API int fourq_dh_exchange_batch_dev(fourq_ctx* c, const uint64_t* a, const ui
     if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_exchange
+    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_for<Exchange>
     if (rc) return rc;
     const fq_work::Exchange w(c->work, n);                     // mid = DH(b_i, base): the public keys
     AffineArg point;
@@ -1773,17 +1792,13 @@ FQ_API int fourq_dh_exchange_batch_dev(fourq_ctx* c, const uint64_t* a, const ui
 }
 FQ_API int fourq_dh_exchange_batch(fourq_ctx* c, const uint64_t* a, const uint64_t* b, const uint64_t* base_affine, const uint64_t* table392,
                                    uint64_t* out, uint8_t* status, size_t n) {
-    if (!c || !a || !b || !base_affine || !out || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
     uint64_t base_copy[8];
-    memcpy(base_copy, base_affine, sizeof base_copy);         // the caller's buffer is read once, here
-    PipeArray in[2] = { { (const char*)a, nullptr, 32 }, { (const char*)b, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)out, 64 }, { nullptr, (char*)status, 1 } };
-    // one generation of the fixed-base half (two waves per SIMD) = two of the variable-base half (one wave per SIMD)
-    return run_pipeline(c, in, 2, o, 2, n, c->lanes_w4 / 2, PipeRoute{ PR_EXCH + (table392 ? 1 : 0), (table392 ? KT_DH_FIXED : KT_DH_VAR) + KT_DH_VAR }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_dh_exchange_batch_dev(c, (const uint64_t*)di[0], (const uint64_t*)di[1], base_copy, table392, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    }, c->lanes_w4, reserve_exchange);
+    // unit: one generation of the fixed-base half (two waves per SIMD) = two of the variable-base half (one wave per SIMD)
+    const HostCall d = { { { a, 32 }, { b, 32 } }, { { out, 64 }, { status, 1 } }, { PR_EXCH, table392 ? 1 : 0, (table392 ? KT_DH_FIXED : KT_DH_VAR) + KT_DH_VAR }, unit_w4_half, unit_w4,
+                         reserve_for<fq_work::Exchange>, base_affine != nullptr };
+    return host_call(c, n, d, [&] { memcpy(base_copy, base_affine, sizeof base_copy); return FOURQ_OK; }, [&](const Chunk& k) {      // the caller's buffer is read once
+        return fourq_dh_exchange_batch_dev(c, k.in<uint64_t>(0), k.in<uint64_t>(1), base_copy, table392, k.out<uint64_t>(0), k.out<uint8_t>(1), k.m);
+    });
 }
 
 // dh_exchange with the key-generation half through the comb (bench.py's cfg4 step as one call)
@@ -1792,7 +1807,7 @@ FQ_API int fourq_dh_exchange_comb_batch_dev(fourq_ctx* c, const uint64_t* a, con
     if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_exchange
+    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_for<Exchange>
     if (rc) return rc;
     const fq_work::Exchange w(c->work, n);                     // mid = [b_i]B: the public keys
     if ((rc = fourq_comb_mul_batch_dev(c, b, comb, w.mid, w.st_first, n))) return rc;
@@ -1802,15 +1817,10 @@ FQ_API int fourq_dh_exchange_comb_batch_dev(fourq_ctx* c, const uint64_t* a, con
     return FOURQ_OK;
 }
 FQ_API int fourq_dh_exchange_comb_batch(fourq_ctx* c, const uint64_t* a, const uint64_t* b, const uint64_t* comb, uint64_t* out, uint8_t* status, size_t n) {
-    if (!c || !a || !b || !out || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;                            // compared once, not once per chunk
-    PipeArray in[2] = { { (const char*)a, nullptr, 32 }, { (const char*)b, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)out, 64 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 2, o, 2, n, c->lanes_w4 / 2, PipeRoute{ PR_EXCH_COMB, KT_COMB + KT_DH_VAR }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_dh_exchange_comb_batch_dev(c, (const uint64_t*)di[0], (const uint64_t*)di[1], nullptr, (uint64_t*)dout[0], (uint8_t*)dout[1], m);
-    }, c->lanes_w4, reserve_exchange);
+    const HostCall d = { { { a, 32 }, { b, 32 } }, { { out, 64 }, { status, 1 } }, { PR_EXCH_COMB, 0, KT_COMB + KT_DH_VAR }, unit_w4_half, unit_w4, reserve_for<fq_work::Exchange> };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
+        return fourq_dh_exchange_comb_batch_dev(c, k.in<uint64_t>(0), k.in<uint64_t>(1), nullptr, k.out<uint64_t>(0), k.out<uint8_t>(1), k.m);
+    });
 }
 
 // ---- [k]B + [l]P: the curve part of a Schnorr-type verification (R' = [s]B + [h]A) -------------------------------------------
@@ -1831,7 +1841,7 @@ static int double_mul_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb,
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_double_mul(c, n))) return rc;
+    if ((rc = reserve_for<fq_work::DoubleMul>(c, n))) return rc;
     const fq_work::DoubleMul w(c->work, n);
     // (1) [k_i]B, projective
     if ((rc = launch_comb_deferred(c, k, w.st_comb, n))) return rc;
@@ -1843,43 +1853,29 @@ static int double_mul_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb,
                                       encoded ? w.st_decode : nullptr, (const u64*)expect32, (u64*)out, status, ok, (u32)n));
     return FOURQ_OK;
 }
-constexpr double KT_DOUBLE = KT_COMB + KT_ENDO_VAR + KT_LIFT_LOWER;
 FQ_API int fourq_double_mul_affine_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* p, uint64_t* o, size_t n) { return double_mul_dev(c, k, comb, l, p, false, COMBINE_AFFINE, nullptr, o, nullptr, nullptr, n); }
 FQ_API int fourq_double_mul_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* p, uint8_t* o, uint8_t* st, size_t n) { return double_mul_dev(c, k, comb, l, p, true, COMBINE_ENCODE, nullptr, o, st, nullptr, n); }
 FQ_API int fourq_verify_bytes_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* p, const uint8_t* expect32, uint8_t* ok, uint8_t* st, size_t n) { return double_mul_dev(c, k, comb, l, p, true, COMBINE_VERIFY, expect32, nullptr, st, ok, n); }
 FQ_API int fourq_double_mul_affine_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
-    if (!c || !k || !l || !points_affine || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;                            // compared once, not once per chunk
-    PipeArray in[3] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points_affine, nullptr, 64 } };
-    PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
-    return run_pipeline(c, in, 3, o, 1, n, pipe_chunk(c), PipeRoute{ PR_DOUBLE_AFF, KT_DOUBLE }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_double_mul_affine_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint64_t*)di[2], (uint64_t*)dout[0], m);
-    }, 0, reserve_double_mul);
+    const HostCall d = { { { k, 32 }, { l, 32 }, { points_affine, 64 } }, { { out_affine, 64 } }, { PR_DOUBLE_AFF, 0, KT_DOUBLE }, pipe_chunk, nullptr, reserve_for<fq_work::DoubleMul> };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& x) {
+        return fourq_double_mul_affine_batch_dev(c, x.in<uint64_t>(0), nullptr, x.in<uint64_t>(1), x.in<uint64_t>(2), x.out<uint64_t>(0), x.m);
+    });
 }
 FQ_API int fourq_double_mul_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
-    if (!c || !k || !l || !points32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;
-    PipeArray in[3] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points32, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 3, o, 2, n, pipe_chunk(c), PipeRoute{ PR_DOUBLE_BYTES, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_double_mul_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, reserve_double_mul);
+    const HostCall d = { { { k, 32 }, { l, 32 }, { points32, 32 } }, { { out32, 32 }, { status, 1 } }, { PR_DOUBLE_BYTES, 0, KT_DOUBLE + KT_DECODE }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::DoubleMul> };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& x) {
+        return fourq_double_mul_bytes_batch_dev(c, x.in<uint64_t>(0), nullptr, x.in<uint64_t>(1), x.in<uint8_t>(2), x.out<uint8_t>(0), x.out<uint8_t>(1), x.m);
+    });
 }
 FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint8_t* points32, const uint8_t* expect32,
                                     uint8_t* ok, uint8_t* status, size_t n) {
-    if (!c || !k || !l || !points32 || !expect32 || !ok || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;
-    PipeArray in[4] = { { (const char*)k, nullptr, 32 }, { (const char*)l, nullptr, 32 }, { (const char*)points32, nullptr, 32 }, { (const char*)expect32, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 4, o, 2, n, pipe_chunk(c), PipeRoute{ PR_DOUBLE_VERIFY, KT_DOUBLE + KT_DECODE }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_verify_bytes_batch_dev(c, (const uint64_t*)di[0], nullptr, (const uint64_t*)di[1], (const uint8_t*)di[2], (const uint8_t*)di[3], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, reserve_double_mul);
+    const HostCall d = { { { k, 32 }, { l, 32 }, { points32, 32 }, { expect32, 32 } }, { { ok, 1 }, { status, 1 } }, { PR_DOUBLE_VERIFY, 0, KT_DOUBLE + KT_DECODE }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::DoubleMul> };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& x) {
+        return fourq_verify_bytes_batch_dev(c, x.in<uint64_t>(0), nullptr, x.in<uint64_t>(1), x.in<uint8_t>(2), x.in<uint8_t>(3), x.out<uint8_t>(0), x.out<uint8_t>(1), x.m);
+    });
 }
 
 // ---- grouped multi-scalar multiplication: out[g] = R1toAffine(sum_j MUL_endo(k_gj, AffineToR1(P_gj))) over groups of one length ----------
@@ -1890,7 +1886,6 @@ FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint6
 static bool msm_count(size_t groups, size_t group_size, size_t* n) {
     return !__builtin_mul_overflow(groups, group_size, n) && *n <= FOURQ_MAX_BATCH;
 }
-static int reserve_msm(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::Msm::bytes(big)); }
 static int msm_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
     if (!c || !scalars || !points || !out || (encoded && !status)) return FOURQ_ERR_INVALID;
@@ -1898,7 +1893,7 @@ static int msm_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bo
     if (groups == 0) return FOURQ_OK;
     if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
     CtxGuard g(c);
-    int rc = reserve_msm(c, n);
+    int rc = reserve_for<fq_work::Msm>(c, n);
     if (rc) return rc;
     const fq_work::Msm w(c->work, n);
     u32 stride;
@@ -1950,20 +1945,13 @@ static bool sig_msgs_dev_ok(const uint8_t* msgs, size_t stride, const uint32_t* 
     if (msg_len > 0xffffffffu || (!msgs && stride != 0)) return false;
     return aligned16(msgs) && aligned16(lens);
 }
-// the host-pointer calls can look at the lengths: nothing above `stride` or FOURQ_SIG_MAX_MSG gets through
+// the host-pointer calls can look at the lengths: nothing above `stride` or FOURQ_SIG_MAX_MSG gets through.  A batch above the limit is
+// refused here too: the call sites evaluate this before host_call has looked at n, and no caller has that many lengths.
 static bool sig_msgs_host_ok(const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, size_t n) {
-    if (!msgs && stride != 0) return false;
+    if ((!msgs && stride != 0) || n > FOURQ_MAX_BATCH) return false;
     if (!lens) return msg_len <= stride && msg_len <= FOURQ_SIG_MAX_MSG;
     for (size_t i = 0; i < n; i++) if (lens[i] > stride || lens[i] > FOURQ_SIG_MAX_MSG) return false;
     return true;
-}
-constexpr double KT_SHA_BLOCK = 0.05;             // one 128-byte block per element: ~5 000 VALU instructions, a first-call guess like the other KT_*
-// chunk of a host-pointer call that carries a message matrix: the route's own chunk, cut down (to no less than one block's worth of rows)
-// where rows of `stride` bytes would make a pipeline slot larger than 64 MiB
-static size_t sig_chunk(size_t chunk, size_t stride) {
-    const size_t cap = stride ? (size_t)(64u << 20) / stride : chunk;
-    if (cap < chunk) chunk = cap < (size_t)BLOCK ? (size_t)BLOCK : cap;
-    return chunk;
 }
 static double sig_kt_hash(size_t stride, int prefix_bytes) { return KT_SHA_BLOCK * (double)((stride + prefix_bytes + 17 + 127) / 128); }
 
@@ -1980,7 +1968,7 @@ FQ_API int fourq_sig_keygen_batch_dev(fourq_ctx* c, const uint8_t* sk32, const u
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_sig(c, n))) return rc;
+    if ((rc = reserve_for<fq_work::Sig>(c, n))) return rc;
     const fq_work::Sig w(c->work, n);
     HIPRC_TRY(c, sig_launch_nonce(c->stream, false, sk32, SigMsgs{ nullptr, 0, nullptr, 0 }, w.a, nullptr, (u32)n));
     return comb_encode(c, w.a, w.affine, w.st_comb, pk32, n);      // [a]G; the projective neutral would need a = 0 mod N
@@ -1993,7 +1981,7 @@ FQ_API int fourq_sig_sign_batch_dev(fourq_ctx* c, const uint8_t* sk32, const uin
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_sig(c, n))) return rc;
+    if ((rc = reserve_for<fq_work::Sig>(c, n))) return rc;
     const fq_work::Sig w(c->work, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
     HIPRC_TRY(c, sig_launch_nonce(c->stream, true, sk32, m, w.a, w.r, (u32)n));
@@ -2009,7 +1997,7 @@ FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const u
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_double_mul(c, n))) return rc;                         // SigVerify is DoubleMul with its tail carved: double_mul_dev below asks for the same and moves nothing
+    if ((rc = reserve_for<fq_work::DoubleMul>(c, n))) return rc;                         // SigVerify is DoubleMul with its tail carved: double_mul_dev below asks for the same and moves nothing
     const fq_work::SigTail w = fq_work::SigVerify(c->work, n).sig;
     HIPRC_TRY(c, sig_launch_challenge(c->stream, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w.s, w.h, w.r32, w.pre, (u32)n));
     if ((rc = double_mul_dev(c, w.s, nullptr, w.h, pk32, true, COMBINE_VERIFY, (const uint8_t*)w.r32, nullptr, status, ok, n))) return rc;
@@ -2017,68 +2005,34 @@ FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const u
     return FOURQ_OK;
 }
 
-// host-pointer twins: a message matrix is one more array of `stride` bytes per element (left out when stride is 0), the lengths one of four.
-// MsgArrays appends whichever of the two the caller gave to the call's input arrays and finds them again among a chunk's device pointers.
-struct MsgArrays {
-    int i_msg = -1, i_len = -1;
-    MsgArrays(PipeArray* in, int* n_in, const uint8_t* msgs, size_t stride, const uint32_t* lens) {
-        if (stride) { i_msg = *n_in; in[(*n_in)++] = PipeArray{ (const char*)msgs, nullptr, stride }; }
-        if (lens) { i_len = *n_in; in[(*n_in)++] = PipeArray{ (const char*)lens, nullptr, 4 }; }
-    }
-    const uint8_t* msgs(char* const* di) const { return i_msg < 0 ? nullptr : (const uint8_t*)di[i_msg]; }
-    const uint32_t* lens(char* const* di) const { return i_len < 0 ? nullptr : (const uint32_t*)di[i_len]; }
-};
+// host-pointer twins: a message matrix is one more input array of `stride` bytes per element (absent when stride is 0), the lengths one of
+// four (absent when NULL); the launch gets nullptr for an absent one, which is what the _dev call takes in its place.
 FQ_API int fourq_sha512_batch(fourq_ctx* c, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* out64, size_t n) {
-    if (!c || !out64 || n > FOURQ_MAX_BATCH || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[2];
-    int n_in = 0;
-    const MsgArrays ma(in, &n_in, msgs, stride, lens);
-    PipeArray o[1] = { { nullptr, (char*)out64, 64 } };
-    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(4 * c->lanes_w4, stride), PipeRoute{ PR_SHA512, sig_kt_hash(stride, 0) }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_sha512_batch_dev(c, ma.msgs(di), stride, ma.lens(di), msg_len, (uint8_t*)dout[0], m);
-    });
+    const HostCall d = { { { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { out64, 64 } }, { PR_SHA512, 0, sig_kt_hash(stride, 0) }, unit_w4_x4, nullptr, nullptr,
+                         sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&](const Chunk& k) { return fourq_sha512_batch_dev(c, k.in<uint8_t>(0), stride, k.in<uint32_t>(1), msg_len, k.out<uint8_t>(0), k.m); });
 }
 FQ_API int fourq_sig_keygen_batch(fourq_ctx* c, const uint8_t* sk32, const uint64_t* comb, uint8_t* pk32, size_t n) {
-    if (!c || !sk32 || !pk32 || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;                            // compared once, not once per chunk
-    PipeArray in[1] = { { (const char*)sk32, nullptr, 32 } };
-    PipeArray o[1] = { { nullptr, (char*)pk32, 32 } };
-    return run_pipeline(c, in, 1, o, 1, n, c->lanes_w4, PipeRoute{ PR_SIG_KEYGEN, KT_COMB + KT_SHA_BLOCK + KT_ENCODE }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_sig_keygen_batch_dev(c, (const uint8_t*)di[0], nullptr, (uint8_t*)dout[0], m);
-    }, 0, reserve_sig);
+    const HostCall d = { { { sk32, 32 } }, { { pk32, 32 } }, { PR_SIG_KEYGEN, 0, KT_COMB + KT_SHA_BLOCK + KT_ENCODE }, unit_w4, nullptr, reserve_for<fq_work::Sig> };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) { return fourq_sig_keygen_batch_dev(c, k.in<uint8_t>(0), nullptr, k.out<uint8_t>(0), k.m); });
 }
 FQ_API int fourq_sig_sign_batch(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb,
                                 const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* sig64, size_t n) {
-    if (!c || !sk32 || !pk32 || !sig64 || n > FOURQ_MAX_BATCH || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;
-    PipeArray in[4] = { { (const char*)sk32, nullptr, 32 }, { (const char*)pk32, nullptr, 32 } };
-    int n_in = 2;
-    const MsgArrays ma(in, &n_in, msgs, stride, lens);
-    PipeArray o[1] = { { nullptr, (char*)sig64, 64 } };
     const double kt = KT_COMB + KT_ENCODE + KT_SHA_BLOCK + sig_kt_hash(stride, 32) + sig_kt_hash(stride, 64);
-    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(c->lanes_w4, stride), PipeRoute{ PR_SIG_SIGN, kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_sig_sign_batch_dev(c, (const uint8_t*)di[0], (const uint8_t*)di[1], nullptr, ma.msgs(di), stride, ma.lens(di), msg_len, (uint8_t*)dout[0], m);
-    }, 0, reserve_sig);
+    const HostCall d = { { { sk32, 32 }, { pk32, 32 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { sig64, 64 } }, { PR_SIG_SIGN, 0, kt }, unit_w4, nullptr, reserve_for<fq_work::Sig>,
+                         sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
+        return fourq_sig_sign_batch_dev(c, k.in<uint8_t>(0), k.in<uint8_t>(1), nullptr, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.out<uint8_t>(0), k.m);
+    });
 }
 FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
                                   const uint8_t* sig64, uint8_t* ok, uint8_t* status, size_t n) {
-    if (!c || !pk32 || !sig64 || !ok || !status || n > FOURQ_MAX_BATCH || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;
-    PipeArray in[4] = { { (const char*)pk32, nullptr, 32 }, { (const char*)sig64, nullptr, 64 } };
-    int n_in = 2;
-    const MsgArrays ma(in, &n_in, msgs, stride, lens);
-    PipeArray o[2] = { { nullptr, (char*)ok, 1 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_SIG_VERIFY, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_sig_verify_batch_dev(c, (const uint8_t*)di[0], nullptr, ma.msgs(di), stride, ma.lens(di), msg_len, (const uint8_t*)di[1], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, reserve_double_mul);
+    const HostCall d = { { { pk32, 32 }, { sig64, 64 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { ok, 1 }, { status, 1 } },
+                         { PR_SIG_VERIFY, 0, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, pipe_chunk, nullptr, reserve_for<fq_work::DoubleMul>,
+                         sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
+        return fourq_sig_verify_batch_dev(c, k.in<uint8_t>(0), nullptr, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.in<uint8_t>(1), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m);
+    });
 }
 
 // ---- bytes to a point (include/fourq_amd.h, "hash to curve"): expand_message_xmd + hash_to_field in one kernel, the map, the addition, the
@@ -2087,7 +2041,6 @@ FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint6
 static bool h2c_args_ok(const uint8_t* dst, size_t dst_len, int mode) {
     return dst && dst_len >= 1 && dst_len <= FOURQ_H2C_MAX_DST && (mode == FOURQ_H2C_RO || mode == FOURQ_H2C_NU);
 }
-constexpr double KT_ELL2 = 0.20;                  // one map: four GF(p) exponentiations' worth, a first-call guess like the other KT_*
 static double h2c_kt_hash(size_t stride, size_t dst_len, int count) {
     return KT_SHA_BLOCK * (double)((stride + dst_len + 4 + 17 + 127) / 128 + count * ((64 + dst_len + 2 + 17 + 127) / 128));
 }
@@ -2112,7 +2065,7 @@ static int hash_to_curve_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, i
     if (!c || !out || n > FOURQ_MAX_BATCH || !aligned16(out) || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    if (int rc = reserve_h2c(c, n)) return rc;
+    if (int rc = reserve_for<fq_work::H2c>(c, n)) return rc;
     const int count = mode == FOURQ_H2C_RO ? 2 : 1;
     uint64_t* u = fq_work::H2c(c->work, n).u;
     HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), u, (u32)n));
@@ -2123,33 +2076,24 @@ FQ_API int fourq_hash_to_curve_batch_dev(fourq_ctx* c, const uint8_t* dst, size_
 FQ_API int fourq_hash_to_curve_affine_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint64_t* o, size_t n) { return hash_to_curve_dev(c, dst, dl, mode, m, st, ln, ml, H2C_OUT_AFFINE, o, n); }
 // host-pointer twins; what = 0: hash_to_field (out: count x 32 bytes per row), 1: 32-byte points, 2: affine words
 static int h2c_host(fourq_ctx* c, int what, const uint8_t* dst, size_t dst_len, int mode, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, void* out, size_t n) {
-    if (!c || !out || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    const int count = mode == FOURQ_H2C_RO ? 2 : 1;
-    PipeArray in[2];
-    int n_in = 0;
-    const MsgArrays ma(in, &n_in, msgs, stride, lens);
-    PipeArray o[1] = { { nullptr, (char*)out, what == 0 ? (size_t)32 * count : what == 1 ? (size_t)32 : (size_t)64 } };
-    const double kt = h2c_kt_hash(stride, dst_len, count) + (what == 0 ? 0.0 : count * KT_ELL2 + KT_LIFT_LOWER);
-    const PipeRoute route{ what == 0 ? PR_H2F : (what == 1 ? PR_H2C : PR_H2C_AFFINE) + mode, kt };
-    return run_pipeline(c, in, n_in, o, 1, n, sig_chunk(what == 0 ? 4 * c->lanes_w4 : pipe_chunk(c), stride), route, [&](char* const* di, char* const* dout, size_t m) {
-        if (what == 0) return fourq_hash_to_field_batch_dev(c, dst, dst_len, mode, ma.msgs(di), stride, ma.lens(di), msg_len, (uint64_t*)dout[0], m);
-        return hash_to_curve_dev(c, dst, dst_len, mode, ma.msgs(di), stride, ma.lens(di), msg_len, what == 1 ? H2C_OUT_BYTES : H2C_OUT_AFFINE, dout[0], m);
-    }, 0, what == 0 ? nullptr : reserve_h2c);
+    const bool ok = h2c_args_ok(dst, dst_len, mode) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n);
+    const int count = mode == FOURQ_H2C_RO ? 2 : 1, nu = mode == FOURQ_H2C_NU ? 1 : 0;
+    const double kt_hash = h2c_kt_hash(stride, dst_len, count), kt_map = count * KT_ELL2 + KT_LIFT_LOWER;
+    const HostIn msg = { msgs, stride }, len = { lens, 4, MAY_BE_NULL };
+    const HostCall field = { { msg, len }, { { out, (size_t)32 * count } }, { PR_H2F, 0, kt_hash }, unit_w4_x4, nullptr, nullptr, ok, stride };
+    const HostCall curve = { { msg, len }, { { out, what == 1 ? (size_t)32 : (size_t)64 } }, { what == 1 ? PR_H2C : PR_H2C_AFFINE, nu, kt_hash + kt_map }, pipe_chunk, nullptr,
+                             reserve_for<fq_work::H2c>, ok, stride };
+    return host_call(c, n, what == 0 ? field : curve, [&](const Chunk& k) {
+        if (what == 0) return fourq_hash_to_field_batch_dev(c, dst, dst_len, mode, k.in<uint8_t>(0), stride, k.in<uint32_t>(1), msg_len, k.out<uint64_t>(0), k.m);
+        return hash_to_curve_dev(c, dst, dst_len, mode, k.in<uint8_t>(0), stride, k.in<uint32_t>(1), msg_len, what == 1 ? H2C_OUT_BYTES : H2C_OUT_AFFINE, k.out<void>(0), k.m);
+    });
 }
 FQ_API int fourq_hash_to_field_batch(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint64_t* o, size_t n) { return h2c_host(c, 0, dst, dl, mode, m, st, ln, ml, o, n); }
 FQ_API int fourq_hash_to_curve_batch(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint8_t* o, size_t n) { return h2c_host(c, 1, dst, dl, mode, m, st, ln, ml, o, n); }
 FQ_API int fourq_hash_to_curve_affine_batch(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint64_t* o, size_t n) { return h2c_host(c, 2, dst, dl, mode, m, st, ln, ml, o, n); }
 FQ_API int fourq_map_to_curve_batch(fourq_ctx* c, const uint64_t* u, uint64_t* out_affine, size_t n) {
-    if (!c || !u || !out_affine || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[1] = { { (const char*)u, nullptr, 32 } };
-    PipeArray o[1] = { { nullptr, (char*)out_affine, 64 } };
-    return run_pipeline(c, in, 1, o, 1, n, pipe_chunk(c), PipeRoute{ PR_H2C_MAP, KT_ELL2 + KT_LIFT_LOWER }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_map_to_curve_batch_dev(c, (const uint64_t*)di[0], (uint64_t*)dout[0], m);
-    });
+    const HostCall d = { { { u, 32 } }, { { out_affine, 64 } }, { PR_H2C_MAP, 0, KT_ELL2 + KT_LIFT_LOWER }, pipe_chunk };
+    return host_call(c, n, d, [&](const Chunk& k) { return fourq_map_to_curve_batch_dev(c, k.in<uint64_t>(0), k.out<uint64_t>(0), k.m); });
 }
 
 // ---- oblivious PRF (include/fourq_amd.h, "oblivious PRF"): the hash-to-curve stages, the ladders with affine / encoded I/O, DH_endo and the
@@ -2162,12 +2106,6 @@ static int scinv_group(const fourq_ctx* c, size_t n) {
     const size_t wave_per_simd = (size_t)c->cus * BLOCK;
     return n <= wave_per_simd ? 1 : n <= 8 * wave_per_simd ? OPRF_SCINV_K_MID : OPRF_SCINV_K_BIG;
 }
-static int reserve_oprf_blind(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::OprfBlind::bytes(big)); }
-static int reserve_oprf_evaluate(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::OprfEvaluate::bytes(big)); }
-static int reserve_oprf_finalize(fourq_ctx* c, size_t big) { return reserve_work(c, big, false, fq_work::OprfFinalize::bytes(big)); }
-static int reserve_oprf_eval(fourq_ctx* c, size_t big) { return reserve_work(c, big, true, fq_work::OprfEval::bytes(big)); }
-// first-call guesses like the other KT_*: a Fermat chain is about 1.2 ladders' worth of instructions, shared by 8 elements
-constexpr double KT_SCINV = 0.70;
 
 // Test hook, gated like the routing variables (route_env): refused unless FOURQ_DEBUG_ROUTES=1 is set.  It is a call and not one more variable:
 // the set of variables the library reads is pinned (tests/test_host.py).  k: 1, 8 or 16 elements per inversion, 0 = by batch size again.
@@ -2186,14 +2124,8 @@ FQ_API int fourq_scalar_inv_batch_dev(fourq_ctx* c, const uint64_t* scalars, uin
     return FOURQ_OK;
 }
 FQ_API int fourq_scalar_inv_batch(fourq_ctx* c, const uint64_t* scalars, uint64_t* out, size_t n) {
-    if (!c || !scalars || !out || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[1] = { { (const char*)scalars, nullptr, 32 } };
-    PipeArray o[1] = { { nullptr, (char*)out, 32 } };
-    return run_pipeline(c, in, 1, o, 1, n, 16 * (size_t)c->cus * BLOCK, PipeRoute{ PR_SC_INV, KT_SCINV }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_scalar_inv_batch_dev(c, (const uint64_t*)di[0], (uint64_t*)dout[0], m);
-    });
+    const HostCall d = { { { scalars, 32 } }, { { out, 32 } }, { PR_SC_INV, 0, KT_SCINV }, unit_scinv };
+    return host_call(c, n, d, [&](const Chunk& k) { return fourq_scalar_inv_batch_dev(c, k.in<uint64_t>(0), k.out<uint64_t>(0), k.m); });
 }
 
 FQ_API int fourq_oprf_blind_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
@@ -2202,7 +2134,7 @@ FQ_API int fourq_oprf_blind_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t d
     if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_oprf_blind(c, n);
+    int rc = reserve_for<fq_work::OprfBlind>(c, n);
     if (rc) return rc;
     const fq_work::OprfBlind w(c->work, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
@@ -2231,7 +2163,7 @@ FQ_API int fourq_oprf_finalize_batch_dev(fourq_ctx* c, const uint8_t* dst, size_
     if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_oprf_finalize(c, n);
+    int rc = reserve_for<fq_work::OprfFinalize>(c, n);
     if (rc) return rc;
     const fq_work::OprfFinalize w(c->work, n);
     HIPRC_TRY(c, oprf_launch_sc_inv(c->stream, scinv_group(c, n), blinds, w.inv, w.st_zero, (u32)n));
@@ -2264,56 +2196,35 @@ FQ_API int fourq_oprf_eval_batch_dev(fourq_ctx* c, const uint64_t* key, const ui
 static double oprf_kt_final(size_t stride, size_t dst_len) { return KT_SHA_BLOCK * (double)((32 + stride + 9 + dst_len + 17 + 127) / 128); }
 FQ_API int fourq_oprf_blind_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
                                   const uint64_t* blinds, uint8_t* out32, uint8_t* status, size_t n) {
-    if (!c || !blinds || !out32 || !status || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[3] = { { (const char*)blinds, nullptr, 32 } };
-    int n_in = 1;
-    const MsgArrays ma(in, &n_in, msgs, stride, lens);
-    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
     const double kt = h2c_kt_hash(stride, dst_len, 2) + 2 * KT_ELL2 + KT_ENDO_VAR + 2 * KT_LIFT_LOWER;
-    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_OPRF_BLIND, kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_oprf_blind_batch_dev(c, dst, dst_len, ma.msgs(di), stride, ma.lens(di), msg_len, (const uint64_t*)di[0], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, reserve_oprf_blind);
+    const HostCall d = { { { blinds, 32 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { out32, 32 }, { status, 1 } }, { PR_OPRF_BLIND, 0, kt }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::OprfBlind>, h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&](const Chunk& k) {
+        return fourq_oprf_blind_batch_dev(c, dst, dst_len, k.in<uint8_t>(1), stride, k.in<uint32_t>(2), msg_len, k.in<uint64_t>(0), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m);
+    });
 }
 FQ_API int fourq_oprf_evaluate_batch(fourq_ctx* c, const uint64_t* key, const uint8_t* blinded32, uint8_t* out32, uint8_t* status, size_t n) {
-    if (!c || !key || !blinded32 || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[1] = { { (const char*)blinded32, nullptr, 32 } };
-    PipeArray o[2] = { { nullptr, (char*)out32, 32 }, { nullptr, (char*)status, 1 } };
-    return run_pipeline(c, in, 1, o, 2, n, pipe_chunk(c), PipeRoute{ PR_OPRF_EVALUATE, KT_DH_VAR + KT_CODEC }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_oprf_evaluate_batch_dev(c, key, (const uint8_t*)di[0], (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, reserve_oprf_evaluate);
+    const HostCall d = { { { blinded32, 32 } }, { { out32, 32 }, { status, 1 } }, { PR_OPRF_EVALUATE, 0, KT_DH_VAR + KT_CODEC }, pipe_chunk, nullptr, reserve_for<fq_work::OprfEvaluate>,
+                         key != nullptr };
+    return host_call(c, n, d, [&](const Chunk& k) { return fourq_oprf_evaluate_batch_dev(c, key, k.in<uint8_t>(0), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m); });
 }
 FQ_API int fourq_oprf_finalize_batch(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
                                      const uint64_t* blinds, const uint8_t* evaluated32, uint8_t* out64, uint8_t* status, size_t n) {
-    if (!c || !blinds || !evaluated32 || !out64 || !status || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[4] = { { (const char*)blinds, nullptr, 32 }, { (const char*)evaluated32, nullptr, 32 } };
-    int n_in = 2;
-    const MsgArrays ma(in, &n_in, msgs, stride, lens);
-    PipeArray o[2] = { { nullptr, (char*)out64, 64 }, { nullptr, (char*)status, 1 } };
     const double kt = KT_SCINV + KT_ENDO_VAR + KT_LIFT_LOWER + KT_CODEC + oprf_kt_final(stride, dst_len);
-    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_OPRF_FINALIZE, kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_oprf_finalize_batch_dev(c, dst, dst_len, ma.msgs(di), stride, ma.lens(di), msg_len, (const uint64_t*)di[0], (const uint8_t*)di[1], (uint8_t*)dout[0],
-                                             (uint8_t*)dout[1], m);
-    }, 0, reserve_oprf_finalize);
+    const HostCall d = { { { blinds, 32 }, { evaluated32, 32 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { out64, 64 }, { status, 1 } }, { PR_OPRF_FINALIZE, 0, kt }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::OprfFinalize>, h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&](const Chunk& k) {
+        return fourq_oprf_finalize_batch_dev(c, dst, dst_len, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.in<uint64_t>(0), k.in<uint8_t>(1), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m);
+    });
 }
 FQ_API int fourq_oprf_eval_batch(fourq_ctx* c, const uint64_t* key, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens,
                                  size_t msg_len, uint8_t* out64, uint8_t* status, size_t n) {
-    if (!c || !key || !out64 || !status || n > FOURQ_MAX_BATCH || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_host_ok(msgs, stride, lens, msg_len, n)) return FOURQ_ERR_INVALID;
-    if (n == 0) return FOURQ_OK;
-    CtxGuard g(c);
-    PipeArray in[2];
-    int n_in = 0;
-    const MsgArrays ma(in, &n_in, msgs, stride, lens);
-    PipeArray o[2] = { { nullptr, (char*)out64, 64 }, { nullptr, (char*)status, 1 } };
     const double kt = h2c_kt_hash(stride, dst_len, 2) + 2 * KT_ELL2 + KT_LIFT_LOWER + KT_DH_VAR + KT_ENCODE + oprf_kt_final(stride, dst_len);
-    return run_pipeline(c, in, n_in, o, 2, n, sig_chunk(pipe_chunk(c), stride), PipeRoute{ PR_OPRF_EVAL, kt }, [&](char* const* di, char* const* dout, size_t m) {
-        return fourq_oprf_eval_batch_dev(c, key, dst, dst_len, ma.msgs(di), stride, ma.lens(di), msg_len, (uint8_t*)dout[0], (uint8_t*)dout[1], m);
-    }, 0, reserve_oprf_eval);
+    const HostCall d = { { { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { out64, 64 }, { status, 1 } }, { PR_OPRF_EVAL, 0, kt }, pipe_chunk, nullptr, reserve_for<fq_work::OprfEval>,
+                         key && h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&](const Chunk& k) {
+        return fourq_oprf_eval_batch_dev(c, key, dst, dst_len, k.in<uint8_t>(0), stride, k.in<uint32_t>(1), msg_len, k.out<uint8_t>(0), k.out<uint8_t>(1), k.m);
+    });
 }
 
 // ---- pinned host memory and transfer statistics of the host-pointer calls ---------------------------------------

@@ -5,9 +5,14 @@
 // elements ends -- size and offsets come from ONE sequence of take() calls, so they cannot drift apart.  Nothing at run time would notice
 // if they did: the buffer is grown by free + allocate, and a region carved past a too-small total is somebody else's memory.  Rows are
 // multiples of 32 bytes and a status region is align256(n) bytes (one byte per element), so every region starts 16-byte aligned.
+//
+// A layout that sizes the buffer for a call also says, in `planes`, whether the _dev call behind it may defer a normalisation into the
+// context's projective planes (fourq_ctx::proj): what a host-array call sizes for its largest chunk before the first one is enqueued
+// (reserve_for<Layout> in fourq_amd.hip).  Every such layout is named once more, in `All` at the end of this file.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 
 namespace fq_work {
 
@@ -27,6 +32,7 @@ struct DhBytes {                    // decode -> DH_* -> encode
     uint8_t *st_decode, *st_dh;
     size_t end;
     DhBytes(char* base, size_t n) { Carver w(base); pts = w.take<uint64_t>(n * 8); shared = w.take<uint64_t>(n * 8); st_decode = w.take_status(n); st_dh = w.take_status(n); end = w.used; }
+    static constexpr bool planes = true;
     static size_t bytes(size_t n) { return DhBytes(nullptr, n).end; }
 };
 struct Exchange {                   // both exchange calls; the one whose first half goes through the comb leaves base_pts unused
@@ -34,6 +40,7 @@ struct Exchange {                   // both exchange calls; the one whose first 
     uint8_t* st_first;
     size_t end;
     Exchange(char* base, size_t n) { Carver w(base); base_pts = w.take<uint64_t>(n * 8); mid = w.take<uint64_t>(n * 8); st_first = w.take_status(n); end = w.used; }
+    static constexpr bool planes = true;
     static size_t bytes(size_t n) { return Exchange(nullptr, n).end; }
 };
 struct MulRows {                    // MUL_* with affine or encoded I/O
@@ -42,6 +49,7 @@ struct MulRows {                    // MUL_* with affine or encoded I/O
     uint8_t* st_decode;
     size_t end;
     MulRows(char* base, size_t n) { Carver w(base); rows_in = w.take<uint64_t>(n * 20); rows_out = w.take<uint64_t>(n * 20); unused = w.take<uint64_t>(n * 8); st_decode = w.take_status(n); end = w.used; }
+    static constexpr bool planes = false;
     static size_t bytes(size_t n) { return MulRows(nullptr, n).end; }
 };
 struct SigTail {                    // what the signature check hands the double multiplication
@@ -59,6 +67,7 @@ struct DoubleMul {
     char* tail;
     size_t end;
     DoubleMul(char* base, size_t n) { Carver w(base); rows_in = w.take<uint64_t>(n * 20); rows_out = w.take<uint64_t>(n * 20); st_decode = w.take_status(n); st_comb = w.take_status(n); tail = w.take<char>(SigTail::bytes(n)); end = w.used; }
+    static constexpr bool planes = true;
     static size_t bytes(size_t n) { return DoubleMul(nullptr, n).end; }
 };
 struct SigVerify : DoubleMul {      // the signature check: the double multiplication's layout with its tail carved
@@ -72,12 +81,14 @@ struct Sig {                        // keygen / sign
     uint8_t* st_comb;
     size_t end;
     Sig(char* base, size_t n) { Carver w(base); a = w.take<uint64_t>(n * 4); r = w.take<uint64_t>(n * 4); r32 = w.take<uint8_t>(n * 32); affine = w.take<uint64_t>(n * 8); st_comb = w.take_status(n); end = w.used; }
+    static constexpr bool planes = true;
     static size_t bytes(size_t n) { return Sig(nullptr, n).end; }
 };
 struct H2c {                        // hash to curve
     uint64_t* u;                    // u_0, u_1 as rows of 32 bytes: n x 8 words
     size_t end;
     H2c(char* base, size_t n) { Carver w(base); u = w.take<uint64_t>(n * 8); end = w.used; }
+    static constexpr bool planes = false;
     static size_t bytes(size_t n) { return H2c(nullptr, n).end; }
 };
 // Grouped sums out[g] = sum [k]P over groups of one length; n = groups x group_size elements.  A fold pass turns m rows per group into
@@ -91,6 +102,7 @@ struct Msm {
     uint8_t *st_a, *st_b;           // the largest decode code among a partial sum's elements
     size_t end;
     Msm(char* base, size_t n) { Carver w(base); rows_in = w.take<uint64_t>(n * 20); rows_out = w.take<uint64_t>(n * 20); st_decode = w.take_status(n); part_a = w.take<uint64_t>(n / 2 * 12); st_a = w.take_status(n / 2); part_b = w.take<uint64_t>(n / 4 * 12); st_b = w.take_status(n / 4); end = w.used; }
+    static constexpr bool planes = false;
     static size_t bytes(size_t n) { return Msm(nullptr, n).end; }
 };
 // ---- the oblivious PRF (oprf.hip.h).  Each of the four totals is below SigVerify's 416 n + 3 n (blind and finalize: 384 n + n and
@@ -102,6 +114,7 @@ struct OprfBlind {                  // hash to curve -> MUL_endo by the blind ->
     uint8_t* st_decode;             // all zero (the points come from the map, not from a decode): what lower_kernel<K, true> reads
     size_t end;
     OprfBlind(char* base, size_t n) { Carver w(base); pts = w.take<uint64_t>(n * 8); rows_in = w.take<uint64_t>(n * 20); u = rows_in; rows_out = w.take<uint64_t>(n * 20); st_decode = w.take_status(n); end = w.used; }
+    static constexpr bool planes = false;
     static size_t bytes(size_t n) { return OprfBlind(nullptr, n).end; }
 };
 struct OprfEvaluate {               // the key on n scalar rows -> decode -> DH_endo -> encode
@@ -109,6 +122,7 @@ struct OprfEvaluate {               // the key on n scalar rows -> decode -> DH_
     uint64_t* keys;                 // n x 4 words
     size_t end;
     OprfEvaluate(char* base, size_t n) { Carver w(base); dh = w.take<char>(DhBytes::bytes(n)); keys = w.take<uint64_t>(n * 4); end = w.used; }
+    static constexpr bool planes = true;
     static size_t bytes(size_t n) { return OprfEvaluate(nullptr, n).end; }
 };
 struct OprfFinalize {               // 1 / blind -> decode -> MUL_endo -> encode -> hash
@@ -119,6 +133,7 @@ struct OprfFinalize {               // 1 / blind -> decode -> MUL_endo -> encode
     uint8_t* st_zero;               // FOURQ_OPRF_BLIND_ZERO where the blind is 0 mod N
     size_t end;
     OprfFinalize(char* base, size_t n) { Carver w(base); inv = w.take<uint64_t>(n * 4); rows_in = w.take<uint64_t>(n * 20); rows_out = w.take<uint64_t>(n * 20); e32 = w.take<uint64_t>(n * 4); st_decode = w.take_status(n); st_lower = w.take_status(n); st_zero = w.take_status(n); end = w.used; }
+    static constexpr bool planes = false;
     static size_t bytes(size_t n) { return OprfFinalize(nullptr, n).end; }
 };
 struct OprfEval {                   // hash to curve -> DH_endo by the key -> encode -> hash
@@ -129,7 +144,16 @@ struct OprfEval {                   // hash to curve -> DH_endo by the key -> en
     uint8_t* st_dh;
     size_t end;
     OprfEval(char* base, size_t n) { Carver w(base); pts = w.take<uint64_t>(n * 8); shared = w.take<uint64_t>(n * 8); u = shared; keys = w.take<uint64_t>(n * 4); e32 = w.take<uint64_t>(n * 4); st_dh = w.take_status(n); end = w.used; }
+    static constexpr bool planes = true;
     static size_t bytes(size_t n) { return OprfEval(nullptr, n).end; }
 };
+
+// Every layout a call sizes the work buffer by: fourq_ctx_reserve allocates max_bytes(n), so that no _dev call of at most n elements
+// reallocates.  SigTail is not one of them (it is carved inside DoubleMul's tail, whose total includes it), and SigVerify is DoubleMul's
+// carving with that tail opened: the same total.  tests/test_work_layout.py compares this list with the structs of this file.
+template <class... L> struct Layouts {
+    static size_t max_bytes(size_t n) { size_t most = 0; for (size_t b : { L::bytes(n)... }) if (b > most) most = b; return most; }
+};
+using All = Layouts<DhBytes, Exchange, MulRows, DoubleMul, Sig, H2c, Msm, OprfBlind, OprfEvaluate, OprfFinalize, OprfEval>;
 
 }  // namespace fq_work

@@ -1,10 +1,17 @@
-// prints every work-buffer layout for n elements: ./work_layout_dump n  ->  lines "layout region offset" and "layout bytes total"
+// prints every work-buffer layout for n elements: ./work_layout_dump n  ->  lines "layout region offset" and "layout bytes total", then the
+// list of all layouts as the header has it: "list Struct total" per member and "list max_bytes value"
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "work_layout.h"
 static char* const BASE = reinterpret_cast<char*>(uintptr_t(1) << 44);      // never dereferenced: the layouts only compute addresses
 static void region(const char* layout, const char* name, const void* p) { printf("%s %s %zu\n", layout, name, (size_t)(static_cast<const char*>(p) - BASE)); }
 #define REGION(layout, w, member) region(layout, #member, w.member)
+template <class L> static void listed(size_t n) {          // g++ spells the type out: "... [with L = fq_work::DhBytes; ...]"
+    const char* at = strstr(__PRETTY_FUNCTION__, "fq_work::") + 9;
+    printf("list %.*s %zu\n", (int)strcspn(at, ";]"), at, L::bytes(n));
+}
+template <class... L> static void list_all(fq_work::Layouts<L...>, size_t n) { (listed<L>(n), ...); printf("list max_bytes %zu\n", fq_work::Layouts<L...>::max_bytes(n)); }
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
     const size_t n = strtoull(argv[1], 0, 10);
@@ -19,5 +26,6 @@ int main(int argc, char** argv) {
     { const H2c w(BASE, n); REGION("h2c", w, u); }
     printf("dh_bytes bytes %zu\nexchange bytes %zu\nmul_rows bytes %zu\ndouble_mul bytes %zu\nsig_verify bytes %zu\nsig bytes %zu\nh2c bytes %zu\n",
            DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), DoubleMul::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n));
+    list_all(All(), n);
     return 0;
 }

@@ -133,6 +133,33 @@ def test_hash_to_field_dev_fixed_length_and_clamping(eng):
     assert bad_rows(eng.hash_to_field(m, dst=DSTS[1], mode="nu"), want_u_words(m, np.full(70, 45), DSTS[1], "nu")).size == 0
 
 
+def test_host_calls_over_several_chunks_equal_the_dev_forms(eng):
+    """The host-array calls cut into chunks (the message matrix and the lengths are two of a chunk's arrays) against the _dev forms on the
+    same bytes, which the tests around this one pin against the restatement.  One chunk of hash_to_field is 16 x lanes rows, so it
+    takes more than 2 x lanes + 77 rows to make a second one; one of hash_to_curve is `lanes` rows."""
+    import torch
+    dev = torch.device("cuda", 0)
+    for what, n, stride in (("field", 16 * eng.lanes + 77, 16), ("curve", 2 * eng.lanes + 77, 40)):
+        m = random_matrix(n, stride, 31)
+        lens = np.random.default_rng(32).integers(0, stride + 1, size=n, dtype=np.uint32)
+        d_m, d_lens = torch.from_numpy(m).to(dev), torch.from_numpy(lens.view(np.int32)).to(dev)
+        if what == "field":
+            got = eng.hash_to_field(m, lens, dst=DSTS[43], mode="nu")
+            chunks = eng.host_stats()["chunks"]
+            out = torch.empty((n, 1, 4), dtype=torch.int64, device=dev)
+            eng.hash_to_field_dev(d_m, stride, d_lens, 0, out, n, dst=DSTS[43], mode="nu")
+            eng.sync()
+            same = np.array_equal(got, out.cpu().numpy().view(np.uint64))
+        else:
+            got = eng.hash_to_curve(m, lens, dst=DSTS[43])
+            chunks = eng.host_stats()["chunks"]
+            out = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+            eng.hash_to_curve_dev(d_m, stride, d_lens, 0, out, n, dst=DSTS[43])
+            eng.sync()
+            same = np.array_equal(got, out.cpu().numpy())
+        assert chunks > 1 and same, what
+
+
 # ---- 2. the map -------------------------------------------------------------------------------------------------------------------------
 def test_map_to_curve_and_the_primitive(eng):
     rng = random.Random(20261017)

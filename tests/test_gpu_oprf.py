@@ -303,6 +303,39 @@ def test_large_shapes_against_the_composition(eng):
     assert not st.any() and bad_rows(direct[~zero], out[~zero]).size == 0
 
 
+def test_host_calls_over_several_chunks_equal_the_dev_forms(eng):
+    """blind, finalize and eval cut into chunks of `lanes` rows (the message matrix and the lengths are two of a chunk's arrays) against the
+    _dev forms on the same bytes, which the other tests pin against the restatement at small n."""
+    import torch
+    n, stride = 2 * eng.lanes + 77, 40
+    rng = np.random.default_rng(79)
+    m = rng.integers(0, 256, size=(n, stride), dtype=np.uint8)
+    lens = rng.integers(0, stride + 1, size=n, dtype=np.uint32)
+    r = rng.integers(0, 2**63, size=(n, 4), dtype=np.int64).astype(np.uint64) * np.uint64(2) + np.uint64(1)
+    r[7] = 0
+    k = codec.pack_scalars([0x1234567890ABCDEF << 128 | 0xFEDCBA])[0]
+    d_m, d_lens, d_r = to_dev(m), to_dev(lens), to_dev(r)
+    out32, out64, st = dev_empty((n, 32), torch.uint8), dev_empty((n, 64), torch.uint8), dev_empty(n, torch.uint8)
+
+    blinded, bst = eng.oprf_blind(m, r, lens, dst=DST)
+    assert eng.host_stats()["chunks"] > 1
+    eng.oprf_blind_dev(d_m, stride, d_lens, 0, d_r, out32, st, n, dst=DST)
+    eng.sync()
+    assert np.array_equal(blinded, out32.cpu().numpy()) and np.array_equal(bst, st.cpu().numpy()) and bst[7] == _lib.OPRF_BLIND_ZERO and bst.sum() == bst[7]
+
+    final, fst = eng.oprf_finalize(m, r, blinded, lens, dst=DST)     # row 7 is all zero: it does not decode
+    assert eng.host_stats()["chunks"] > 1
+    eng.oprf_finalize_dev(d_m, stride, d_lens, 0, d_r, out32, out64, st, n, dst=DST)
+    eng.sync()
+    assert np.array_equal(final, out64.cpu().numpy()) and np.array_equal(fst, st.cpu().numpy()) and np.flatnonzero(fst).tolist() == [7]
+
+    direct, dst_ = eng.oprf_eval(k, m, lens, dst=DST)
+    assert eng.host_stats()["chunks"] > 1
+    eng.oprf_eval_dev(k, d_m, stride, d_lens, 0, out64, st, n, dst=DST)
+    eng.sync()
+    assert np.array_equal(direct, out64.cpu().numpy()) and np.array_equal(dst_, st.cpu().numpy()) and not dst_.any()
+
+
 # ---- 6. the _dev forms --------------------------------------------------------------------------------------------------------------------
 def test_dev_forms_clamp_and_refuse_misaligned_pointers(eng):
     import torch

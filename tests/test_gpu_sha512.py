@@ -107,3 +107,20 @@ def test_host_call_refuses_lengths_beyond_the_stride(eng):
     m = random_matrix(4, 32, 8)
     with pytest.raises(FourQError):
         eng.sha512(m, np.array([1, 2, 33, 4], dtype=np.uint32))
+
+
+def test_host_call_over_several_chunks_equals_the_dev_form(eng):
+    """The host-array call cut into chunks (the message matrix and the lengths are two of the chunk's arrays) against the _dev form on
+    the same bytes, which the tests above pin against hashlib.  One chunk of this call is 16 x lanes rows, so it takes more than
+    2 x lanes + 77 rows to make a second one."""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, stride = 16 * eng.lanes + 77, 16
+    m = random_matrix(n, stride, 9)
+    lens = np.random.default_rng(10).integers(0, stride + 1, size=n, dtype=np.uint32)
+    got = eng.sha512(m, lens)
+    assert eng.host_stats()["chunks"] > 1
+    out = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    eng.sha512_dev(torch.from_numpy(m).to(dev), stride, torch.from_numpy(lens.view(np.int32)).to(dev), 0, out, n)
+    eng.sync()
+    assert np.array_equal(got, out.cpu().numpy())

@@ -131,6 +131,33 @@ def test_keygen_sign_verify_at_scale(eng):
     assert ok.all() and not st.any()
 
 
+def test_host_calls_over_several_chunks_equal_the_dev_forms(eng):
+    """sign and verify cut into chunks (the message matrix and the lengths are two of a chunk's arrays) against the _dev forms on the same
+    bytes, which the tests around this one pin against the restatement.  One chunk of sign is 4 x lanes rows, so it takes more than
+    2 x lanes + 77 rows to make a second one; one of verify is `lanes` rows, and it runs on the first 2 x lanes + 77 of them."""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, nv, stride = 4 * eng.lanes + 77, 2 * eng.lanes + 77, 24
+    g_comb(eng)
+    rng = np.random.default_rng(6200)
+    sk = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    matrix = rng.integers(0, 256, size=(n, stride), dtype=np.uint8)
+    lens = rng.integers(0, stride + 1, size=n, dtype=np.uint32)
+    pk = eng.sig_keygen(sk)
+    sig = eng.sig_sign(sk, pk, matrix, lens)
+    assert eng.host_stats()["chunks"] > 1
+    d_pk, d_m, d_len = to_dev(pk), to_dev(matrix), to_dev(lens)
+    d_sig = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    eng.sig_sign_dev(to_dev(sk), d_pk, d_m, stride, d_len, 0, d_sig, n)
+    eng.sync()
+    assert np.array_equal(sig, d_sig.cpu().numpy())
+    sig[5, 3] ^= 1                                                 # one row that does not verify, on both sides
+    ok, st = eng.sig_verify(pk[:nv], matrix[:nv], sig[:nv], lens[:nv])
+    assert eng.host_stats()["chunks"] > 1
+    d_ok, d_st = dev_verify(eng, pk[:nv], matrix[:nv], lens[:nv], sig[:nv])
+    assert np.array_equal(ok, d_ok) and np.array_equal(st, d_st) and ok.sum() == nv - 1 and not ok[5]
+
+
 # ---- 3. the verifier must not say yes too often ----------------------------------------------------------------------------------
 def test_every_tamper_class_inside_one_batch(eng, golden):
     n = 4096

@@ -287,6 +287,25 @@ def test_null_arguments_are_rejected_without_a_device():
     assert lib.fourq_prim_batch(None, 0, None, None, 0) == _lib.ERR_INVALID
 
 
+def test_every_batch_entry_point_refuses_a_null_context_before_it_looks_at_anything_else():
+    """Every *_batch / *_batch_dev call with ctx == NULL and every other argument VALID (pointers at a small host buffer, sizes 1,
+    enums 0) is FOURQ_ERR_INVALID: the context is refused before anything is derived from it -- a chunk unit such as ctx->lanes_w4 / 2
+    computed ahead of the check would read through the NULL pointer, and this test would not return."""
+    import ctypes
+    from fourq_amd import _lib
+    lib = _lib.load()
+    names = [n for n in _lib.PROTOTYPES if n.endswith(("_batch", "_batch_dev"))]
+    assert len(names) >= 73 and "fourq_oprf_eval_batch" in names and "fourq_mul_endo_fixed_batch_dev" in names
+    buf = np.zeros(4096, dtype=np.uint8)
+    for name in names:
+        args = []
+        for kind in _lib.PROTOTYPES[name][1][1:]:
+            assert kind in (ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int), (name, kind)
+            args.append(ctypes.c_void_p(buf.ctypes.data) if kind is ctypes.c_void_p else 1 if kind is ctypes.c_size_t else 0)
+        assert getattr(lib, name)(None, *args) == _lib.ERR_INVALID, name
+    assert not buf.any()
+
+
 def test_documents_quote_the_committed_bench_line():
     """DESIGN.md section 6 and README.md carry numbers generated from the driver's own record (BENCH_rNN.json.parsed, newest parsed one, stated
     first) and from profiles/r06_bench_driver_args_run*.full.json (the builder's runs of the driver's protocol); the generator's --check mode must

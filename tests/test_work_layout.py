@@ -50,21 +50,23 @@ def layouts(tmp_path_factory):
 
     def run(n):
         if n not in cache:
-            regions, totals = {}, {}
+            regions, totals, listed = {}, {}, {}
             for line in subprocess.run([exe, str(n)], check=True, capture_output=True, text=True).stdout.splitlines():
                 layout, name, value = line.split()
-                if name == "bytes":
+                if layout == "list":                  # the header's list of all layouts: struct name -> total, and "max_bytes"
+                    listed[name] = int(value)
+                elif name == "bytes":
                     totals[layout] = int(value)
                 else:
                     regions.setdefault(layout, {})[name] = int(value)
-            cache[n] = (regions, totals)
+            cache[n] = (regions, totals, listed)
         return cache[n]
     return run
 
 
 @pytest.mark.parametrize("n", SIZES)
 def test_regions_are_aligned_disjoint_and_inside_the_total(layouts, n):
-    regions, totals = layouts(n)
+    regions, totals, _ = layouts(n)
     assert set(regions) == set(NEED) == set(totals)
     for layout, offs in regions.items():
         assert set(offs) == set(NEED[layout]), layout
@@ -78,7 +80,7 @@ def test_regions_are_aligned_disjoint_and_inside_the_total(layouts, n):
 
 @pytest.mark.parametrize("n", SIZES)
 def test_totals_are_the_formulas_the_library_allocated_by(layouts, n):
-    regions, totals = layouts(n)
+    regions, totals, _ = layouts(n)
     for layout, formula in BYTES.items():
         assert totals[layout] == formula(n), layout
     # the signature check is the double multiplication plus a tail: same total (double_mul_dev, called with the buffer already sized by
@@ -90,3 +92,28 @@ def test_totals_are_the_formulas_the_library_allocated_by(layouts, n):
     # two offsets the kernels' callers have always used
     assert regions["mul_rows"]["st_decode"] == 2 * n * 160 + n * 64
     assert regions["sig"]["affine"] == 3 * n * 32
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_the_list_of_all_layouts_gives_the_largest_total(layouts, n):
+    """fourq_ctx_reserve sizes the work buffer by the list's max_bytes(n): it is the largest of the members' totals, and the members'
+    totals are the ones pinned above."""
+    _, totals, listed = layouts(n)
+    listed = dict(listed)
+    most = listed.pop("max_bytes")
+    assert most == max(listed.values()) == BYTES["sig_verify"](n)              # the signature check's, as it has been since it came
+    for struct, label in (("DhBytes", "dh_bytes"), ("Exchange", "exchange"), ("MulRows", "mul_rows"), ("DoubleMul", "double_mul"), ("Sig", "sig"), ("H2c", "h2c")):
+        assert listed[struct] == totals[label] == BYTES[label](n), struct
+
+
+def test_the_list_names_every_layout_struct_of_the_header(layouts):
+    """A layout left out of the list would not be counted by fourq_ctx_reserve, and the first large _dev call that uses it would synchronise
+    and reallocate.  The structs of work_layout.h that carve the buffer are those with a bytes( member of their own.  Two are special: SigTail
+    is carved INSIDE DoubleMul's tail (DoubleMul's total includes it) and sizes nothing itself, so it is the one struct with a total that
+    the list leaves out; SigVerify has no bytes( of its own -- it inherits DoubleMul's total, which the list has."""
+    import re
+    text = open(os.path.join(ROOT, "fourq_amd", "csrc", "work_layout.h")).read()
+    structs = {m.group(1) for m in re.finditer(r"^struct (\w+)[^\n]*\{(.*?)^\};", text, re.M | re.S) if "bytes(" in m.group(2)} - {"Carver"}
+    listed = set(layouts(1)[2]) - {"max_bytes"}
+    assert len(listed) == 11 and structs == listed | {"SigTail"}, sorted(structs ^ listed)
+    assert re.search(r"^struct SigVerify : DoubleMul \{", text, re.M) and "SigVerify" not in structs
