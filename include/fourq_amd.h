@@ -188,7 +188,10 @@ int fourq_dev_free(fourq_ctx *ctx, void *ptr);
 int fourq_dev_upload(fourq_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);
 int fourq_dev_download(fourq_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes);
 
-/* ---- look-up tables: table_windowed(P) curve4q.py:179, table_endo(P) curve4q.py:385 ----------- */
+/* ---- look-up tables: table_windowed(P) curve4q.py:179, table_endo(P) curve4q.py:385 -----------
+ * Host pointers; synchronous: they run behind whatever the context's stream still holds and wait for it.  Building a table (these two and
+ * fourq_comb_table) does not change what the context has STAGED: the fixed-base table of the last fixed-base call and the comb that
+ * comb == NULL stands for are the same before and after. */
 int fourq_table_windowed(fourq_ctx *ctx, const uint64_t *p_r1, uint64_t *table);
 int fourq_table_endo(fourq_ctx *ctx, const uint64_t *p_r1, uint64_t *table);
 
@@ -285,6 +288,7 @@ int fourq_decode_batch_dev(fourq_ctx *ctx, const uint8_t *in32, uint64_t *out_af
  * comb table: FOURQ_COMB_WORDS words = 1 024 + 80 entries x (x+y, y-x, 2d*x*y), 4 words each (103.5 KiB). */
 #define FOURQ_COMB_POINTS 1104
 #define FOURQ_COMB_WORDS (1104 * 12)
+/* Builds and returns the table; it is neither staged nor does it disturb the staged one (see "look-up tables" above). */
 int fourq_comb_table(fourq_ctx *ctx, const uint64_t *p_r1, uint64_t *comb);
 /* The device copy of the comb stays staged between calls.  A batch call with a non-NULL `comb` compares it with the staged
  * copy (103.5 KiB on the host, per call) and uploads it when it differs; fourq_comb_stage does that once, and batch calls
