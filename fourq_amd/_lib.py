@@ -28,6 +28,7 @@ BYTES_DECODE_BASE = 16
 SIG_S_RANGE, SIG_MSG_CLAMPED, SIG_MAX_MSG = 32, 64, 1 << 20   # FOURQ_SIG_*
 H2C_RO, H2C_NU, H2C_MAX_DST = 0, 1, 255                       # FOURQ_H2C_*
 OPRF_BLIND_ZERO = 48                                          # FOURQ_OPRF_BLIND_ZERO
+DLEQ_NONCE_ZERO = 80                                          # FOURQ_DLEQ_NONCE_ZERO
 
 
 class HostStats(ctypes.Structure):
@@ -143,6 +144,13 @@ PROTOTYPES = {
     "fourq_scalar_inv_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_scalar_inv_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_ctx_set_scinv_group": (c_int, [c_void_p, c_int]),
+    "fourq_dleq_reserve": (c_int, [c_void_p, c_size_t, c_size_t]),
+    "fourq_dleq_composites": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_dleq_composites_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_dleq_prove": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_dleq_prove_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_dleq_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_dleq_verify_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_encode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_decode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),

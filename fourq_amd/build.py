@@ -24,7 +24,7 @@ RESOURCES_PATH = os.path.join(HERE, "kernel_resources.json")
 PLACEMENT_PATH = os.path.join(HERE, "code_placement.json")
 # four translation units: FQ_CHAIN=0 / 1 (kernels.hip.h), and the constant-time-selection builds of both flavours
 SOURCES = ["fourq_amd.hip", "fourq_chain.hip", "fourq_ct_fused.hip", "fourq_ct_chain.hip"]
-HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "kernels.hip.h", "combine.hip.h", "msm.hip.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "work_layout.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", "h2c.hip.h", "oprf.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
+HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "kernels.hip.h", "combine.hip.h", "msm.hip.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "work_layout.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", "h2c.hip.h", "oprf.hip.h", "dleq_layout.h", "dleq.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Rpass-analysis=kernel-resource-usage"]
 # Code placement (tools/asmgen/place_asm.py, profiles/r04_ladder_step.txt): the device code of every translation unit goes through
 # assembly text, where every 8-byte instruction is put on an 8-byte boundary (an _e32 instruction in front of it re-encoded as _e64),
@@ -60,6 +60,10 @@ RESOURCE_POLICY = [
     (r"\bell2_kernel<", "occupancy", lambda v: v >= 2, "the map runs the generated GF(p^2) bodies, whose temporaries are fixed high registers: two waves per SIMD"),
     (r"\boprf_final_kernel\(", "scratch", lambda v: v == 0, "the finalisation hash is a hashing kernel like the signature layer's (the tail is read from the kernel arguments, not copied)"),
     (r"\boprf_final_kernel\(", "occupancy", lambda v: v >= 4, "the finalisation hash is throughput code held to 128 VGPRs: four waves per SIMD"),
+    (r"\b(dleq_composite_kernel|dleq_prove_kernel|dleq_check_kernel)\(", "scratch", lambda v: v == 0,
+     "the proofs' hashing kernels load their rows into the message schedule of the block they belong to: only the state lives across a compression, nothing may spill"),
+    (r"\b(dleq_composite_kernel|dleq_prove_kernel|dleq_check_kernel)\(", "occupancy", lambda v: v >= 4,
+     "the proofs' hashing kernels are throughput code held to 128 VGPRs, as the finalisation hash: four waves per SIMD"),
     (r"\bsc_inv_kernel<", "scratch", lambda v: v == 0, "the inversion modulo N keeps its window table and its K - 1 prefix products in registers across the chain, at every K"),
 ]
 

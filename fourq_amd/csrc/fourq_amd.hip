@@ -41,6 +41,8 @@
 #include "sig.hip.h"
 #include "h2c.hip.h"
 #include "oprf.hip.h"
+#include "dleq_layout.h"
+#include "dleq.hip.h"
 
 using namespace fq;
 
@@ -2224,6 +2226,160 @@ FQ_API int fourq_oprf_eval_batch(fourq_ctx* c, const uint64_t* key, const uint8_
                          key && h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
     return host_call(c, n, d, [&](const Chunk& k) {
         return fourq_oprf_eval_batch_dev(c, key, dst, dst_len, k.in<uint8_t>(0), stride, k.in<uint32_t>(1), msg_len, k.out<uint8_t>(0), k.out<uint8_t>(1), k.m);
+    });
+}
+
+// ---- batched DLEQ proofs (include/fourq_amd.h, "oblivious PRF: proofs"): that a batch was evaluated with the key behind pk32 ------------------
+// Every curve operation is one of the calls above -- the grouped sum (M, Z and [s]M + [c]Z), [k]B + [l]P ([s]G + [c]pk), DH_endo and MUL_endo
+// on encodings (Z = DH_endo(k, M), [r]M), the comb with its encoding ([r]G and the public key in one launch) -- and dleq.hip.h's kernels
+// hash, reduce, split and compare in between.  The inner calls carve their own layouts at the start of the work buffer; this call's regions
+// lie behind the largest of them (dleq_layout.h), and the buffer and the projective planes are sized ONCE, here, for everything the inner
+// calls will ask, so that none of them moves the buffer under a value an earlier stage has left.
+static bool dleq_args_ok(const fourq_ctx* c, const uint8_t* dst, size_t dst_len, size_t groups, size_t group_size, bool pair, size_t* n) {
+    *n = 0;
+    if (!c || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO)) return false;
+    if (groups == 0) return true;
+    if (group_size == 0 || !msm_count(groups, group_size, n)) return false;
+    return !pair || 2 * groups <= FOURQ_MAX_BATCH;                // verify's sum of two is a grouped sum over 2 x groups rows
+}
+static int dleq_size(fourq_ctx* c, size_t n, size_t groups) {
+    if (int rc = ensure_proj(c, fq_work::Dleq::plane_rows(groups))) return rc;
+    return ensure_work(c, fq_work::Dleq::bytes(n, groups));
+}
+FQ_API int fourq_dleq_reserve(fourq_ctx* c, size_t groups, size_t group_size) {
+    size_t n;
+    if (!c || (groups && (group_size == 0 || !msm_count(groups, group_size, &n) || 2 * groups > FOURQ_MAX_BATCH))) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    return dleq_size(c, n, groups);
+}
+// d, then M32 = sum [d]C and (with_z) Z32 = sum [d]D with their statuses, from the public key's row at pk_dev
+static int dleq_composites_stage(fourq_ctx* c, const fq_work::Dleq& w, const OprfTail& tail, const uint8_t* pk_dev, const uint8_t* blinded32, const uint8_t* evaluated32,
+                                 uint8_t* m32, uint8_t* z32, bool with_z, size_t groups, size_t group_size) {
+    const size_t n = groups * group_size;
+    HIPRC_TRY(c, dleq_launch_composite(c->stream, pk_dev, blinded32, evaluated32, tail, w.d, (u32)group_size, (u32)n));
+    if (int rc = msm_dev(c, w.d, blinded32, true, m32, w.st_m, groups, group_size)) return rc;
+    return with_z ? msm_dev(c, w.d, evaluated32, true, z32, w.st_z, groups, group_size) : FOURQ_OK;
+}
+FQ_API int fourq_dleq_composites_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* pk32, const uint8_t* blinded32, const uint8_t* evaluated32,
+                                     uint8_t* m32, uint8_t* z32, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !pk32 || !blinded32 || !evaluated32 || !m32 || !z32 || !status) return FOURQ_ERR_INVALID;
+    if (!aligned16(blinded32) || !aligned16(evaluated32) || !aligned16(m32) || !aligned16(z32)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = dleq_size(c, n, groups);
+    if (rc) return rc;
+    const fq_work::Dleq w(c->work, n, groups);
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w.pk, 1));
+    if ((rc = dleq_composites_stage(c, w, dleq_make_tail("Composite", dst, dst_len), (const uint8_t*)w.pk, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
+    HIPRC_TRY(c, dleq_launch_composites_merge(c->stream, w.st_m, w.st_z, m32, z32, status, (u32)groups));
+    return FOURQ_OK;
+}
+FQ_API int fourq_dleq_prove_dev(fourq_ctx* c, const uint64_t* key, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
+                                const uint64_t* nonces, uint8_t* proof64, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !key || !blinded32 || !evaluated32 || !nonces || !proof64 || !status) return FOURQ_ERR_INVALID;
+    if (!aligned16(blinded32) || !aligned16(evaluated32) || !aligned16(nonces) || !aligned16(proof64)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = dleq_size(c, n, groups))) return rc;
+    const fq_work::Dleq w(c->work, n, groups);
+    uint8_t *m32 = (uint8_t*)w.m32, *z32 = (uint8_t*)w.z32, *t2 = (uint8_t*)w.t2, *t3 = (uint8_t*)w.t3;
+    const uint8_t* pk_dev = t2 + 32 * groups;
+    // r mod N on the groups' rows and K behind them: ONE comb launch gives every t2 and the public key
+    HIPRC_TRY(c, dleq_launch_nonces(c->stream, key, nonces, w.sc_a, (u32)groups));
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w.sc_b, (u32)groups));
+    if ((rc = comb_encode(c, w.sc_a, w.affine, w.st_t2, t2, groups + 1))) return rc;
+    if ((rc = dleq_composites_stage(c, w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, nullptr, false, groups, group_size))) return rc;
+    if ((rc = dh_bytes_dev(c, ENDO, w.sc_b, m32, nullptr, z32, w.st_z, groups))) return rc;                 // Z = DH_endo(k, M): D is hashed, never decoded
+    if ((rc = mul_bytes_dev(c, ENDO, w.sc_a, m32, t3, w.st_t3, groups))) return rc;                        // t3 = encode([r]M)
+    HIPRC_TRY(c, dleq_launch_prove(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), key, w.sc_a, w.st_m, w.st_z, w.st_t3, proof64, status,
+                                   (u32)groups));
+    return FOURQ_OK;
+}
+FQ_API int fourq_dleq_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
+                                 const uint8_t* proof64, uint8_t* ok, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, true, &n) || !pk32 || !blinded32 || !evaluated32 || !proof64 || !ok || !status) return FOURQ_ERR_INVALID;
+    if (!aligned16(blinded32) || !aligned16(evaluated32) || !aligned16(proof64)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = dleq_size(c, n, groups))) return rc;
+    const fq_work::Dleq w(c->work, n, groups);
+    uint8_t *m32 = (uint8_t*)w.m32, *z32 = (uint8_t*)w.z32, *t2 = (uint8_t*)w.t2, *t3 = (uint8_t*)w.t3;
+    const uint8_t* pk_dev = (const uint8_t*)w.pk;
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w.pk, (u32)groups));             // pk on every group's row: the point of [s]G + [c]pk
+    if ((rc = dleq_composites_stage(c, w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
+    HIPRC_TRY(c, dleq_launch_split(c->stream, proof64, m32, z32, w.sc_a, w.sc_b, w.pair_sc, w.pair_pt, w.st_pre, (u32)groups));
+    if ((rc = double_mul_dev(c, w.sc_a, nullptr, w.sc_b, pk_dev, true, COMBINE_ENCODE, nullptr, t2, w.st_t2, nullptr, groups))) return rc;       // t2' = [s]G + [c]pk
+    if ((rc = msm_dev(c, w.pair_sc, w.pair_pt, true, t3, w.st_t3, groups, 2))) return rc;                                                     // t3' = [s]M + [c]Z
+    HIPRC_TRY(c, dleq_launch_check(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), w.sc_b, w.st_m, w.st_z, w.st_t2, w.st_pre, w.st_t3, ok, status,
+                                   (u32)groups));
+    return FOURQ_OK;
+}
+// Host arrays, as msm_host: copy in through the staging buffer, the _dev call, copy out, synchronise.  No chunks: the outputs are per group.
+// One array of a call: copied in where `in` is set (n rows with `per_row`, `groups` rows otherwise), copied out (`groups` rows) where `out` is.
+struct DleqHostArray { const void* in; void* out; size_t row_bytes; bool per_row; };
+static int dleq_host(fourq_ctx* c, size_t n, size_t groups, std::initializer_list<DleqHostArray> arrays, const std::function<int(char**)>& call) {
+    CtxGuard g(c);
+    size_t total = 0;
+    for (const DleqHostArray& a : arrays) total += (a.per_row ? n : groups) * a.row_bytes;
+    int rc = ensure_stage(c, total);
+    if (rc) return rc;
+    char* dev[8];
+    size_t k = 0, used = 0;
+    for (const DleqHostArray& a : arrays) {                       // the caller lists the 32- and 64-byte rows first: every one of them starts 16-byte aligned
+        dev[k] = (char*)c->stage + used;
+        const size_t bytes = (a.per_row ? n : groups) * a.row_bytes;
+        if (a.in) HIP_TRY(c, hipMemcpyAsync(dev[k], a.in, bytes, hipMemcpyHostToDevice, c->stream));
+        used += bytes; k++;
+    }
+    if ((rc = call(dev))) return rc;
+    k = 0;
+    for (const DleqHostArray& a : arrays) {
+        if (a.out) HIP_TRY(c, hipMemcpyAsync(a.out, dev[k], groups * a.row_bytes, hipMemcpyDeviceToHost, c->stream));
+        k++;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FOURQ_OK;
+}
+FQ_API int fourq_dleq_composites(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* pk32, const uint8_t* blinded32, const uint8_t* evaluated32, uint8_t* m32,
+                                 uint8_t* z32, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !pk32 || !blinded32 || !evaluated32 || !m32 || !z32 || !status) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    return dleq_host(c, n, groups, { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { nullptr, m32, 32, false }, { nullptr, z32, 32, false }, { nullptr, status, 1, false } },
+                     [&](char** d) {
+        return fourq_dleq_composites_dev(c, dst, dst_len, pk32, (uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, group_size);
+    });
+}
+FQ_API int fourq_dleq_prove(fourq_ctx* c, const uint64_t* key, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
+                            const uint64_t* nonces, uint8_t* proof64, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !key || !blinded32 || !evaluated32 || !nonces || !proof64 || !status) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;
+    return dleq_host(c, n, groups, { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { nonces, nullptr, 32, false }, { nullptr, proof64, 64, false }, { nullptr, status, 1, false } },
+                     [&](char** d) {
+        return fourq_dleq_prove_dev(c, key, nullptr, dst, dst_len, (uint8_t*)d[0], (uint8_t*)d[1], (uint64_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, group_size);
+    });
+}
+FQ_API int fourq_dleq_verify(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
+                             const uint8_t* proof64, uint8_t* ok, uint8_t* status, size_t groups, size_t group_size) {
+    size_t n;
+    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, true, &n) || !pk32 || !blinded32 || !evaluated32 || !proof64 || !ok || !status) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (int rc = stage_comb(c, comb)) return rc;
+    return dleq_host(c, n, groups, { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { proof64, nullptr, 64, false }, { nullptr, ok, 1, false }, { nullptr, status, 1, false } },
+                     [&](char** d) {
+        return fourq_dleq_verify_dev(c, pk32, nullptr, dst, dst_len, (uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, group_size);
     });
 }
 

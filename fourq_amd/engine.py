@@ -608,6 +608,85 @@ class Engine:
         buf, dst_len, _ = self._h2c(dst, "ro")
         self._ck(self._lib.fourq_oprf_eval_batch_dev(self._ctx, _ptr(self._key(key_host)), buf, dst_len, _ptr(msgs), stride, _ptr(lens), msg_len, _ptr(out64), _ptr(status), n))
 
+    # ---- oblivious PRF: proofs (fourq_dleq_*: one batched DLEQ proof per group of rows, include/fourq_amd.h) -------------------------
+    @staticmethod
+    def _pk32(pk32):
+        pk = np.ascontiguousarray(np.frombuffer(bytes(pk32), dtype=np.uint8) if isinstance(pk32, (bytes, bytearray)) else pk32, dtype=np.uint8).ravel()
+        if pk.size != 32:
+            raise ValueError("a public key is 32 bytes")
+        return pk
+
+    def _dleq_rows(self, blinded32, evaluated32, group_size):
+        b, z = _host(blinded32, 32, np.uint8), _host(evaluated32, 32, np.uint8)
+        if len(b) != len(z):
+            raise ValueError("blinded and evaluated elements differ in length")
+        groups, group_size = self._groups(len(b), max(len(b), 1) if group_size is None else group_size)      # None: one group covers everything
+        return b, z, groups, group_size
+
+    def dleq_reserve(self, groups, group_size):
+        """Size the context's buffers for `dleq_*_dev` calls of up to groups x group_size rows (fourq_dleq_reserve; reserve() is not
+        enough for them): such calls then only enqueue and, with the comb staged, can be captured."""
+        self._ck(self._lib.fourq_dleq_reserve(self._ctx, int(groups), int(group_size)))
+
+    def dleq_public_key(self, key):
+        """pk32 = encode(DH_endo(key, G)) as (32,) uint8: oprf_evaluate of the generator's encoding."""
+        from . import codec
+        from .constants import Gx, Gy
+        out, status = self.oprf_evaluate(key, self.encode(codec.pack_points([(Gx, Gy)], 2)))
+        if status[0]:
+            raise ValueError("the key is 0 mod N: it has no public key (status %d)" % int(status[0]))
+        return out[0].copy()
+
+    def dleq_composites(self, pk32, blinded32, evaluated32, group_size=None, dst=b"", out=None, status=None):
+        """The verifier's composites per group: ((groups, 32) M32, (groups, 32) Z32, status).  group_size None = one group.
+        `out`: a pair of arrays."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        pk = self._pk32(pk32)
+        b, z, groups, group_size = self._dleq_rows(blinded32, evaluated32, group_size)
+        m32, z32 = (None, None) if out is None else out
+        m32, z32, status = _out(m32, groups, 32, np.uint8), _out(z32, groups, 32, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_dleq_composites(self._ctx, buf, dst_len, _ptr(pk), _ptr(b), _ptr(z), _ptr(m32), _ptr(z32), _ptr(status), groups, group_size))
+        return m32, z32, status
+
+    def dleq_prove(self, key, blinded32, evaluated32, nonces, group_size=None, dst=b"", comb=None, out=None, status=None):
+        """One proof c || s per group that evaluated = oprf_evaluate(key, blinded): ((groups, 64) uint8, status).  nonces: (groups, 4)
+        words, uniformly random and never reused.  status: 0, BYTES_DECODE_BASE + DECODE_*, DH_NEUTRAL (key = 0 mod N), DLEQ_NONCE_ZERO."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        k, r = self._key(key), _host(nonces, 4)
+        b, z, groups, group_size = self._dleq_rows(blinded32, evaluated32, group_size)
+        if len(r) != groups:
+            raise ValueError("one nonce per group")
+        out, status = _out(out, groups, 64, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_dleq_prove(self._ctx, _ptr(k), _ptr(self._comb_arg(comb)), buf, dst_len, _ptr(b), _ptr(z), _ptr(r), _ptr(out), _ptr(status), groups, group_size))
+        return out, status
+
+    def dleq_verify(self, pk32, blinded32, evaluated32, proofs64, group_size=None, dst=b"", comb=None, ok=None, status=None):
+        """(ok, status) per group: ok[g] = 1 iff proofs64[g] proves the group's rows under pk32.  status says why a 0 is a 0: 0 = the proof
+        does not hold, SIG_S_RANGE = c or s >= N, BYTES_DECODE_BASE + DECODE_* = a row or the key does not decode."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        pk, p = self._pk32(pk32), _host(proofs64, 64, np.uint8)
+        b, z, groups, group_size = self._dleq_rows(blinded32, evaluated32, group_size)
+        if len(p) != groups:
+            raise ValueError("one proof per group")
+        ok, status = _out(ok, groups, None, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_dleq_verify(self._ctx, _ptr(pk), _ptr(self._comb_arg(comb)), buf, dst_len, _ptr(b), _ptr(z), _ptr(p), _ptr(ok), _ptr(status), groups, group_size))
+        return ok, status
+
+    def dleq_composites_dev(self, pk32_host, blinded32, evaluated32, m32, z32, status, groups, group_size, dst=b""):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_dleq_composites_dev(self._ctx, buf, dst_len, _ptr(self._pk32(pk32_host)), _ptr(blinded32), _ptr(evaluated32), _ptr(m32), _ptr(z32), _ptr(status),
+                                                     groups, group_size))
+
+    def dleq_prove_dev(self, key_host, blinded32, evaluated32, nonces, proof64, status, groups, group_size, dst=b"", comb_host=None):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_dleq_prove_dev(self._ctx, _ptr(self._key(key_host)), _ptr(self._comb_arg(comb_host)), buf, dst_len, _ptr(blinded32), _ptr(evaluated32), _ptr(nonces),
+                                                _ptr(proof64), _ptr(status), groups, group_size))
+
+    def dleq_verify_dev(self, pk32_host, blinded32, evaluated32, proof64, ok, status, groups, group_size, dst=b"", comb_host=None):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_dleq_verify_dev(self._ctx, _ptr(self._pk32(pk32_host)), _ptr(self._comb_arg(comb_host)), buf, dst_len, _ptr(blinded32), _ptr(evaluated32),
+                                                 _ptr(proof64), _ptr(ok), _ptr(status), groups, group_size))
+
     def dh_exchange_dev(self, a_scalars, b_scalars, base_affine_host, table392_host, out_affine, status, n):
         base = _host(base_affine_host, None).ravel()
         t = None if table392_host is None else _host(table392_host, None).ravel()

@@ -231,6 +231,46 @@ class MultiEngine:
         return self._sharded(lambda e, m, ln, o, st: e.oprf_eval(key, m, ln, dst, out=o, status=st), [m, ln],
                              [_out(out, len(m), 64, np.uint8), _out(status, len(m), None, np.uint8)])
 
+    # ---- oblivious PRF: proofs.  A proof covers a whole group, so WHOLE groups are sharded: device g owns the groups shard_bounds gives it
+    # and, with them, their rows ----------------------------------------------------------------------------------------------------------
+    def _sharded_groups(self, call, rows, per_group, outs, group_size):
+        """as _sharded, cut between groups: `rows` have group_size rows per group, `per_group` and `outs` one"""
+        groups, world = len(outs[0]), len(self.engines)
+
+        def one(g):
+            lo, hi = shard_bounds(groups, g, world)
+            if hi > lo:
+                call(self.engines[g], *[a[lo * group_size:hi * group_size] for a in rows], *[a[lo:hi] for a in per_group], *[o[lo:hi] for o in outs])
+
+        if world == 1 or groups < 2:
+            for g in range(world):
+                one(g)
+        else:
+            for f in [self._pool.submit(one, g) for g in range(world)]:
+                f.result()
+        return tuple(outs)
+
+    def dleq_public_key(self, key):
+        return self.engines[0].dleq_public_key(key)
+
+    def dleq_prove(self, key, blinded32, evaluated32, nonces, group_size=None, dst=b"", comb=None, out=None, status=None):
+        b, z, r = _host(blinded32, 32, np.uint8), _host(evaluated32, 32, np.uint8), _host(nonces, 4)
+        self._same_len(b, z)
+        groups, group_size = Engine._groups(len(b), max(len(b), 1) if group_size is None else group_size)
+        if len(r) != groups:
+            raise ValueError("one nonce per group")
+        return self._sharded_groups(lambda e, b, z, r, o, st: e.dleq_prove(key, b, z, r, group_size, dst, comb, out=o, status=st), [b, z], [r],
+                                    [_out(out, groups, 64, np.uint8), _out(status, groups, None, np.uint8)], group_size)
+
+    def dleq_verify(self, pk32, blinded32, evaluated32, proofs64, group_size=None, dst=b"", comb=None, ok=None, status=None):
+        b, z, p = _host(blinded32, 32, np.uint8), _host(evaluated32, 32, np.uint8), _host(proofs64, 64, np.uint8)
+        self._same_len(b, z)
+        groups, group_size = Engine._groups(len(b), max(len(b), 1) if group_size is None else group_size)
+        if len(p) != groups:
+            raise ValueError("one proof per group")
+        return self._sharded_groups(lambda e, b, z, p, o, st: e.dleq_verify(pk32, b, z, p, group_size, dst, comb, ok=o, status=st), [b, z], [p],
+                                    [_out(ok, groups, None, np.uint8), _out(status, groups, None, np.uint8)], group_size)
+
     # ---- wire format ----------------------------------------------------------------------------------------------
     def encode(self, points_affine, out=None):
         p = _host(points_affine, 8)

@@ -509,6 +509,65 @@ int fourq_scalar_inv_batch_dev(fourq_ctx *ctx, const uint64_t *scalars, uint64_t
  * by batch size again (results do not depend on it).  FOURQ_ERR_INVALID unless the process runs with FOURQ_DEBUG_ROUTES=1. */
 int fourq_ctx_set_scinv_group(fourq_ctx *ctx, int k);
 
+/* ---- oblivious PRF: proofs -- a batched Chaum-Pedersen (DLEQ) proof that a batch was evaluated with the key behind a public key -----------------
+ * What a VERIFIABLE oblivious PRF adds (RFC 9497 section 2.2, the shape Privacy Pass uses): the server proves that every evaluated element
+ * of a group is the blinded one multiplied by the key of its published public key, without showing the key.  groups x group_size rows laid
+ * out group after group, as fourq_msm_*; ONE proof per group, so a server answers many small requests (down to one row per proof) in one call.
+ * Suite.  Like the OPRF's, the suite is this library's own (RFC 9497 registers none for FourQ); the yardstick is the CPU restatement
+ * tests/dleq_ref.py and the fixture tests/golden/dleq.json made with the reference's point functions.
+ * Notation.  Gen = (Gx, Gy) the generator, N the group order, k the server's key (4 words, any value in [0, 2^256)), K = 392 k mod N the
+ * scalar DH_endo really multiplies by (its cofactor clearing, curve4q.py:446-462: evaluated = [K]blinded), H = SHA-512, LE(x) the
+ * little-endian integer of a byte string, dst 1..FOURQ_H2C_MAX_DST bytes, tail(L) = L || dst || I2OSP(len(dst), 1) (the shape of F's tail).
+ *   public key   pk32 = encode(DH_endo(k, Gen)): what fourq_oprf_evaluate_batch returns for the one row encode(Gen)
+ *   rows         row i = (g, j), j < group_size:  C_i = blinded32[i], D_i = evaluated32[i], 32-byte encodings
+ *   d_i          = LE(H(pk32 || C_i || D_i || I2OSP(j, 4) || tail("Composite"))) mod N: 100 fixed bytes, then the tail; j is the index
+ *                INSIDE the group, so a group's proof does not depend on where in the batch the group stands
+ *   composites   M_g = sum_j [d_gj]decode(C_gj);  verifier: Z_g = sum_j [d_gj]decode(D_gj);  prover: Z_g = DH_endo(k, M_g) -- one
+ *                multiplication per group: the prover hashes D and never decodes it.  M32 = encode(M_g), Z32 = encode(Z_g).
+ *   prove        r = nonces[g] mod N (from the caller, like the blinds: there is no RNG in this library; uniformly random, never reused);
+ *                t2 = encode([r]Gen);  t3 = encode(R1toAffine(MUL_endo(r, AffineToR1(M_g))));
+ *                c = LE(H(pk32 || M32 || Z32 || t2 || t3 || tail("Challenge"))) mod N;  s = (r - c K) mod N;  proof64[g] = LE32(c) || LE32(s)
+ *   verify       t2' = encode([s]Gen + [c]decode(pk32))   (fourq_double_mul_bytes_batch with pk32 on every group's row);
+ *                t3' = encode([s]M_g + [c]Z_g)            (fourq_msm_bytes_batch over the groups of two (s, M32), (c, Z32));
+ *                ok[g] = (LE(H(pk32 || M32 || Z32 || t2' || t3' || tail("Challenge"))) mod N == c)
+ * status, one byte per group; the group's output row is all zero, and ok is 0, unless it is 0.  A bad group never affects another.
+ *   prove        FOURQ_BYTES_DECODE_BASE + the LARGEST FOURQ_DECODE_* among the group's C rows; else FOURQ_DH_NEUTRAL when k = 0 (mod N);
+ *                else FOURQ_DLEQ_NONCE_ZERO when r = 0 (mod N).  An evaluated row that does not decode does not stop the prover.
+ *   verify       FOURQ_BYTES_DECODE_BASE + the largest decode code among the group's C and D rows and pk32 (a pk32 that does not decode
+ *                marks every group); else FOURQ_SIG_S_RANGE when LE(c) >= N or LE(s) >= N; else 0, and ok is the comparison.
+ *   composites   the decode part of verify's, without pk32 (it is only hashed there); M32 and Z32 are both zero unless it is 0.
+ *   A composite that comes out as the NEUTRAL point is refused by the next stage's decode, FOURQ_BYTES_DECODE_BASE +
+ *   FOURQ_DECODE_REF_ATTRIBUTE_ERROR (prove, verify; composites hands out its encoding 01 00 .. 00): it takes an accident of the kind of a
+ *   hash collision -- or blinded elements outside the subgroup of order N, for which DH_endo may also report FOURQ_DH_NEUTRAL.
+ * Secrets.  k, K and r meet no branch and no address that depends on their value in the proofs' own kernels (reductions, one product, the
+ * mul-sub, masked statuses); in the ladders and the comb that holds under fourq_ctx_set_ct_select, as everywhere.  d, M, Z and c are public.
+ * Arguments.  `key`, `pk32` and `dst` are HOST pointers in both flavours (they travel in kernel arguments); `comb` is the generator's comb
+ * or NULL = the staged one, as in fourq_sig_*.  groups == 0: FOURQ_OK, nothing touched.  group_size == 0 with groups > 0, or groups *
+ * group_size (overflow-checked) above FOURQ_MAX_BATCH -- for verify and reserve also 2 * groups, the rows of its sum of two --:
+ * FOURQ_ERR_INVALID.  _dev array pointers are 16-byte aligned (ok and status need not be); nothing is staged before the arguments are accepted.
+ * Work buffer.  The inner calls carve their own layouts; this call's regions lie behind the largest of them (dleq_layout.h), which is MORE
+ * than fourq_ctx_reserve sizes: fourq_dleq_reserve(groups, group_size) is the reservation for these calls.  After it a _dev call of at
+ * most that shape allocates and synchronises nothing and, with the comb staged, can be captured.  The host-array calls are synchronous --
+ * copy in, the _dev call, copy out -- without chunks, as fourq_msm_*: the outputs are per group.
+ * Cost (not measured into this text; profiles/dleq_timing.txt): prove is one decode + ladder per row and three multiplications per group
+ * (comb, DH_endo, MUL_endo); verify two per row and four per group ([s]G + [c]pk counts two, the sum of two counts two). */
+#define FOURQ_DLEQ_NONCE_ZERO 80      /* status of prove: the nonce is 0 mod N (s would be -c K: the proof would hand out the key) */
+int fourq_dleq_reserve(fourq_ctx *ctx, size_t groups, size_t group_size);
+/* the verifier's composites: m32, z32 groups x 32 bytes */
+int fourq_dleq_composites(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *pk32, const uint8_t *blinded32,
+                          const uint8_t *evaluated32, uint8_t *m32, uint8_t *z32, uint8_t *status, size_t groups, size_t group_size);
+int fourq_dleq_composites_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *pk32, const uint8_t *blinded32,
+                              const uint8_t *evaluated32, uint8_t *m32, uint8_t *z32, uint8_t *status, size_t groups, size_t group_size);
+/* nonces: groups x 4 words; proof64: groups x 64 bytes */
+int fourq_dleq_prove(fourq_ctx *ctx, const uint64_t *key, const uint64_t *comb, const uint8_t *dst, size_t dst_len, const uint8_t *blinded32,
+                     const uint8_t *evaluated32, const uint64_t *nonces, uint8_t *proof64, uint8_t *status, size_t groups, size_t group_size);
+int fourq_dleq_prove_dev(fourq_ctx *ctx, const uint64_t *key, const uint64_t *comb, const uint8_t *dst, size_t dst_len, const uint8_t *blinded32,
+                         const uint8_t *evaluated32, const uint64_t *nonces, uint8_t *proof64, uint8_t *status, size_t groups, size_t group_size);
+int fourq_dleq_verify(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb, const uint8_t *dst, size_t dst_len, const uint8_t *blinded32,
+                      const uint8_t *evaluated32, const uint8_t *proof64, uint8_t *ok, uint8_t *status, size_t groups, size_t group_size);
+int fourq_dleq_verify_dev(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb, const uint8_t *dst, size_t dst_len, const uint8_t *blinded32,
+                          const uint8_t *evaluated32, const uint8_t *proof64, uint8_t *ok, uint8_t *status, size_t groups, size_t group_size);
+
 /* ---- primitives (one reference function per op, batched) --------------------------------------
  * Used by the Python mirror of the reference's helper API (GFp.*, GFp2.*, DBL, ADD, phi, ...) and by
  * the parity tests to check every layer of the path on the GPU.  in/out are HOST pointers;
