@@ -2,7 +2,7 @@
 missing GPU is an error, never a silent CPU path."""
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_int, c_size_t, c_uint8, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_int, c_size_t, c_uint, c_uint8, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FOURQ_AMD_LIB") or os.path.join(HERE, "libfourq_amd.so")   # override: experiments only
@@ -117,6 +117,12 @@ PROTOTYPES = {
     "fourq_msm_affine_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_msm_bytes_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_msm_bytes_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_bucketsum_window": (c_int, [c_size_t]),
+    "fourq_bucketsum_reserve": (c_int, [c_void_p, c_size_t, c_size_t, c_uint]),
+    "fourq_bucketsum_affine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),
+    "fourq_bucketsum_affine_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),
+    "fourq_bucketsum_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),
+    "fourq_bucketsum_bytes_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),
     "fourq_sha512_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_sha512_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_sig_keygen_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),

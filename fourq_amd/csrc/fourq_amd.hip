@@ -1941,6 +1941,74 @@ FQ_API int fourq_msm_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint
 FQ_API int fourq_msm_affine_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size) { return msm_host(c, s, p, false, o, nullptr, groups, group_size); }
 FQ_API int fourq_msm_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return msm_host(c, s, p, true, o, st, groups, group_size); }
 
+// ---- the same sums by the bucket method (bucket.hip.h, bucket_layout.h): same arrays, same bytes, another route -------------------------
+// window 0: the window measured fastest for the group size, or the ladder route where no window beat it by more than msm_dev's own run-to-run
+// spread (profiles/bucket_sum_timing.txt: the ladder route up to one group of 2^18, 1.10 of it there; window 11 at 2^19, 0.72, and at 2^20,
+// 0.52).  The threshold is the smallest MEASURED group size at which a window won; the table is indexed by group_size alone.
+static const struct { size_t from; int window; } BUCKET_WINDOWS[] = { { 0, 0 }, { (size_t)1 << 19, 11 } };      // { smallest group_size, window }, ascending
+FQ_API int fourq_bucketsum_window(size_t group_size) {
+    int window = 0;
+    for (const auto& row : BUCKET_WINDOWS) if (group_size >= row.from) window = row.window;
+    return window;
+}
+static bool bucket_window_ok(unsigned window) { return window == 0 || fq_work::BucketGeom::window_ok(window); }
+FQ_API int fourq_bucketsum_reserve(fourq_ctx* c, size_t groups, size_t group_size, unsigned window) {
+    size_t n;
+    if (!c || !bucket_window_ok(window)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    if (!window) window = (unsigned)fourq_bucketsum_window(group_size);
+    if (!window) return reserve_for<fq_work::Msm>(c, n);
+    return ensure_work(c, fq_work::Bucket::bytes(groups, group_size, window));
+}
+// In constant-time selection mode the ladder route runs whatever the window is: a bucket's address is a digit of a scalar.
+static int bucket_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size, unsigned window) {
+    size_t n;
+    if (!c || !scalars || !points || !out || (encoded && !status) || !bucket_window_ok(window)) return FOURQ_ERR_INVALID;
+    if (!aligned16(scalars) || !aligned16(points) || !aligned16(out)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    if (!window) window = (unsigned)fourq_bucketsum_window(group_size);
+    if (c->ct || !window) return msm_dev(c, scalars, points, encoded, out, status, groups, group_size);
+    int rc = ensure_work(c, fq_work::Bucket::bytes(groups, group_size, window));
+    if (rc) return rc;
+    const fq_work::Bucket w(c->work, groups, group_size, window);
+    if (encoded) {
+        hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)points, w.affine, w.st_decode, (u32)n);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIPRC_TRY(c, chain_launch_bucket_sum(c->stream, w, scalars, encoded ? w.affine : (const u64*)points, encoded ? w.st_decode : nullptr));
+    return launch_lower(c, encoded, w.sum, 12, w.st_sum, (uint64_t*)out, status, groups);
+}
+// Host arrays, as msm_host: copy in, the _dev call, copy out, in one piece.
+static int bucket_host(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size, unsigned window) {
+    size_t n;
+    if (!c || !scalars || !points || !out || (encoded && !status) || !bucket_window_ok(window)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    const size_t point_bytes = encoded ? 32 : 64;
+    int rc = ensure_stage(c, n * (32 + point_bytes) + groups * (point_bytes + 1));
+    if (rc) return rc;
+    char* d_scalars = (char*)c->stage;
+    char* d_points = d_scalars + n * 32;
+    char* d_out = d_points + n * point_bytes;
+    char* d_status = d_out + groups * point_bytes;
+    HIP_TRY(c, hipMemcpyAsync(d_scalars, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_points, points, n * point_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = bucket_dev(c, (const uint64_t*)d_scalars, d_points, encoded, d_out, encoded ? (uint8_t*)d_status : nullptr, groups, group_size, window))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, groups * point_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (encoded) HIP_TRY(c, hipMemcpyAsync(status, d_status, groups, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FOURQ_OK;
+}
+FQ_API int fourq_bucketsum_affine_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size, unsigned window) { return bucket_dev(c, s, p, false, o, nullptr, groups, group_size, window); }
+FQ_API int fourq_bucketsum_bytes_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) { return bucket_dev(c, s, p, true, o, st, groups, group_size, window); }
+FQ_API int fourq_bucketsum_affine(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size, unsigned window) { return bucket_host(c, s, p, false, o, nullptr, groups, group_size, window); }
+FQ_API int fourq_bucketsum_bytes(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) { return bucket_host(c, s, p, true, o, st, groups, group_size, window); }
+
 // ---- signatures from bytes (include/fourq_amd.h): SHA-512 and the arithmetic modulo N on the device (sig.hip.h) around the comb, the
 // ladder and the combiner.  Every intermediate -- H(sk), the nonce, the challenge, s / h / R as rows -- lives in the context's work buffer.
 static bool sig_msgs_dev_ok(const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len) {

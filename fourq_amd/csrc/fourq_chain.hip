@@ -1,13 +1,14 @@
 // Second translation unit of libfourq_amd.so: the kernels that profit from chained carries (FQ_CHAIN=1, see
 // kernels.hip.h): fixed-base ladders (table in LDS), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
 // translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P,
-// msm.hip.h the one that folds the ladder's rows of a group into one.
+// msm.hip.h the one that folds the ladder's rows of a group into one, bucket.hip.h the bucket route of the same sums.
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
 #endif
 #include "kernels.hip.h"
 #include "combine.hip.h"
 #include "msm.hip.h"
+#include "bucket.hip.h"
 
 namespace fq {
 

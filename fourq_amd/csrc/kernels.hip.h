@@ -19,6 +19,7 @@
 #include "ladder_asm.hip.h"
 #include "recode.hip.h"
 #include "pair.hip.h"
+#include "bucket_layout.h"
 
 namespace fq {
 
@@ -1114,6 +1115,8 @@ int chain_launch_combine(int k, int out_kind, hipStream_t stream, const uint4* p
 // st_in (NULL: none) / st_out: one raw decode code per row, folded as a maximum
 constexpr u32 MSM_FOLD = 64;
 int chain_launch_msm_fold(hipStream_t stream, const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out, size_t groups, size_t m_in);
+// bucket.hip.h: the grouped sums by the bucket method, from the sub-scalars to one projective row (and decode code) per group in w.sum / w.st_sum
+int chain_launch_bucket_sum(hipStream_t stream, const fq_work::Bucket& w, const u64* scalars, const u64* points_affine, const uint8_t* st_decode);
 // constant-time selection builds of the same kernels: fourq_ct_fused.hip (FQ_CHAIN=0) and fourq_ct_chain.hip (FQ_CHAIN=1)
 int ct_launch_fused(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);
 int ct_launch_pair(int algo, bool dh, bool fixed, bool quad, unsigned grid, hipStream_t stream, const LadderArgs& a);

@@ -412,6 +412,44 @@ class Engine:
     def msm_bytes_dev(self, scalars, points32, out32, status, groups, group_size):
         self._ck(self._lib.fourq_msm_bytes_batch_dev(self._ctx, _ptr(scalars), _ptr(points32), _ptr(out32), _ptr(status), groups, group_size))
 
+    # ---- the same sums by the bucket method (fourq_bucketsum_*): same arrays, same bytes, for large groups ----------------------------
+    # window: 0 = the library picks (bucket_sum_window; the ladder route where no window beat it), 4..12 = the bucket route with that window.
+    # With ct_select on the ladder route runs whatever the window is (a bucket's address is a digit of a scalar).
+    def bucket_sum_window(self, group_size):
+        """What window=0 stands for at this group size: 0 (the ladder route, msm) or 4..12."""
+        return int(self._lib.fourq_bucketsum_window(int(group_size)))
+
+    def bucket_sum_reserve(self, groups, group_size, window=0):
+        """Size the work buffer for `bucket_sum*_dev` calls of this shape and window (fourq_bucketsum_reserve; reserve() is not enough
+        for them): such calls then only enqueue."""
+        self._ck(self._lib.fourq_bucketsum_reserve(self._ctx, int(groups), int(group_size), int(window)))
+
+    def bucket_sum(self, scalars, points_affine, group_size, window=0, out=None):
+        """msm()'s result, byte for byte, by the bucket method."""
+        k, p = _host(scalars, 4), _host(points_affine, 8)
+        if len(k) != len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        groups, group_size = self._groups(len(k), group_size)
+        out = _out(out, groups, 8)
+        self._ck(self._lib.fourq_bucketsum_affine(self._ctx, _ptr(k), _ptr(p), _ptr(out), groups, group_size, int(window)))
+        return out
+
+    def bucket_sum_bytes(self, scalars, points32, group_size, window=0, out=None, status=None):
+        """msm_bytes()'s (out32, status), byte for byte, by the bucket method."""
+        k, p = _host(scalars, 4), _host(points32, 32, np.uint8)
+        if len(k) != len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        groups, group_size = self._groups(len(k), group_size)
+        out, status = _out(out, groups, 32, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_bucketsum_bytes(self._ctx, _ptr(k), _ptr(p), _ptr(out), _ptr(status), groups, group_size, int(window)))
+        return out, status
+
+    def bucket_sum_dev(self, scalars, points_affine, out_affine, groups, group_size, window=0):
+        self._ck(self._lib.fourq_bucketsum_affine_dev(self._ctx, _ptr(scalars), _ptr(points_affine), _ptr(out_affine), groups, group_size, int(window)))
+
+    def bucket_sum_bytes_dev(self, scalars, points32, out32, status, groups, group_size, window=0):
+        self._ck(self._lib.fourq_bucketsum_bytes_dev(self._ctx, _ptr(scalars), _ptr(points32), _ptr(out32), _ptr(status), groups, group_size, int(window)))
+
     # ---- signatures from bytes (fourq_sha512_* / fourq_sig_*): SHA-512 and the arithmetic modulo N run on the device -------------
     @staticmethod
     def _msgs(msgs, lens, n=None):

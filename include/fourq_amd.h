@@ -364,6 +364,41 @@ int fourq_msm_bytes_batch(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t
 int fourq_msm_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status,
                               size_t groups, size_t group_size);
 
+/* ---- sums across elements: the bucket route ---------------------------------------------------------------------------------------------
+ * The same arrays and, byte for byte, the same outputs and status as fourq_msm_affine_batch / fourq_msm_bytes_batch above -- the neutral
+ * as an ordinary result, FOURQ_BYTES_DECODE_BASE + the largest FOURQ_DECODE_* per group, a zero row for such a group, its neighbours
+ * untouched -- by the bucket method (Pippenger) instead of one ladder per element: for large groups.  Scalars: any value in [0, 2^256).
+ *
+ * The identity behind it: decompose(k) gives v_0..v_3 < 2^64 with MUL_endo(k, P) = [v_0]P + [v_1]phi(P) + [v_2]psi(P) + [v_3]psi(phi(P)),
+ * and phi, psi are homomorphisms, so  sum_i MUL_endo(k_i, P_i) = S_0 + phi(S_1) + psi(S_2) + psi(phi(S_3))  with  S_j = sum_i [v_j(k_i)]P_i:
+ * four 64-bit bucket sums over the same points and three endomorphisms per GROUP.  It holds for every point the ladder route accepts, points
+ * outside the order-N subgroup included (where MUL_endo(k, P) is not [k]P), which is why the bytes are the ladder route's.
+ *
+ * window: 0 = the library picks, by group_size, from a table measured on the device (profiles/bucket_sum_timing.txt), and runs the ladder
+ * route (fourq_msm_*_dev) where no window beat it; 4..12 = the bucket route with windows of that many bits, at any group size; anything
+ * else FOURQ_ERR_INVALID.  fourq_bucketsum_window(group_size) is what 0 stands for: 0 (the ladder route) or 4..12.
+ * With constant-time selection on (fourq_ctx_set_ct_select) every call runs the ladder route whatever the window is: a bucket's address
+ * is a digit of a scalar, and the scalars of a commitment are secrets; the bytes are the same either way.  (In the default mode the
+ * ladders use digits as addresses too, so the bucket route gives up nothing more.)
+ *
+ * Argument rules as fourq_msm_*: groups == 0 is FOURQ_OK and touches nothing; group_size == 0 with groups > 0, or groups * group_size above
+ * FOURQ_MAX_BATCH, FOURQ_ERR_INVALID; _dev: every array pointer 16-byte aligned (status need not be).  The intermediates -- per group
+ * 4 * ceil(64 / window) columns of 2^window - 1 buckets, and one index per element and column -- live in the context's work buffer BEHIND
+ * what fourq_msm_* keeps there; fourq_ctx_reserve does not cover them.  fourq_bucketsum_reserve(ctx, groups, group_size, window) does:
+ * after it a _dev call of that shape and window (or, with the same window, of no more groups and no larger groups) allocates and
+ * synchronises nothing, and the geometry of every launch, pass counts included, follows from (groups, group_size, window) on the host.
+ * The host-array calls copy in, run and copy out in one piece, as fourq_msm_* do. */
+int fourq_bucketsum_window(size_t group_size);
+int fourq_bucketsum_reserve(fourq_ctx *ctx, size_t groups, size_t group_size, unsigned window);
+int fourq_bucketsum_affine(fourq_ctx *ctx, const uint64_t *scalars, const uint64_t *points_affine, uint64_t *out_affine, size_t groups,
+                           size_t group_size, unsigned window);
+int fourq_bucketsum_affine_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint64_t *points_affine, uint64_t *out_affine, size_t groups,
+                               size_t group_size, unsigned window);
+int fourq_bucketsum_bytes(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status, size_t groups,
+                          size_t group_size, unsigned window);
+int fourq_bucketsum_bytes_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status,
+                              size_t groups, size_t group_size, unsigned window);
+
 /* ---- signatures from bytes: SchnorrQ-shaped sign / verify with SHA-512 and the arithmetic modulo N on the device ---------------------
  * Nothing but byte arrays crosses the ABI -- secret keys, public keys, messages, signatures, one ok and one status byte per row -- and no
  * intermediate (the hash of the secret key, the nonce, the challenge, R as a point) is ever on the host.  With H = SHA-512, LE(x) the
