@@ -123,6 +123,14 @@ PROTOTYPES = {
     "fourq_bucketsum_affine_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),
     "fourq_bucketsum_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),
     "fourq_bucketsum_bytes_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),
+    "fourq_commit_bases_set": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "fourq_commit_bases_count": (c_int, [c_void_p, POINTER(c_size_t)]),
+    "fourq_commit_route": (c_int, [c_size_t]),
+    "fourq_commit_reserve": (c_int, [c_void_p, c_size_t, c_size_t]),
+    "fourq_commit_affine": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_int]),
+    "fourq_commit_affine_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_int]),
+    "fourq_commit_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_int]),
+    "fourq_commit_bytes_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_int]),
     "fourq_sha512_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_sha512_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_sig_keygen_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),

@@ -472,6 +472,8 @@ struct fourq_ctx {
     u64* table_packed = nullptr;   // 128 words
     u32* comb_limbs = nullptr;     // FOURQ_COMB_POINTS x 36 working limbs of the staged comb table
     u64* comb_packed = nullptr;    // FOURQ_COMB_POINTS x 12 words
+    u32* commit_combs = nullptr;   // fourq_commit_bases_set: commit_count combs of COMB_POINTS x COMB_ENTRY_U32 working limbs, back to back
+    size_t commit_count = 0;
     uint64_t table_shadow[FOURQ_TABLE_WORDS];   // host copies of what table_limbs / comb_limbs currently hold
     uint64_t comb_shadow[FOURQ_COMB_WORDS];
     bool table_staged = false, comb_staged = false;
@@ -1356,7 +1358,7 @@ FQ_API int fourq_ctx_destroy(fourq_ctx* c) {
     DeviceGuard g(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     for (void* p : { (void*)c->scratch, (void*)c->proj, (void*)c->table_limbs, (void*)c->table_packed, (void*)c->part_counter, (void*)c->part_list,
-                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, c->stage, (void*)c->work, (void*)c->pipe_dev })
+                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, (void*)c->commit_combs, c->stage, (void*)c->work, (void*)c->pipe_dev })
         if (p) (void)hipFree(p);
     if (c->pipe_pin) (void)hipHostFree(c->pipe_pin);
     if (c->zero_copy) (void)hipHostFree(c->zero_copy);
@@ -2008,6 +2010,115 @@ FQ_API int fourq_bucketsum_affine_dev(fourq_ctx* c, const uint64_t* s, const uin
 FQ_API int fourq_bucketsum_bytes_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) { return bucket_dev(c, s, p, true, o, st, groups, group_size, window); }
 FQ_API int fourq_bucketsum_affine(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size, unsigned window) { return bucket_host(c, s, p, false, o, nullptr, groups, group_size, window); }
 FQ_API int fourq_bucketsum_bytes(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) { return bucket_host(c, s, p, true, o, st, groups, group_size, window); }
+
+// ---- commitments over a fixed generator set (commit.hip.h, commit_layout.h): out[g] = sum_j [k_gj]B_j, one comb per generator ------------
+static_assert(fq_work::Commit::FOLD == MSM_FOLD, "commit_layout.h sizes the fold regions for msm_fold_kernel's segment");
+// One comb per base, built where the single comb is (comb_table_kernel over the context's scratch slots, comb_unpack_kernel) and written
+// into a NEW array: the old set is replaced only once the new one is complete, so a failure keeps it.  The staged single comb
+// (comb_limbs, its shadow) is not touched; comb_packed is only the bounce row between the two kernels, as in fourq_comb_table.
+FQ_API int fourq_commit_bases_set(fourq_ctx* c, const uint64_t* points_affine, size_t m) {
+    if (!c || !points_affine || m == 0 || m > FOURQ_COMMIT_MAX_BASES) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    if (int rc = staging_allowed(c)) return rc;
+    if (int rc = ensure_stage(c, m * (64 + 160))) return rc;
+    u64* affine = (u64*)c->stage;
+    u64* r1 = affine + 8 * m;
+    u32* combs = nullptr;
+    hipError_t e = hipMalloc(&combs, m * COMB_POINTS * COMB_ENTRY_U32 * sizeof(u32));
+    if (e != hipSuccess) return fail(c, e, "hipMalloc(the combs of the generator set)");
+    auto build = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(affine, points_affine, m * 64, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(lift_affine_kernel, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, affine, r1, (u32)m);
+        HIP_TRY(c, hipGetLastError());
+        for (size_t j = 0; j < m; j++) {
+            hipLaunchKernelGGL(comb_table_kernel, dim3((COMB_POINTS + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, (const u64*)(r1 + 20 * j), c->scratch, c->comb_packed);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(comb_unpack_kernel, dim3((COMB_POINTS + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->comb_packed, combs + j * COMB_POINTS * COMB_ENTRY_U32);
+            HIP_TRY(c, hipGetLastError());
+        }
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return FOURQ_OK;
+    };
+    if (int rc = build()) { (void)hipStreamSynchronize(c->stream); (void)hipFree(combs); return rc; }
+    if (c->commit_combs) (void)hipFree(c->commit_combs);      // the stream is idle: nothing reads the old set any more
+    c->commit_combs = combs;
+    c->commit_count = m;
+    return FOURQ_OK;
+}
+FQ_API int fourq_commit_bases_count(const fourq_ctx* c, size_t* m) {
+    if (!c || !m) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    *m = c->commit_count;
+    return FOURQ_OK;
+}
+// route 0: the staged route from the smallest MEASURED number of groups at which it beat the gather route by more than the spread of msm_dev's
+// own timings (profiles/commit_timing.txt: 1024 x 64, 0.1460 against 0.1494 ms, 2.3 % with a spread of 2.0 %; at 32768 x 2 and 65536 x 1 the two
+// are within the spread, at 64 x 1024 and 1 x 4096 the gather route is 2.8 and 44 times faster), the gather route below; the table is indexed
+// by `groups` alone, as BUCKET_WINDOWS is by group_size.
+static const struct { size_t from; int route; } COMMIT_ROUTES[] = { { 0, 2 }, { 1024, 1 } };      // { smallest groups, route }, ascending
+FQ_API int fourq_commit_route(size_t groups) {
+    int route = 2;
+    for (const auto& row : COMMIT_ROUTES) if (groups >= row.from) route = row.route;
+    return route;
+}
+FQ_API int fourq_commit_reserve(fourq_ctx* c, size_t groups, size_t group_size) {
+    size_t n;
+    if (!c) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    return ensure_work(c, fq_work::Commit::bytes(groups, group_size));
+}
+// The combs into w.rows, the fold passes of the grouped sums until one row per group is left, the lowering: affine words, or the encoding.
+static int commit_dev(fourq_ctx* c, const uint64_t* scalars, void* out, bool encoded, size_t groups, size_t group_size, int route) {
+    size_t n;
+    if (!c) return FOURQ_ERR_INVALID;
+    if (!scalars || !out || route < 0 || route > 2) return FOURQ_ERR_INVALID;
+    if (!aligned16(scalars) || !aligned16(out)) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (group_size == 0 || group_size > c->commit_count || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;     // no set: count 0
+    if (!route) route = fourq_commit_route(groups);
+    int rc = ensure_work(c, fq_work::Commit::bytes(groups, group_size));
+    if (rc) return rc;
+    const fq_work::Commit w(c->work, groups, group_size);
+    if (c->ct) HIPRC_TRY(c, ct_launch_commit((unsigned)(c->lanes_w4 / BLOCK), c->stream, scalars, c->commit_combs, w.rows, groups, group_size));
+    else HIPRC_TRY(c, chain_launch_commit(route, (unsigned)c->cus, c->stream, scalars, c->commit_combs, w.rows, groups, group_size));
+    const uint64_t* rows = w.rows;
+    bool to_a = true;
+    for (size_t m = group_size; m > 1; to_a = !to_a) {
+        uint64_t* part = to_a ? w.part_a : w.part_b;
+        HIPRC_TRY(c, chain_launch_msm_fold(c->stream, rows, 12, nullptr, part, nullptr, groups, m));
+        m = (m + MSM_FOLD - 1) / MSM_FOLD;
+        rows = part;
+    }
+    if (!encoded) return launch_lower(c, false, rows, 12, nullptr, (uint64_t*)out, nullptr, groups);
+    HIP_TRY(c, hipMemsetAsync(w.st_zero, 0, groups, c->stream));
+    return launch_lower(c, true, rows, 12, w.st_zero, (uint64_t*)out, w.st_out, groups);
+}
+// Host arrays, as msm_host: copy in, the _dev call, copy out, in one piece.
+static int commit_host(fourq_ctx* c, const uint64_t* scalars, void* out, bool encoded, size_t groups, size_t group_size, int route) {
+    size_t n;
+    if (!c) return FOURQ_ERR_INVALID;
+    if (!scalars || !out || route < 0 || route > 2) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (group_size == 0 || group_size > c->commit_count || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    const size_t point_bytes = encoded ? 32 : 64;
+    int rc = ensure_stage(c, n * 32 + groups * point_bytes);
+    if (rc) return rc;
+    char* d_scalars = (char*)c->stage;
+    char* d_out = d_scalars + n * 32;
+    HIP_TRY(c, hipMemcpyAsync(d_scalars, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
+    if ((rc = commit_dev(c, (const uint64_t*)d_scalars, d_out, encoded, groups, group_size, route))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, groups * point_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FOURQ_OK;
+}
+FQ_API int fourq_commit_affine_dev(fourq_ctx* c, const uint64_t* s, uint64_t* o, size_t groups, size_t group_size, int route) { return commit_dev(c, s, o, false, groups, group_size, route); }
+FQ_API int fourq_commit_bytes_dev(fourq_ctx* c, const uint64_t* s, uint8_t* o, size_t groups, size_t group_size, int route) { return commit_dev(c, s, o, true, groups, group_size, route); }
+FQ_API int fourq_commit_affine(fourq_ctx* c, const uint64_t* s, uint64_t* o, size_t groups, size_t group_size, int route) { return commit_host(c, s, o, false, groups, group_size, route); }
+FQ_API int fourq_commit_bytes(fourq_ctx* c, const uint64_t* s, uint8_t* o, size_t groups, size_t group_size, int route) { return commit_host(c, s, o, true, groups, group_size, route); }
 
 // ---- signatures from bytes (include/fourq_amd.h): SHA-512 and the arithmetic modulo N on the device (sig.hip.h) around the comb, the
 // ladder and the combiner.  Every intermediate -- H(sk), the nonce, the challenge, s / h / R as rows -- lives in the context's work buffer.

@@ -1,7 +1,8 @@
 // Second translation unit of libfourq_amd.so: the kernels that profit from chained carries (FQ_CHAIN=1, see
 // kernels.hip.h): fixed-base ladders (table in LDS), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
 // translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P,
-// msm.hip.h the one that folds the ladder's rows of a group into one, bucket.hip.h the bucket route of the same sums.
+// msm.hip.h the one that folds the ladder's rows of a group into one, bucket.hip.h the bucket route of the same sums, commit.hip.h the combs of a
+// fixed generator set.
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
 #endif
@@ -9,6 +10,7 @@
 #include "combine.hip.h"
 #include "msm.hip.h"
 #include "bucket.hip.h"
+#include "commit.hip.h"
 
 namespace fq {
 
@@ -31,6 +33,7 @@ int chain_launch_ladder(int algo, bool dh, unsigned grid, hipStream_t stream, co
 int chain_setup_device() {
     hipError_t e = hipFuncSetAttribute((const void*)comb_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMB_FAST_LDS_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)comb_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMB_FAST_LDS_BYTES);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)commit_kernel<COMMIT_STAGED, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMB_FAST_LDS_BYTES);
     return (int)e;
 }
 // One block per CU holds the whole 144 KB table; its width follows the batch so that a small batch still reaches every CU.
@@ -77,6 +80,19 @@ int chain_launch_msm_fold(hipStream_t stream, const u64* rows, u32 stride, const
     if (blocks == 0 || blocks > 0x7fffffffu || m_in > 0xffffffffu) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(msm_fold_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, stream, rows, stride, st_in, rows_out, st_out, (u32)m_in, (u32)m_out, team,
                        (u32)((segment + team - 1) / team), teams);
+    return (int)hipGetLastError();
+}
+// The combs of a commitment (commit.hip.h): row g * group_size + j from comb j, canonical (X, Y, Z) rows.  route: COMMIT_STAGED or COMMIT_GATHER
+int chain_launch_commit(int route, unsigned cus, hipStream_t stream, const u64* scalars, const u32* combs, u64* rows, size_t groups, size_t group_size) {
+    if (route == COMMIT_GATHER) {
+        const size_t blocks = (groups * group_size + BLOCK - 1) / BLOCK;
+        if (blocks > 0x7fffffffu) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL((commit_kernel<COMMIT_GATHER, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, stream, scalars, combs, rows, (u32)groups, (u32)group_size, 0u, 0u);
+        return (int)hipGetLastError();
+    }
+    const fq_work::CommitGeom geom(groups, group_size, cus, COMB_BLOCK_MAX);
+    hipLaunchKernelGGL((commit_kernel<COMMIT_STAGED, false>), dim3(geom.grid), dim3(geom.width), COMB_FAST_LDS_BYTES, stream, scalars, combs, rows, (u32)groups, (u32)group_size,
+                       (u32)geom.slices, (u32)geom.items);
     return (int)hipGetLastError();
 }
 

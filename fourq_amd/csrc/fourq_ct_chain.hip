@@ -1,10 +1,12 @@
 // Fourth translation unit of libfourq_amd.so: the fixed-base (LDS) ladders, the comb and the tail of a mixed round (prep_kernel +
 // mixed_ct_tail_kernel) with CONSTANT-TIME table selection (FOURQ_CT_SELECT / fourq_ctx_set_ct_select).  Same build flavour as fourq_chain.hip
 // (FQ_CHAIN=1): every entry of the shared table is read by every lane at every step (same addresses across the wave: LDS broadcasts).
+// commit.hip.h adds the combs of a fixed generator set in the same mode.
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
 #endif
 #include "kernels.hip.h"
+#include "commit.hip.h"
 
 namespace fq {
 
@@ -41,6 +43,14 @@ int ct_launch_mixed_tail(unsigned prep_grid, unsigned tail_grid, hipStream_t str
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(mixed_ct_tail_kernel<0>, dim3(tail_grid), dim3(BLOCK), 0, stream, a, fix_list, var_list, counts, over_scratch);
+    return (int)hipGetLastError();
+}
+// The combs of a commitment with constant-time selection (commit.hip.h): the staged structure over the 80-point shape, whatever the route
+int ct_launch_commit(unsigned blocks_max, hipStream_t stream, const u64* scalars, const u32* combs, u64* rows, size_t groups, size_t group_size) {
+    constexpr size_t lds_bytes = (size_t)CombScan::POINTS * COMB_LDS_U32 * sizeof(u32);
+    const fq_work::CommitGeom geom(groups, group_size, blocks_max, BLOCK);
+    hipLaunchKernelGGL((commit_kernel<COMMIT_STAGED, true>), dim3(geom.grid), dim3(geom.width), lds_bytes, stream, scalars, combs, rows, (u32)groups, (u32)group_size,
+                       (u32)geom.slices, (u32)geom.items);
     return (int)hipGetLastError();
 }
 

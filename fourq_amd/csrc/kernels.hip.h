@@ -20,6 +20,7 @@
 #include "recode.hip.h"
 #include "pair.hip.h"
 #include "bucket_layout.h"
+#include "commit_layout.h"
 
 namespace fq {
 
@@ -1117,6 +1118,10 @@ constexpr u32 MSM_FOLD = 64;
 int chain_launch_msm_fold(hipStream_t stream, const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out, size_t groups, size_t m_in);
 // bucket.hip.h: the grouped sums by the bucket method, from the sub-scalars to one projective row (and decode code) per group in w.sum / w.st_sum
 int chain_launch_bucket_sum(hipStream_t stream, const fq_work::Bucket& w, const u64* scalars, const u64* points_affine, const uint8_t* st_decode);
+// commit.hip.h: the combs of a commitment, row g * group_size + j from comb j of `combs` as a canonical 12-word (X, Y, Z) row; route 1 = staged, 2 = gather
+// (commit_layout.h has the geometry); ct_launch_commit: the constant-time build, blocks_max = resident 256-lane blocks
+int chain_launch_commit(int route, unsigned cus, hipStream_t stream, const u64* scalars, const u32* combs, u64* rows, size_t groups, size_t group_size);
+int ct_launch_commit(unsigned blocks_max, hipStream_t stream, const u64* scalars, const u32* combs, u64* rows, size_t groups, size_t group_size);
 // constant-time selection builds of the same kernels: fourq_ct_fused.hip (FQ_CHAIN=0) and fourq_ct_chain.hip (FQ_CHAIN=1)
 int ct_launch_fused(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);
 int ct_launch_pair(int algo, bool dh, bool fixed, bool quad, unsigned grid, hipStream_t stream, const LadderArgs& a);

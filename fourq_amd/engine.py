@@ -450,6 +450,59 @@ class Engine:
     def bucket_sum_bytes_dev(self, scalars, points32, out32, status, groups, group_size, window=0):
         self._ck(self._lib.fourq_bucketsum_bytes_dev(self._ctx, _ptr(scalars), _ptr(points32), _ptr(out32), _ptr(status), groups, group_size, int(window)))
 
+    # ---- commitments over a fixed generator set (fourq_commit_*): out[g] = sum_j [k_gj]B_j, one comb per generator held by the context ----
+    # route: 0 = the library picks by the number of groups (commit_route), 1 = staged (comb j in a CU's LDS), 2 = gather (entries read where
+    # they lie).  With ct_select on the route makes no difference.  The bytes are the same on every route.
+    def commit_generators(self, count, dst):
+        """`count` generators nobody knows a relation between: hash_to_curve(I2OSP(j, 4), dst, affine=True) for j < count, (count, 8) words.
+        They have order N by construction (the x392 chain)."""
+        msgs = np.array([list(int(j).to_bytes(4, "big")) for j in range(int(count))], dtype=np.uint8).reshape(int(count), 4)
+        return self.hash_to_curve(msgs, dst=dst, affine=True)
+
+    def commit_bases(self, points_affine):
+        """Build one comb per base on the device and keep the set in the context (fourq_commit_bases_set): (m, 8) affine words, 1 <= m <= 4096,
+        every base of order N (not checked).  Replaces any earlier set; the staged comb and tables are untouched."""
+        p = _host(points_affine, 8)
+        self._ck(self._lib.fourq_commit_bases_set(self._ctx, _ptr(p), len(p)))
+
+    @property
+    def commit_bases_count(self):
+        """The size of the generator set, 0 when none was ever set."""
+        m = ctypes.c_size_t()
+        self._ck(self._lib.fourq_commit_bases_count(self._ctx, ctypes.byref(m)))
+        return int(m.value)
+
+    def commit_route(self, groups):
+        """What route=0 stands for at this number of groups: 1 (staged) or 2 (gather)."""
+        return int(self._lib.fourq_commit_route(int(groups)))
+
+    def commit_reserve(self, groups, group_size):
+        """Size the work buffer for `commit*_dev` calls of at most this shape (reserve() is not enough for them): such calls then only enqueue."""
+        self._ck(self._lib.fourq_commit_reserve(self._ctx, int(groups), int(group_size)))
+
+    def commit(self, scalars, group_size, route=0, out=None):
+        """Canonical affine commitments, (n // group_size, 8) words: out[g] = sum over j < group_size of [k_gj]B_j with the bases of
+        commit_bases -- msm()'s result over the tiled bases, byte for byte.  The neutral point (0, 1) is an ordinary result."""
+        k = _host(scalars, 4)
+        groups, group_size = self._groups(len(k), group_size)
+        out = _out(out, groups, 8)
+        self._ck(self._lib.fourq_commit_affine(self._ctx, _ptr(k), _ptr(out), groups, group_size, int(route)))
+        return out
+
+    def commit_bytes(self, scalars, group_size, route=0, out=None):
+        """encode() of commit()'s points: (n // group_size, 32) bytes; the neutral is 01 00 .. 00.  No status: nothing is decoded."""
+        k = _host(scalars, 4)
+        groups, group_size = self._groups(len(k), group_size)
+        out = _out(out, groups, 32, np.uint8)
+        self._ck(self._lib.fourq_commit_bytes(self._ctx, _ptr(k), _ptr(out), groups, group_size, int(route)))
+        return out
+
+    def commit_dev(self, scalars, out_affine, groups, group_size, route=0):
+        self._ck(self._lib.fourq_commit_affine_dev(self._ctx, _ptr(scalars), _ptr(out_affine), groups, group_size, int(route)))
+
+    def commit_bytes_dev(self, scalars, out32, groups, group_size, route=0):
+        self._ck(self._lib.fourq_commit_bytes_dev(self._ctx, _ptr(scalars), _ptr(out32), groups, group_size, int(route)))
+
     # ---- signatures from bytes (fourq_sha512_* / fourq_sig_*): SHA-512 and the arithmetic modulo N run on the device -------------
     @staticmethod
     def _msgs(msgs, lens, n=None):

@@ -271,6 +271,29 @@ class MultiEngine:
         return self._sharded_groups(lambda e, b, z, p, o, st: e.dleq_verify(pk32, b, z, p, group_size, dst, comb, ok=o, status=st), [b, z], [p],
                                     [_out(ok, groups, None, np.uint8), _out(status, groups, None, np.uint8)], group_size)
 
+    # ---- commitments over a fixed generator set: the set is replicated, WHOLE groups are sharded as for the proofs -----------------------
+    def commit_generators(self, count, dst):
+        return self.engines[0].commit_generators(count, dst)
+
+    def commit_bases(self, points_affine):
+        p = _host(points_affine, 8)
+        for e in self.engines:
+            e.commit_bases(p)
+
+    @property
+    def commit_bases_count(self):
+        return self.engines[0].commit_bases_count
+
+    def commit(self, scalars, group_size, route=0, out=None):
+        k = _host(scalars, 4)
+        groups, group_size = Engine._groups(len(k), group_size)
+        return self._sharded_groups(lambda e, k, o: e.commit(k, group_size, route, out=o), [k], [], [_out(out, groups, 8)], group_size)[0]
+
+    def commit_bytes(self, scalars, group_size, route=0, out=None):
+        k = _host(scalars, 4)
+        groups, group_size = Engine._groups(len(k), group_size)
+        return self._sharded_groups(lambda e, k, o: e.commit_bytes(k, group_size, route, out=o), [k], [], [_out(out, groups, 32, np.uint8)], group_size)[0]
+
     # ---- wire format ----------------------------------------------------------------------------------------------
     def encode(self, points_affine, out=None):
         p = _host(points_affine, 8)

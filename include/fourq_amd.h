@@ -399,6 +399,57 @@ int fourq_bucketsum_bytes(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t
 int fourq_bucketsum_bytes_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status,
                               size_t groups, size_t group_size, unsigned window);
 
+/* ---- commitments over a fixed generator set: out[g] = sum_j [k_gj]B_j through one comb per generator -----------------------------------
+ * Pedersen and vector commitments use the same generators B_0 .. B_{m-1} in every group.  The context holds one comb per generator (the
+ * object of fourq_comb_table: 1 024 points + the 80 of the constant-time shape, as working limbs), and row j of every group goes through
+ * comb j: 6 doublings and 27 mixed additions instead of a variable-base ladder, no points over the link, and constant-time selection
+ * (fourq_ctx_set_ct_select) stays on this route -- the scalars of a commitment are secrets.
+ *
+ * fourq_commit_bases_set(ctx, points_affine, m): m x 8 canonical affine words on the HOST.  Builds the m combs on the device into one array
+ * the context owns (m x FOURQ_COMB_POINTS x 144 bytes: 155 KiB per generator) and replaces any earlier set.  Synchronous.  The staged single
+ * comb (fourq_comb_stage) and the staged tables are untouched.  m == 0 or m > FOURQ_COMMIT_MAX_BASES: FOURQ_ERR_INVALID, and the old set
+ * stays.  The set survives fourq_ctx_set_stream (it is plain device memory, complete when the call returns) and is freed with the context.
+ * Every base must have order N: like fourq_comb_table the call does not check it, and the result for any other base is unspecified
+ * (for an even k the comb computes -[N - k]B, which is [k]B only where [N]B is the neutral).  The outputs of
+ * fourq_hash_to_curve_* and every [t]G qualify.  fourq_commit_bases_count: the size of the set, 0 when none was ever set.
+ *
+ * scalars: groups x group_size rows of 4 words, group after group, as fourq_msm_* takes them; any value in [0, 2^256).  Row j of every group
+ * multiplies base j; 1 <= group_size <= the set's size, and a shorter vector uses the first bases.
+ * out_affine[g], for bases of order N, equals bit for bit what fourq_msm_affine_batch returns for the same scalars with the bases tiled
+ * `groups` times; out32[g] is its encoding.  The neutral point is an ordinary result: (0, 1), or 01 00 .. 00.  There is no status array:
+ * nothing is decoded.
+ *
+ * route: 0 = the library picks, by `groups`, from a table measured on the device (profiles/commit_timing.txt; fourq_commit_route(groups) is
+ * what 0 stands for); 1 = staged: one block per CU with comb j in the CU's LDS, staged again only when a block's base changes -- for many
+ * groups per base; 2 = gather: one lane per row, every entry read where it lies in the set's array -- for few groups per base (one group
+ * of 4 096 bases is 4 096 combs with one row each); anything else FOURQ_ERR_INVALID.  With constant-time selection on, the route makes no
+ * difference: a block stages its base's 80-point shape (11.5 KB) and every addition reads all 16 entries of its block of the table.  The
+ * bytes are the same on every route and in both modes.
+ *
+ * Cost, measured against fourq_msm_affine_batch_dev over the tiled bases (profiles/commit_timing.txt, groups x group_size, time as a
+ * fraction of msm_dev's, staged / gather): 32768 x 2: 0.351 / 0.348; 1024 x 64: 0.414 / 0.424; 65536 x 1: 0.342 / 0.335; 64 x 1024: 1.385 /
+ * 0.489 -- the staged route is SLOWER than msm_dev there, four combs staged per block for 64 rows each; 1 x 4096: 35.4 / 0.798.  With
+ * constant-time selection, 1024 x 64: 0.62 of msm_dev in that mode.  The operation count alone would give 0.22; the fold passes and the
+ * lowering are the same on both sides.  The staged route beat the gather route by more than the spread of msm_dev's own timings at one measured
+ * shape only, 1024 x 64 (2.3 % against 2.0 %); at 32768 and 65536 groups the two are within the spread.  So route 0 is the staged route from
+ * 1 024 groups and the gather route below.  fourq_commit_bases_set took 0.33 ms per base: 21 ms for 64 bases, 339 ms for 1 024.
+ *
+ * A NULL context is refused before anything else is looked at.  groups == 0: FOURQ_OK, nothing touched.  FOURQ_ERR_INVALID: group_size == 0,
+ * group_size above the set's size, no set, groups * group_size (overflow-checked) above FOURQ_MAX_BATCH, a route outside 0..2.  _dev: enqueues
+ * on the context's stream and returns; both array pointers 16-byte aligned.  The intermediates (12 words per row and the fold's partial
+ * sums) live in the context's work buffer; fourq_ctx_reserve does not cover them, fourq_commit_reserve(ctx, groups, group_size) does: after
+ * it a _dev call of at most that shape allocates and synchronises nothing, and the geometry of every launch follows from (groups,
+ * group_size, route) on the host.  The host-array calls copy in, run and copy out in one piece, as fourq_msm_* do. */
+#define FOURQ_COMMIT_MAX_BASES 4096
+int fourq_commit_bases_set(fourq_ctx *ctx, const uint64_t *points_affine, size_t m);
+int fourq_commit_bases_count(const fourq_ctx *ctx, size_t *m);
+int fourq_commit_route(size_t groups);
+int fourq_commit_reserve(fourq_ctx *ctx, size_t groups, size_t group_size);
+int fourq_commit_affine(fourq_ctx *ctx, const uint64_t *scalars, uint64_t *out_affine, size_t groups, size_t group_size, int route);
+int fourq_commit_affine_dev(fourq_ctx *ctx, const uint64_t *scalars, uint64_t *out_affine, size_t groups, size_t group_size, int route);
+int fourq_commit_bytes(fourq_ctx *ctx, const uint64_t *scalars, uint8_t *out32, size_t groups, size_t group_size, int route);
+int fourq_commit_bytes_dev(fourq_ctx *ctx, const uint64_t *scalars, uint8_t *out32, size_t groups, size_t group_size, int route);
+
 /* ---- signatures from bytes: SchnorrQ-shaped sign / verify with SHA-512 and the arithmetic modulo N on the device ---------------------
  * Nothing but byte arrays crosses the ABI -- secret keys, public keys, messages, signatures, one ok and one status byte per row -- and no
  * intermediate (the hash of the secret key, the nonce, the challenge, R as a point) is ever on the host.  With H = SHA-512, LE(x) the
