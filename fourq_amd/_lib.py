@@ -29,6 +29,7 @@ SIG_S_RANGE, SIG_MSG_CLAMPED, SIG_MAX_MSG = 32, 64, 1 << 20   # FOURQ_SIG_*
 H2C_RO, H2C_NU, H2C_MAX_DST = 0, 1, 255                       # FOURQ_H2C_*
 OPRF_BLIND_ZERO = 48                                          # FOURQ_OPRF_BLIND_ZERO
 DLEQ_NONCE_ZERO = 80                                          # FOURQ_DLEQ_NONCE_ZERO
+KEYSET_MAX_KEYS, KEYSET_NOT_ORDER_N, KEYSET_ID_RANGE = 4096, 96, 112   # FOURQ_KEYSET_*
 
 
 class HostStats(ctypes.Structure):
@@ -139,6 +140,13 @@ PROTOTYPES = {
     "fourq_sig_sign_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_sig_verify_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_sig_verify_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_keyset_set": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fourq_keyset_count": (c_int, [c_void_p, POINTER(c_size_t)]),
+    "fourq_keyset_reserve": (c_int, [c_void_p, c_size_t]),
+    "fourq_keyset_double_mul_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_keyset_double_mul_bytes_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_keyset_sig_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_keyset_sig_verify_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_hash_to_field_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_hash_to_field_batch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     "fourq_map_to_curve_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),

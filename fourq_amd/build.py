@@ -24,7 +24,7 @@ RESOURCES_PATH = os.path.join(HERE, "kernel_resources.json")
 PLACEMENT_PATH = os.path.join(HERE, "code_placement.json")
 # four translation units: FQ_CHAIN=0 / 1 (kernels.hip.h), and the constant-time-selection builds of both flavours
 SOURCES = ["fourq_amd.hip", "fourq_chain.hip", "fourq_ct_fused.hip", "fourq_ct_chain.hip"]
-HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "kernels.hip.h", "combine.hip.h", "msm.hip.h", "bucket.hip.h", "bucket_layout.h", "commit.hip.h", "commit_layout.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "work_layout.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", "h2c.hip.h", "oprf.hip.h", "dleq_layout.h", "dleq.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
+HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "kernels.hip.h", "combine.hip.h", "msm.hip.h", "bucket.hip.h", "bucket_layout.h", "commit.hip.h", "commit_layout.h", "keyset.hip.h", "keyset_layout.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "work_layout.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", "h2c.hip.h", "oprf.hip.h", "dleq_layout.h", "dleq.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Rpass-analysis=kernel-resource-usage"]
 # Code placement (tools/asmgen/place_asm.py, profiles/r04_ladder_step.txt): the device code of every translation unit goes through
 # assembly text, where every 8-byte instruction is put on an 8-byte boundary (an _e32 instruction in front of it re-encoded as _e64),
@@ -54,6 +54,11 @@ RESOURCE_POLICY = [
     (r"\bbucket_accumulate_kernel<", "occupancy", lambda v: v >= 3, "the bucket accumulation hides its gathers and its dependent chain behind other waves: no fewer than the fold's three per SIMD"),
     (r"\bcommit_kernel<", "scratch", lambda v: v == 0, "the commitment combs are the keygen comb's chain with another table per lane: nothing may spill, in either mode"),
     (r"\bcommit_kernel<", "occupancy", lambda v: v >= 4, "the staged commitment comb runs 1 024-lane blocks (four waves per SIMD), the gather and constant-time ones four 256-lane blocks per CU"),
+    (r"\bkeyset_comb_kernel\(", "scratch", lambda v: v == 0, "the keyed comb is the gather commitment comb with two tables under shared doublings: nothing may spill"),
+    (r"\bkeyset_comb_kernel\(", "occupancy", lambda v: v >= 4, "the keyed comb hides its gathers behind other waves, as the gather commitment comb: four 256-lane blocks per CU"),
+    (r"\bsig_challenge_keyed_kernel\(", "scratch", lambda v: v == 0, "the keyed challenge is the challenge kernel with its key row fetched by index: a hashing kernel, nothing may spill"),
+    (r"\bsig_challenge_keyed_kernel\(", "occupancy", lambda v: v >= 4, "the keyed challenge is throughput code held to 128 VGPRs, as the other hashing kernels: four waves per SIMD"),
+    (r"\bkeyset_order_kernel\(", "scratch", lambda v: v == 0, "the order check is one chain of doublings and additions per key: its point and the key's table entry stay in registers"),
     (r"\b(sha512_kernel|sig_challenge_kernel|sig_nonce_kernel<\w+>|sig_finish_kernel)\(", "scratch", lambda v: v == 0,
      "the hashing kernels hold 40 live 64-bit values: state, schedule, working variables, prefix -- nothing of it may spill"),
     (r"\b(sha512_kernel|sig_challenge_kernel|sig_nonce_kernel<\w+>|sig_finish_kernel)\(", "occupancy", lambda v: v >= 4,

@@ -42,6 +42,7 @@
 #include "h2c.hip.h"
 #include "oprf.hip.h"
 #include "dleq_layout.h"
+#include "keyset_layout.h"
 #include "dleq.hip.h"
 
 using namespace fq;
@@ -457,7 +458,7 @@ const PrimShape* find_prim(int op) {
 // (ENDO / WINDOWED, RO / NU, without / with table392) names the flavour in PipeRoute::variant, 0 or 1.
 enum PipeRouteId { PR_MUL_VAR, PR_MUL_FIX, PR_DH_VAR, PR_DH_FIX, PR_MIXED, PR_COMB, PR_ENCODE, PR_DECODE, PR_DHB_VAR, PR_DHB_FIX, PR_AFF, PR_BYTES, PR_EXCH, PR_EXCH_COMB,
                    PR_DOUBLE_AFF, PR_DOUBLE_BYTES, PR_DOUBLE_VERIFY, PR_SHA512, PR_SIG_KEYGEN, PR_SIG_SIGN, PR_SIG_VERIFY, PR_H2F, PR_H2C_MAP, PR_H2C, PR_H2C_AFFINE,
-                   PR_OPRF_BLIND, PR_OPRF_EVALUATE, PR_OPRF_FINALIZE, PR_OPRF_EVAL, PR_SC_INV, PR_COUNT };
+                   PR_OPRF_BLIND, PR_OPRF_EVALUATE, PR_OPRF_FINALIZE, PR_OPRF_EVAL, PR_SC_INV, PR_KEYSET_DOUBLE, PR_KEYSET_VERIFY, PR_COUNT };
 constexpr int PIPE_SLOTS_MAX = 6;
 struct fourq_ctx {
     int device = 0;
@@ -474,6 +475,10 @@ struct fourq_ctx {
     u64* comb_packed = nullptr;    // FOURQ_COMB_POINTS x 12 words
     u32* commit_combs = nullptr;   // fourq_commit_bases_set: commit_count combs of COMB_POINTS x COMB_ENTRY_U32 working limbs, back to back
     size_t commit_count = 0;
+    u32* keyset_combs = nullptr;   // fourq_keyset_set: keyset_count combs of the same shape, one per registered public key (a refused slot's is all zero)
+    uint8_t* keyset_bytes = nullptr;   // ... the keys as registered, keyset_count x 32 bytes, and behind them one status byte per slot
+    uint8_t* keyset_status = nullptr;
+    size_t keyset_count = 0;
     uint64_t table_shadow[FOURQ_TABLE_WORDS];   // host copies of what table_limbs / comb_limbs currently hold
     uint64_t comb_shadow[FOURQ_COMB_WORDS];
     bool table_staged = false, comb_staged = false;
@@ -1358,7 +1363,7 @@ FQ_API int fourq_ctx_destroy(fourq_ctx* c) {
     DeviceGuard g(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     for (void* p : { (void*)c->scratch, (void*)c->proj, (void*)c->table_limbs, (void*)c->table_packed, (void*)c->part_counter, (void*)c->part_list,
-                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, (void*)c->commit_combs, c->stage, (void*)c->work, (void*)c->pipe_dev })
+                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, (void*)c->commit_combs, (void*)c->keyset_combs, (void*)c->keyset_bytes, c->stage, (void*)c->work, (void*)c->pipe_dev })
         if (p) (void)hipFree(p);
     if (c->pipe_pin) (void)hipHostFree(c->pipe_pin);
     if (c->zero_copy) (void)hipHostFree(c->zero_copy);
@@ -2016,6 +2021,19 @@ static_assert(fq_work::Commit::FOLD == MSM_FOLD, "commit_layout.h sizes the fold
 // One comb per base, built where the single comb is (comb_table_kernel over the context's scratch slots, comb_unpack_kernel) and written
 // into a NEW array: the old set is replaced only once the new one is complete, so a failure keeps it.  The staged single comb
 // (comb_limbs, its shadow) is not touched; comb_packed is only the bounce row between the two kernels, as in fourq_comb_table.
+// comb j of `combs` from the R1 row j of `r1` (device), on the context's stream; refused (host, or NULL: none): a slot with a non-zero byte
+// gets an all-zero comb instead -- limbs that any addition may read
+static int build_combs(fourq_ctx* c, const u64* r1, const uint8_t* refused, u32* combs, size_t m) {
+    for (size_t j = 0; j < m; j++) {
+        u32* comb = combs + j * COMB_POINTS * COMB_ENTRY_U32;
+        if (refused && refused[j]) { HIP_TRY(c, hipMemsetAsync(comb, 0, (size_t)COMB_POINTS * COMB_ENTRY_U32 * sizeof(u32), c->stream)); continue; }
+        hipLaunchKernelGGL(comb_table_kernel, dim3((COMB_POINTS + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, (const u64*)(r1 + 20 * j), c->scratch, c->comb_packed);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(comb_unpack_kernel, dim3((COMB_POINTS + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->comb_packed, comb);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FOURQ_OK;
+}
 FQ_API int fourq_commit_bases_set(fourq_ctx* c, const uint64_t* points_affine, size_t m) {
     if (!c || !points_affine || m == 0 || m > FOURQ_COMMIT_MAX_BASES) return FOURQ_ERR_INVALID;
     CtxGuard g(c);
@@ -2030,12 +2048,7 @@ FQ_API int fourq_commit_bases_set(fourq_ctx* c, const uint64_t* points_affine, s
         HIP_TRY(c, hipMemcpyAsync(affine, points_affine, m * 64, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(lift_affine_kernel, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, affine, r1, (u32)m);
         HIP_TRY(c, hipGetLastError());
-        for (size_t j = 0; j < m; j++) {
-            hipLaunchKernelGGL(comb_table_kernel, dim3((COMB_POINTS + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, (const u64*)(r1 + 20 * j), c->scratch, c->comb_packed);
-            HIP_TRY(c, hipGetLastError());
-            hipLaunchKernelGGL(comb_unpack_kernel, dim3((COMB_POINTS + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->comb_packed, combs + j * COMB_POINTS * COMB_ENTRY_U32);
-            HIP_TRY(c, hipGetLastError());
-        }
+        if (int rc = build_combs(c, r1, nullptr, combs, m)) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return FOURQ_OK;
     };
@@ -2213,6 +2226,136 @@ FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint6
                          sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
     return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
         return fourq_sig_verify_batch_dev(c, k.in<uint8_t>(0), nullptr, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.in<uint8_t>(1), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m);
+    });
+}
+
+// ---- signatures of registered keys (include/fourq_amd.h; keyset.hip.h, keyset_layout.h): [s]G + [h]A_id with A_id as fixed as G ----------
+// The set: decode (decode_kernel), the order check (keyset_order_kernel), AffineToR1, then one comb per accepted key where the commitment
+// bases get theirs (build_combs).  Everything goes into NEW arrays, and the old set is replaced once they are complete.
+FQ_API int fourq_keyset_set(fourq_ctx* c, const uint8_t* pk32, size_t m, uint8_t* key_status) {
+    if (!c || !pk32 || m == 0 || m > FOURQ_KEYSET_MAX_KEYS) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    if (int rc = staging_allowed(c)) return rc;
+    if (int rc = ensure_stage(c, m * (64 + 160))) return rc;
+    u64* affine = (u64*)c->stage;
+    u64* r1 = affine + 8 * m;
+    u32* combs = nullptr;
+    uint8_t* bytes = nullptr;
+    hipError_t e = hipMalloc(&combs, m * COMB_POINTS * COMB_ENTRY_U32 * sizeof(u32));
+    if (e == hipSuccess) e = hipMalloc(&bytes, m * 32 + fq_work::align256(m));
+    if (e != hipSuccess) { if (combs) (void)hipFree(combs); return fail(c, e, "hipMalloc(the combs of the key set)"); }
+    uint8_t* status = bytes + m * 32;
+    std::vector<uint8_t> st(m);
+    auto build = [&]() -> int {
+        const unsigned grid = (unsigned)((m + BLOCK - 1) / BLOCK);
+        HIP_TRY(c, hipMemcpyAsync(bytes, pk32, m * 32, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, (const u64*)bytes, affine, status, (u32)m);
+        HIP_TRY(c, hipGetLastError());
+        HIPRC_TRY(c, chain_launch_keyset_order(c->stream, affine, status, (u32)m));
+        hipLaunchKernelGGL(lift_affine_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, affine, r1, (u32)m);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(st.data(), status, m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (int rc = build_combs(c, r1, st.data(), combs, m)) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return FOURQ_OK;
+    };
+    if (int rc = build()) { (void)hipStreamSynchronize(c->stream); (void)hipFree(combs); (void)hipFree(bytes); return rc; }
+    if (c->keyset_combs) (void)hipFree(c->keyset_combs);      // the stream is idle: nothing reads the old set any more
+    if (c->keyset_bytes) (void)hipFree(c->keyset_bytes);
+    c->keyset_combs = combs;
+    c->keyset_bytes = bytes;
+    c->keyset_status = status;
+    c->keyset_count = m;
+    if (key_status) memcpy(key_status, st.data(), m);
+    return FOURQ_OK;
+}
+FQ_API int fourq_keyset_count(const fourq_ctx* c, size_t* m) {
+    if (!c || !m) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    *m = c->keyset_count;
+    return FOURQ_OK;
+}
+FQ_API int fourq_keyset_reserve(fourq_ctx* c, size_t n) {
+    if (!c || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    return reserve_for<fq_work::Keyset>(c, n);
+}
+// the host-pointer calls can look at the indices: one outside the set is an argument error there
+static bool keyset_ids_host_ok(const fourq_ctx* c, const uint32_t* key_ids, size_t n) {
+    if (!c || !key_ids || n > FOURQ_MAX_BATCH) return false;
+    size_t count;
+    { CtxGuard g(c); count = c->keyset_count; }
+    for (size_t i = 0; i < n; i++) if (key_ids[i] >= count) return false;
+    return true;
+}
+// Default mode: the two combs in one accumulator, then the lowering.  Constant-time selection: the rows' key bytes gathered by index, the
+// existing route over them, and the set's statuses put on its result -- a gathered address would be a digit of l.
+FQ_API int fourq_keyset_double_mul_bytes_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint32_t* key_ids, uint8_t* out32,
+                                             uint8_t* status, size_t n) {
+    if (!c) return FOURQ_ERR_INVALID;
+    if (!k || !l || !key_ids || !out32 || !status || n > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    if (!aligned16(k) || !aligned16(l) || !aligned16(key_ids) || !aligned16(out32)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (c->keyset_count == 0) return FOURQ_ERR_INVALID;
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = reserve_for<fq_work::Keyset>(c, n))) return rc;
+    const fq_work::Keyset w(c->work, n);
+    const u32 count = (u32)c->keyset_count;
+    if (c->ct) {
+        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, w.pk32, (u32)n));
+        if ((rc = double_mul_dev(c, k, nullptr, l, w.pk32, true, COMBINE_ENCODE, nullptr, out32, status, nullptr, n))) return rc;
+        HIPRC_TRY(c, chain_launch_keyset_fix(c->stream, key_ids, c->keyset_status, count, (u64*)out32, nullptr, status, (u32)n));
+        return FOURQ_OK;
+    }
+    HIPRC_TRY(c, chain_launch_keyset_comb(c->stream, k, l, key_ids, c->comb_limbs, c->keyset_combs, c->keyset_status, count, w.rows, w.pre, (u32)n));
+    HIPRC_TRY(c, chain_launch_keyset_lower(c->stream, false, w.rows, w.pre, nullptr, (u64*)out32, nullptr, status, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_keyset_sig_verify_dev(fourq_ctx* c, const uint32_t* key_ids, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                            const uint8_t* sig64, uint8_t* ok, uint8_t* status, size_t n) {
+    if (!c) return FOURQ_ERR_INVALID;
+    if (!key_ids || !sig64 || !ok || !status || n > FOURQ_MAX_BATCH || !aligned16(key_ids) || !aligned16(sig64)) return FOURQ_ERR_INVALID;
+    if (!sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (c->keyset_count == 0) return FOURQ_ERR_INVALID;
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = reserve_for<fq_work::Keyset>(c, n))) return rc;
+    const fq_work::Keyset w(c->work, n);
+    const u32 count = (u32)c->keyset_count;
+    if (c->ct) {
+        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, w.pk32, (u32)n));
+        if ((rc = fourq_sig_verify_batch_dev(c, w.pk32, nullptr, msgs, stride, lens, msg_len, sig64, ok, status, n))) return rc;
+        HIPRC_TRY(c, chain_launch_keyset_fix(c->stream, key_ids, c->keyset_status, count, nullptr, ok, status, (u32)n));
+        return FOURQ_OK;
+    }
+    HIPRC_TRY(c, sig_launch_challenge_keyed(c->stream, key_ids, c->keyset_bytes, c->keyset_status, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w.s, w.h, w.r32,
+                                            w.pre, (u32)n));
+    HIPRC_TRY(c, chain_launch_keyset_comb(c->stream, w.s, w.h, key_ids, c->comb_limbs, c->keyset_combs, c->keyset_status, count, w.rows, nullptr, (u32)n));
+    HIPRC_TRY(c, chain_launch_keyset_lower(c->stream, true, w.rows, w.pre, w.r32, nullptr, ok, status, (u32)n));
+    return FOURQ_OK;
+}
+// host-pointer twins: key_ids is a 4-byte-per-row input in place of the key bytes
+static int keyset_prepare(fourq_ctx* c, const uint64_t* comb) { return c->keyset_count == 0 ? FOURQ_ERR_INVALID : stage_comb(c, comb); }
+FQ_API int fourq_keyset_double_mul_bytes(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint32_t* key_ids, uint8_t* out32, uint8_t* status,
+                                         size_t n) {
+    const HostCall d = { { { k, 32 }, { l, 32 }, { key_ids, 4 } }, { { out32, 32 }, { status, 1 } }, { PR_KEYSET_DOUBLE, 0, 2 * KT_COMB + KT_ENCODE }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::Keyset>, keyset_ids_host_ok(c, key_ids, n) };
+    return host_call(c, n, d, [&] { return keyset_prepare(c, comb); }, [&](const Chunk& x) {
+        return fourq_keyset_double_mul_bytes_dev(c, x.in<uint64_t>(0), nullptr, x.in<uint64_t>(1), x.in<uint32_t>(2), x.out<uint8_t>(0), x.out<uint8_t>(1), x.m);
+    });
+}
+FQ_API int fourq_keyset_sig_verify(fourq_ctx* c, const uint32_t* key_ids, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
+                                        const uint8_t* sig64, uint8_t* ok, uint8_t* status, size_t n) {
+    const HostCall d = { { { key_ids, 4 }, { sig64, 64 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { ok, 1 }, { status, 1 } },
+                         { PR_KEYSET_VERIFY, 0, 2 * KT_COMB + KT_ENCODE + sig_kt_hash(stride, 64) }, pipe_chunk, nullptr, reserve_for<fq_work::Keyset>,
+                         sig_msgs_host_ok(msgs, stride, lens, msg_len, n) && keyset_ids_host_ok(c, key_ids, n), stride };
+    return host_call(c, n, d, [&] { return keyset_prepare(c, comb); }, [&](const Chunk& x) {
+        return fourq_keyset_sig_verify_dev(c, x.in<uint32_t>(0), nullptr, x.in<uint8_t>(2), stride, x.in<uint32_t>(3), msg_len, x.in<uint8_t>(1), x.out<uint8_t>(0), x.out<uint8_t>(1), x.m);
     });
 }
 

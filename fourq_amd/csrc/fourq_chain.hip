@@ -2,7 +2,7 @@
 // kernels.hip.h): fixed-base ladders (table in LDS), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
 // translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P,
 // msm.hip.h the one that folds the ladder's rows of a group into one, bucket.hip.h the bucket route of the same sums, commit.hip.h the combs of a
-// fixed generator set.
+// fixed generator set, keyset.hip.h the two combs in one accumulator of a signature check over registered keys.
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
 #endif
@@ -11,6 +11,7 @@
 #include "msm.hip.h"
 #include "bucket.hip.h"
 #include "commit.hip.h"
+#include "keyset.hip.h"
 
 namespace fq {
 
@@ -93,6 +94,30 @@ int chain_launch_commit(int route, unsigned cus, hipStream_t stream, const u64* 
     const fq_work::CommitGeom geom(groups, group_size, cus, COMB_BLOCK_MAX);
     hipLaunchKernelGGL((commit_kernel<COMMIT_STAGED, false>), dim3(geom.grid), dim3(geom.width), COMB_FAST_LDS_BYTES, stream, scalars, combs, rows, (u32)groups, (u32)group_size,
                        (u32)geom.slices, (u32)geom.items);
+    return (int)hipGetLastError();
+}
+
+// Signatures of registered keys (keyset.hip.h).  Every grid follows from the row count.
+int chain_launch_keyset_order(hipStream_t stream, const u64* affine, uint8_t* status, u32 m) {
+    hipLaunchKernelGGL(keyset_order_kernel, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, affine, status, m);
+    return (int)hipGetLastError();
+}
+int chain_launch_keyset_comb(hipStream_t stream, const u64* k, const u64* l, const u32* key_ids, const u32* comb_g, const u32* combs, const uint8_t* key_status, u32 count,
+                             u64* rows, uint8_t* pre, u32 n) {
+    hipLaunchKernelGGL(keyset_comb_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, k, l, key_ids, comb_g, combs, key_status, count, rows, pre, n);
+    return (int)hipGetLastError();
+}
+int chain_launch_keyset_lower(hipStream_t stream, bool verify, const u64* rows, const uint8_t* pre, const u64* expect, u64* out, uint8_t* ok, uint8_t* status, u32 n) {
+    if (verify) hipLaunchKernelGGL(keyset_lower_kernel<true>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, rows, pre, expect, out, ok, status, n);
+    else hipLaunchKernelGGL(keyset_lower_kernel<false>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, rows, pre, expect, out, ok, status, n);
+    return (int)hipGetLastError();
+}
+int chain_launch_keyset_gather(hipStream_t stream, const u32* key_ids, const uint8_t* key_bytes, u32 count, uint8_t* pk32, u32 n) {
+    hipLaunchKernelGGL(keyset_gather_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, key_ids, key_bytes, count, pk32, n);
+    return (int)hipGetLastError();
+}
+int chain_launch_keyset_fix(hipStream_t stream, const u32* key_ids, const uint8_t* key_status, u32 count, u64* out, uint8_t* ok, uint8_t* status, u32 n) {
+    hipLaunchKernelGGL(keyset_fix_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, key_ids, key_status, count, out, ok, status, n);
     return (int)hipGetLastError();
 }
 

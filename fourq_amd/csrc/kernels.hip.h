@@ -1122,6 +1122,15 @@ int chain_launch_bucket_sum(hipStream_t stream, const fq_work::Bucket& w, const 
 // (commit_layout.h has the geometry); ct_launch_commit: the constant-time build, blocks_max = resident 256-lane blocks
 int chain_launch_commit(int route, unsigned cus, hipStream_t stream, const u64* scalars, const u32* combs, u64* rows, size_t groups, size_t group_size);
 int ct_launch_commit(unsigned blocks_max, hipStream_t stream, const u64* scalars, const u32* combs, u64* rows, size_t groups, size_t group_size);
+// keyset.hip.h: signatures of registered keys.  order: status[i] from decode's raw code to the slot's status; comb: [k]B + [l]A_id as canonical 12-word rows
+// from the generator's comb and comb id of `combs` (pre, or NULL: the row's inherited status); lower: the rows' encodings, or with `verify` ok = (encoding ==
+// expect); gather + fix: the constant-time route's key bytes by index, and the set's statuses on the existing routes' results
+int chain_launch_keyset_order(hipStream_t stream, const u64* affine, uint8_t* status, u32 m);
+int chain_launch_keyset_comb(hipStream_t stream, const u64* k, const u64* l, const u32* key_ids, const u32* comb_g, const u32* combs, const uint8_t* key_status, u32 count,
+                             u64* rows, uint8_t* pre, u32 n);
+int chain_launch_keyset_lower(hipStream_t stream, bool verify, const u64* rows, const uint8_t* pre, const u64* expect, u64* out, uint8_t* ok, uint8_t* status, u32 n);
+int chain_launch_keyset_gather(hipStream_t stream, const u32* key_ids, const uint8_t* key_bytes, u32 count, uint8_t* pk32, u32 n);
+int chain_launch_keyset_fix(hipStream_t stream, const u32* key_ids, const uint8_t* key_status, u32 count, u64* out, uint8_t* ok, uint8_t* status, u32 n);
 // constant-time selection builds of the same kernels: fourq_ct_fused.hip (FQ_CHAIN=0) and fourq_ct_chain.hip (FQ_CHAIN=1)
 int ct_launch_fused(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);
 int ct_launch_pair(int algo, bool dh, bool fixed, bool quad, unsigned grid, hipStream_t stream, const LadderArgs& a);

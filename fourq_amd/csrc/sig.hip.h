@@ -86,6 +86,26 @@ __global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void sig_challenge_kernel(con
     store32(reinterpret_cast<uint8_t*>(h_out + 4 * (size_t)i), h);
 }
 
+// sig_challenge_kernel over a registered key set (fourq_keyset_set): the key row is key_bytes[id_i], and the pre-status carries the whole
+// precedence -- an index outside the set (clamped before it becomes an address), the key's own status, a clamped message, s >= N
+__global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void sig_challenge_keyed_kernel(const u32* key_ids, const uint8_t* key_bytes, const uint8_t* key_status, u32 count, SigMsgs m,
+                                                                                   const uint8_t* sig64, u64* s_out, u64* h_out, u64* r_out, uint8_t* pre_status, u32 n) {
+    const u32 i = blockIdx.x * SIG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const LaneMsg l = lane_msg(m, i);
+    const u32 id = key_ids[i], at = id < count ? id : count - 1;
+    u64 R[4], s[4], pk[4], h[4];
+    load32(sig64 + 64 * (size_t)i, R);
+    load32(sig64 + 64 * (size_t)i + 32, s);
+    load32(key_bytes + 32 * (size_t)at, pk);
+    store32(reinterpret_cast<uint8_t*>(s_out + 4 * (size_t)i), s);
+    store32(reinterpret_cast<uint8_t*>(r_out + 4 * (size_t)i), R);
+    const uint8_t key = id < count ? key_status[at] : (uint8_t)FOURQ_KEYSET_ID_RANGE;
+    pre_status[i] = key ? key : l.clamped ? (uint8_t)FOURQ_SIG_MSG_CLAMPED : sc_lt_n(s) ? (uint8_t)0 : (uint8_t)FOURQ_SIG_S_RANGE;
+    challenge(R, pk, l, sha_load_mode(m.rows, m.stride), h);
+    store32(reinterpret_cast<uint8_t*>(h_out + 4 * (size_t)i), h);
+}
+
 // One pass through ONE copy of the compression function: step 0 hashes the 32-byte secret key (a single block), steps 1.. hash
 // k[32:64] || msg.  The step counter is wave-uniform; only the number of steps differs between lanes (by the message's length).
 template <bool NONCE>
@@ -186,6 +206,12 @@ int sig_launch_sha512(hipStream_t stream, SigMsgs m, uint8_t* out64, uint32_t n)
 int sig_launch_challenge(hipStream_t stream, const uint8_t* pk32, SigMsgs m, const uint8_t* sig64, uint64_t* s_out, uint64_t* h_out, uint64_t* r_out,
                          uint8_t* pre_status, uint32_t n) {
     hipLaunchKernelGGL(sig_challenge_kernel, sig_grid(n), dim3(SIG_BLOCK), 0, stream, pk32, m, sig64, (u64*)s_out, (u64*)h_out, (u64*)r_out, pre_status, n);
+    return (int)hipGetLastError();
+}
+int sig_launch_challenge_keyed(hipStream_t stream, const uint32_t* key_ids, const uint8_t* key_bytes, const uint8_t* key_status, uint32_t count, SigMsgs m, const uint8_t* sig64,
+                               uint64_t* s_out, uint64_t* h_out, uint64_t* r_out, uint8_t* pre_status, uint32_t n) {
+    hipLaunchKernelGGL(sig_challenge_keyed_kernel, sig_grid(n), dim3(SIG_BLOCK), 0, stream, key_ids, key_bytes, key_status, count, m, sig64, (u64*)s_out, (u64*)h_out, (u64*)r_out,
+                       pre_status, n);
     return (int)hipGetLastError();
 }
 // k = SHA-512(sk): a = LE(k[0:32]) (not reduced) into a_out; with `nonce`, r = SHA-512(k[32:64] || msg) mod N into r_out

@@ -571,6 +571,56 @@ class Engine:
         self._ck(self._lib.fourq_sig_verify_batch_dev(self._ctx, _ptr(pk32), _ptr(self._comb_arg(comb_host)), _ptr(msgs), stride, _ptr(lens), msg_len,
                                                       _ptr(sig64), _ptr(ok), _ptr(status), n))
 
+    # ---- signatures of registered keys (fourq_keyset_*, fourq_keyset_sig_verify*): rows name their public key by index, and the context
+    # holds one comb per key (155 KiB each), so [s]G + [h]A_id is two combs in one accumulator instead of a comb and a ladder --------------
+    def keyset_set(self, keys32):
+        """Register (m, 32) public keys, 1 <= m <= 4096, replacing any earlier set; synchronous.  Returns one status byte per slot:
+        0 = accepted, _lib.BYTES_DECODE_BASE + DECODE_* = does not decode, _lib.KEYSET_NOT_ORDER_N = decodes to a point outside the
+        subgroup of order N.  A refused key keeps its slot; rows that name it are reported with its status."""
+        pk = _host(keys32, 32, np.uint8)
+        status = np.zeros(len(pk), dtype=np.uint8)
+        self._ck(self._lib.fourq_keyset_set(self._ctx, _ptr(pk), len(pk), _ptr(status)))
+        return status
+
+    def keyset_count(self):
+        """The number of registered keys; 0 when none were."""
+        m = ctypes.c_size_t(0)
+        self._ck(self._lib.fourq_keyset_count(self._ctx, ctypes.byref(m)))
+        return int(m.value)
+
+    def keyset_reserve(self, n):
+        """Size the buffers for keyed `_dev` calls of at most n rows (reserve() is not enough for them): such calls then only enqueue."""
+        self._ck(self._lib.fourq_keyset_reserve(self._ctx, int(n)))
+
+    def keyset_double_mul_bytes(self, k_scalars, l_scalars, ids, comb=None, out=None, status=None):
+        """encode([k_i]B + [l_i]A_ids[i]) over the registered keys: ((n, 32) bytes, status).  status[i] = 0 or the key's own status (the
+        row is zero then); an index outside the set is an error."""
+        k, l, i = _host(k_scalars, 4), _host(l_scalars, 4), np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        if not len(k) == len(l) == len(i):
+            raise ValueError("the scalar and index arrays differ in length")
+        out, status = _out(out, len(k), 32, np.uint8), _out(status, len(k), None, np.uint8)
+        self._ck(self._lib.fourq_keyset_double_mul_bytes(self._ctx, _ptr(k), _ptr(self._comb_arg(comb)), _ptr(l), _ptr(i), _ptr(out), _ptr(status), len(k)))
+        return out, status
+
+    def keyset_double_mul_bytes_dev(self, k_scalars, l_scalars, ids, out32, status, n, comb_host=None):
+        self._ck(self._lib.fourq_keyset_double_mul_bytes_dev(self._ctx, _ptr(k_scalars), _ptr(self._comb_arg(comb_host)), _ptr(l_scalars), _ptr(ids), _ptr(out32),
+                                                             _ptr(status), n))
+
+    def sig_verify_keyed(self, ids, msgs, sig64, lens=None, comb=None, ok=None, status=None):
+        """sig_verify() with pk32[i] = the registered key ids[i]: (ok, status).  status as sig_verify's, or the key's own status."""
+        i, sig = np.ascontiguousarray(ids, dtype=np.uint32).ravel(), _host(sig64, 64, np.uint8)
+        if len(i) != len(sig):
+            raise ValueError("the index and signature arrays differ in length")
+        m, stride, lens, msg_len = self._msgs(msgs, lens, len(i))
+        ok, status = _out(ok, len(i), None, np.uint8), _out(status, len(i), None, np.uint8)
+        self._ck(self._lib.fourq_keyset_sig_verify(self._ctx, _ptr(i), _ptr(self._comb_arg(comb)), _ptr(m) if stride else None, stride, _ptr(lens), msg_len,
+                                                        _ptr(sig), _ptr(ok), _ptr(status), len(i)))
+        return ok, status
+
+    def sig_verify_keyed_dev(self, ids, msgs, stride, lens, msg_len, sig64, ok, status, n, comb_host=None):
+        self._ck(self._lib.fourq_keyset_sig_verify_dev(self._ctx, _ptr(ids), _ptr(self._comb_arg(comb_host)), _ptr(msgs), stride, _ptr(lens), msg_len,
+                                                            _ptr(sig64), _ptr(ok), _ptr(status), n))
+
     # ---- bytes to a point (fourq_hash_to_*: RFC 9380 with SHA-512 XMD, Elligator 2 and the x392 chain, include/fourq_amd.h) --------
     @staticmethod
     def _h2c(dst, mode):

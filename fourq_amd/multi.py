@@ -194,6 +194,34 @@ class MultiEngine:
         return self._sharded(lambda e, pk, m, sig, ln, o, st: e.sig_verify(pk, m, sig, ln, comb, ok=o, status=st), [pk, m, sig, ln],
                              [_out(ok, len(pk), None, np.uint8), _out(status, len(pk), None, np.uint8)])
 
+    # ---- signatures of registered keys: the set is replicated on every device, rows are sharded --------------------------------------
+    def keyset_set(self, keys32):
+        pk = _host(keys32, 32, np.uint8)
+        status = None
+        for e in self.engines:
+            status = e.keyset_set(pk)
+        return status
+
+    def keyset_count(self):
+        return self.engines[0].keyset_count()
+
+    def keyset_reserve(self, n):
+        for e in self.engines:
+            e.keyset_reserve(n)
+
+    def keyset_double_mul_bytes(self, k_scalars, l_scalars, ids, comb=None, out=None, status=None):
+        k, l, i = _host(k_scalars, 4), _host(l_scalars, 4), np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        self._same_len(k, l, i)
+        return self._sharded(lambda e, k, l, i, o, st: e.keyset_double_mul_bytes(k, l, i, comb, out=o, status=st), [k, l, i],
+                             [_out(out, len(k), 32, np.uint8), _out(status, len(k), None, np.uint8)])
+
+    def sig_verify_keyed(self, ids, msgs, sig64, lens=None, comb=None, ok=None, status=None):
+        i, sig, m = np.ascontiguousarray(ids, dtype=np.uint32).ravel(), _host(sig64, 64, np.uint8), np.ascontiguousarray(msgs, dtype=np.uint8)
+        ln = np.full(len(m), m.shape[1], dtype=np.uint32) if lens is None else np.ascontiguousarray(lens, dtype=np.uint32).ravel()
+        self._same_len(i, sig, m, ln)
+        return self._sharded(lambda e, i, m, sig, ln, o, st: e.sig_verify_keyed(i, m, sig, ln, comb, ok=o, status=st), [i, m, sig, ln],
+                             [_out(ok, len(i), None, np.uint8), _out(status, len(i), None, np.uint8)])
+
     def hash_to_curve(self, msgs, lens=None, dst=b"", mode="ro", affine=False, out=None):
         m = np.ascontiguousarray(msgs, dtype=np.uint8)
         ln = np.full(len(m), m.shape[1], dtype=np.uint32) if lens is None else np.ascontiguousarray(lens, dtype=np.uint32).ravel()

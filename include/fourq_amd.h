@@ -491,6 +491,70 @@ int fourq_sig_verify_batch_dev(fourq_ctx *ctx, const uint8_t *pk32, const uint64
                                const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
                                const uint8_t *sig64, uint8_t *ok, uint8_t *status, size_t n);
 
+/* ---- signatures of registered keys: [s]G + [h]A_id through one comb per key ------------------------------------------------------------
+ * A verifier of a validator set, a fleet's certificates or a CA list sees the same public keys again and again: A is as fixed as G.  The
+ * context holds one comb per registered key (the object of fourq_commit_bases_set: FOURQ_COMB_POINTS x 144 bytes, 155 KiB per key, 620 MiB
+ * for 4 096), rows name their key by index, and one kernel walks G's comb and key id's comb in ONE accumulator: 6 doublings + 54 mixed
+ * additions instead of a comb, a variable-base MUL_endo ladder with its endomorphism table, and the combiner.
+ *
+ * fourq_keyset_set(ctx, pk32, m, key_status): m x 32 bytes on the HOST; key_status: m bytes on the host, or NULL.  Synchronous.  Decodes
+ * the keys on the device, checks every decoded point for order N, builds one comb per accepted key and keeps the 32 bytes and the status
+ * byte of every slot on the device.  The old set is replaced only once the new one is complete.  The set is its own: the commitment bases,
+ * the staged comb and the staged tables are untouched; it survives fourq_ctx_set_stream and is freed with the context.  m == 0 or
+ * m > FOURQ_KEYSET_MAX_KEYS: FOURQ_ERR_INVALID, and the old set stays.  fourq_keyset_count: the size of the set, 0 when none was set.
+ *   key_status[j]   0 accepted | FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_* when the bytes do not decode | FOURQ_KEYSET_NOT_ORDER_N when they
+ *                   decode to a point A with [N]A != (0, 1).  A refused slot is still a slot of the set (the indices of the others do not
+ *                   move); its comb is all zero and never contributes to a result.
+ * Why the order check: for an even scalar the comb computes -[N - k]A, which is [k]A only for A of order N.  fourq_commit_bases_set leaves
+ * that to its caller; public keys come from outside.  The check is [N]A by plain double-and-add with the complete addition (neither
+ * MUL_endo nor MUL_windowed is [k]P outside the subgroup): (-x, -y) of an honest key, of order 2N, decodes and is refused here.
+ *
+ * fourq_keyset_double_mul_bytes[_dev]: out32[i] = encode([k_i]B + [l_i]A_{id_i}); scalars any value in [0, 2^256); the neutral point is an
+ * ordinary result (01 00 .. 00).  For an accepted key, out32 and status equal fourq_double_mul_bytes_batch on points32[i] = key[id_i] byte
+ * for byte.
+ * fourq_keyset_sig_verify[_dev]: h = LE(SHA-512(R || key_bytes[id] || msg)) mod N with the key bytes exactly as registered;
+ * ok = (encode([s]G + [h]A_id) == R).  For an accepted key, ok and status equal fourq_sig_verify_batch on pk32[i] = key[id_i].  Messages
+ * and their rules are those of fourq_sig_verify_batch[_dev].
+ *   status[i], in this order of precedence:
+ *     FOURQ_KEYSET_ID_RANGE    key_ids[i] >= the set's size.  The host-pointer calls can look and return FOURQ_ERR_INVALID instead; the _dev
+ *                              calls clamp the index before it becomes an address, so nothing outside the set is read.
+ *     the key's own status     FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_*, or FOURQ_KEYSET_NOT_ORDER_N
+ *     FOURQ_SIG_MSG_CLAMPED    (_dev verify)
+ *     FOURQ_SIG_S_RANGE        (verify)
+ *   ok[i] = 0 for every non-zero status; out32[i] is all zero for the first two.
+ * `comb`: the generator's table, or NULL = the staged comb, as everywhere.  A NULL context is refused before anything else is looked at.
+ * n == 0: FOURQ_OK, nothing touched.  FOURQ_ERR_INVALID: no set installed, n > FOURQ_MAX_BATCH, a NULL array.  _dev: every array pointer
+ * 16-byte aligned, key_ids included (status and ok need not be).  The intermediates live in the context's work buffer; fourq_ctx_reserve
+ * does not cover them, fourq_keyset_reserve(ctx, n) does: after it a _dev call of at most n rows allocates and synchronises nothing, every
+ * launch's geometry follows from n on the host, and the call can be captured into a graph.  The host-pointer calls run the chunked
+ * pipeline, key_ids a 4-byte-per-row input.
+ * Constant-time selection (fourq_ctx_set_ct_select): a verifier's inputs are public, but the scalar-level call may carry secrets, and a
+ * gathered address is a digit.  With it on, both calls gather the rows' key BYTES by index and run the existing routes
+ * (fourq_double_mul_bytes_batch_dev, fourq_sig_verify_batch_dev); statuses, bytes and ok are identical in both modes.
+ * Cost, measured against fourq_sig_verify_batch_dev on the same rows, pk32 = keys[ids] (profiles/keyset_timing.txt; device-resident, 32-byte
+ * messages, default mode; time as a fraction of the unkeyed call's, ids uniform random / sorted): 65536 rows: 0.419 / 0.421 over 1 key,
+ * 0.429 / 0.426 over 16, 0.456 / 0.447 over 256, 0.470 / 0.482 over 4 096; 2^20 rows: 0.363 / 0.364, 0.363 / 0.363, 0.364 / 0.362 and
+ * 0.372 / 0.362.  The spread of the unkeyed call's own timings was 0.0 to 4.0 %: the keyed route is faster by more than that at every
+ * measured shape, none excepted -- the random gather over the 620 MiB of 4 096 combs costs 5 % at 65536 rows and 3 % at 2^20.  With
+ * constant-time selection the time is the unkeyed route's plus the gather.  fourq_keyset_set took 0.33 ms per key: 22 ms for 64 keys,
+ * 1.36 s for 4 096. */
+#define FOURQ_KEYSET_MAX_KEYS 4096
+#define FOURQ_KEYSET_NOT_ORDER_N 96   /* key / row status: the key decodes to a point whose order is not N */
+#define FOURQ_KEYSET_ID_RANGE 112     /* row status of the _dev calls: key_ids[i] is not below the set's size */
+int fourq_keyset_set(fourq_ctx *ctx, const uint8_t *pk32, size_t m, uint8_t *key_status);
+int fourq_keyset_count(const fourq_ctx *ctx, size_t *m);
+int fourq_keyset_reserve(fourq_ctx *ctx, size_t n);
+int fourq_keyset_double_mul_bytes(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                                  const uint32_t *key_ids, uint8_t *out32, uint8_t *status, size_t n);
+int fourq_keyset_double_mul_bytes_dev(fourq_ctx *ctx, const uint64_t *k_scalars, const uint64_t *comb, const uint64_t *l_scalars,
+                                      const uint32_t *key_ids, uint8_t *out32, uint8_t *status, size_t n);
+int fourq_keyset_sig_verify(fourq_ctx *ctx, const uint32_t *key_ids, const uint64_t *comb,
+                                 const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                                 const uint8_t *sig64, uint8_t *ok, uint8_t *status, size_t n);
+int fourq_keyset_sig_verify_dev(fourq_ctx *ctx, const uint32_t *key_ids, const uint64_t *comb,
+                                     const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                                     const uint8_t *sig64, uint8_t *ok, uint8_t *status, size_t n);
+
 /* ---- bytes to a point: hash to curve (RFC 9380) with SHA-512 XMD, Elligator 2 and the x392 chain on the device -----------------------------
  * RFC 9380's construction instantiated for FourQ.  The suite names FourQ_XMD:SHA-512_ELL2_RO_ and FourQ_XMD:SHA-512_ELL2_NU_ are OURS: no
  * such suite is registered with the RFC or anywhere else, and no other implementation was available to check against -- the yardstick is
