@@ -507,7 +507,9 @@ int fourq_sig_verify_batch_dev(fourq_ctx *ctx, const uint8_t *pk32, const uint64
  *                   move); its comb is all zero and never contributes to a result.
  * Why the order check: for an even scalar the comb computes -[N - k]A, which is [k]A only for A of order N.  fourq_commit_bases_set leaves
  * that to its caller; public keys come from outside.  The check is [N]A by plain double-and-add with the complete addition (neither
- * MUL_endo nor MUL_windowed is [k]P outside the subgroup): (-x, -y) of an honest key, of order 2N, decodes and is refused here.
+ * MUL_endo nor MUL_windowed is [k]P outside the subgroup): (-x, -y) of an honest key, of order 2N, decodes and is refused here.  The
+ * neutral point can never be a registered key: its encoding 01 00 .. 00, like those of the point of order 2 and of both points of order 4
+ * (x0 = 0), does not decode (FOURQ_DECODE_REF_ATTRIBUTE_ERROR), so [N]O = O never reaches the order check.
  *
  * fourq_keyset_double_mul_bytes[_dev]: out32[i] = encode([k_i]B + [l_i]A_{id_i}); scalars any value in [0, 2^256); the neutral point is an
  * ordinary result (01 00 .. 00).  For an accepted key, out32 and status equal fourq_double_mul_bytes_batch on points32[i] = key[id_i] byte
