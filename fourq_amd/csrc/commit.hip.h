@@ -43,17 +43,17 @@ template <bool CT> FQ_DEV void commit_row(const u64* scalars, const u32* table, 
             if constexpr (CT) {
                 const ScanMem<S::BLOCK_POINTS, u32> block{ table + (j << (S::W - 1)) * COMB_LDS_U32, COMB_LDS_U32 };
                 if (i == S::E - 1 && j == 0) { Q = affine_scan_start(block, comb_index(c, col), neg); continue; }
-                if (j == 0) Q = dbl<COMB_MODE>(Q.X, Q.Y, Q.Z);
-                Q = add_affine_scan<COMB_MODE>(Q, block, comb_index(c, col), neg);
+                if (j == 0) Q = dbl<Mul::Signed>(Q.X, Q.Y, Q.Z);
+                Q = add_affine_scan(Q, block, comb_index(c, col), neg);
             } else {
                 const u32* entry = table + ((j << (S::W - 1)) + comb_index(c, col)) * COMB_LDS_U32;
                 if (i == S::E - 1 && j == 0) { Q = affine_table_start(entry, neg); continue; }
-                if (j == 0) Q = dbl<COMB_MODE>(Q.X, Q.Y, Q.Z);
-                Q = add_affine_table<COMB_MODE>(Q, entry, neg);
+                if (j == 0) Q = dbl<Mul::Signed>(Q.X, Q.Y, Q.Z);
+                Q = add_affine_table(Q, entry, neg);
             }
         }
     }
-    Q = ladder_result<COMB_MODE>(Q);
+    Q = r1_unsign(Q);
     if (!live) return;
     u64 w[12];
     store_fe2(w, fe2_carry(fe2_cneg(Q.X, c.negate)));           // even scalar: [k]B = -[N - k]B, -(x, y) = (-x, y)

@@ -48,16 +48,6 @@ template <int BX, int BY, int BZ> struct Proj {   // (X, Y, Z) on E or on the is
 FQ_DEV R2s as_signed(const R2& t) {
     R2s r; r.N = t.N; r.D = t.D; r.E = t.E; r.F = widen<2>(t.F); return r;
 }
-// selectpt(s, T[i], nT[i]) with nT = R2neg(T) = (D, N, E, -F)         curve4q.py:193-206
-// neg_mask = ~0 selects the negated entry, 0 the entry itself; branch-free.
-FQ_DEV R2s r2_apply_sign(const R2& t, u32 neg_mask) {
-    R2s r;
-    r.N = fe2_select(neg_mask, t.D, t.N);
-    r.D = fe2_select(neg_mask, t.N, t.D);
-    r.E = t.E;
-    r.F = fe2_select(neg_mask, fe2_neg(t.F), widen<2>(t.F));
-    return r;
-}
 
 FQ_DEV R1 affine_to_r1(const Fe2<1>& x, const Fe2<1>& y) {            // curve4q.py:100-101
     R1 p; p.X = x; p.Y = y; p.Z = fe2_one(); p.Ta = widen<4>(x); p.Tb = widen<2>(y); return p;
@@ -87,31 +77,31 @@ FQ_DEV Proj<1, 1, 1> r2_to_r4(const R2s& t) {                          // curve4
 }
 
 // R1/R4 -> R1                                                          curve4q.py:138-152
-// CH: 0 plain, 1 chained carries, 2 chained carries on signed limbs (fp127.hip.h; the ladders only)
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0> FQ_DEV R1 dbl(const Fe2<1>& X, const Fe2<1>& Y, const Fe2<1>& Z) {
-    Fe2<1> A = fe2_sqrx<CH>(X);
-    Fe2<1> B = fe2_sqrx<CH>(Y);
-    Fe2<2> C = fe2_dbl(fe2_sqrx<CH>(Z));
+// M: the flavour of its seven products (fp127.hip.h, Mul); Mul::Signed takes and returns signed limbs (the combs)
+template <Mul M = MUL_GROUP> FQ_DEV R1 dbl(const Fe2<1>& X, const Fe2<1>& Y, const Fe2<1>& Z) {
+    Fe2<1> A = fe2_sqrx<M>(X);
+    Fe2<1> B = fe2_sqrx<M>(Y);
+    Fe2<2> C = fe2_dbl(fe2_sqrx<M>(Z));
     Fe2<2> D = fe2_add(A, B);
-    if constexpr (CH == 2) {       // signed: differences carry no bias; G (bound 4) must be a FIRST operand (8*b fits 32 bits signed)
-        Fe2<3> E = fe2_sub_signed(fe2_sqrx<CH>(fe2_add(X, Y)), D);
+    if constexpr (M == Mul::Signed) {   // differences carry no bias; G (bound 4) must be a FIRST operand (8*b fits 32 bits signed)
+        Fe2<3> E = fe2_sub_signed(fe2_sqrx<M>(fe2_add(X, Y)), D);
         Fe2<2> F = fe2_sub_signed(B, A);
         Fe2<4> G = fe2_sub_signed(C, F);
         R1 r;
-        r.X = fe2_mulx<CH>(G, E);
-        r.Z = fe2_mulx<CH>(G, F);
-        r.Y = fe2_mulx<CH>(D, F);
+        r.X = fe2_mulx<M>(G, E);
+        r.Z = fe2_mulx<M>(G, F);
+        r.Y = fe2_mulx<M>(D, F);
         r.Ta = widen<4>(E);
         r.Tb = D;
         return r;
     } else {
-        Fe2<4> E = fe2_sub(fe2_sqrx<CH>(fe2_add(X, Y)), D);
+        Fe2<4> E = fe2_sub(fe2_sqrx<M>(fe2_add(X, Y)), D);
         Fe2<3> F = fe2_sub(B, A);
         Fe2<6> G = fe2_sub(C, F);
         R1 r;                  // operand roles chosen so that 8*G (second operand) and -F.im (first) are shared
-        r.X = fe2_mulx<CH>(E, G);
-        r.Z = fe2_mulx<CH>(F, G);
-        r.Y = fe2_mulx<CH>(F, D);
+        r.X = fe2_mulx<M>(E, G);
+        r.Z = fe2_mulx<M>(F, G);
+        r.Y = fe2_mulx<M>(F, D);
         r.Ta = E;
         r.Tb = D;
         return r;
@@ -435,34 +425,30 @@ template <typename L, typename P> FQ_DEV void load_signed_nd(const P* entry, u32
     N = fe2_bitselect(neg_mask, d, n);
     D = fe2_bitselect(neg_mask, n, d);
 }
-template <int CH, int A, int B> FQ_DEV auto fe2_subx(const Fe2<A>& a, const Fe2<B>& b) {
-    if constexpr (CH == 2) return widen<A + B + 1>(fe2_sub_signed(a, b)); else return fe2_sub(a, b);
-}
-template <int CH, int B> FQ_DEV auto fe2_cnegx(const Fe2<B>& x, u32 mask) {
-    if constexpr (CH == 2) return widen<B + 1>(fe2_cneg_signed(x, mask)); else return fe2_cneg(x, mask);
-}
-// Q + (+-T) for a table entry T read coordinate by coordinate from `entry` (HBM scratch or LDS):
+// Q + (+-T) for a whole table entry T (LimbSlots) read coordinate by coordinate from `entry` (HBM scratch or LDS):
 // ADD(Q, selectpt(s, T, R2neg(T))) of curve4q.py:232-233, :440 with R2neg(T) = (D, N, E, -F).  The N/D swap
 // of the negated entry is a masked select (load_signed_nd), -F is a two-op conditional negation, and E, F are
-// loaded just before the products that consume them, which keeps the live set near 110 VGPRs.
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename P> FQ_DEV R1 add_table(const R1& q, const P* entry, u32 neg_mask) {
-    Fe2<1> T = fe2_mulx<CH>(q.Ta, q.Tb);                          // R1toR3: curve4q.py:119-126
+// loaded just before the products that consume them, which keeps the live set near 110 VGPRs.  hipcc's addition on unsigned limbs, the
+// unit's MUL_GROUP products like dbl(): the comb table's ladder (kernels.hip.h, ladder_endo_hipcc) and the microbenchmarks.
+template <typename P> FQ_DEV R1 add_table(const R1& q, const P* entry, u32 neg_mask) {
+    constexpr Mul M = MUL_GROUP;
+    Fe2<1> T = fe2_mulx<M>(q.Ta, q.Tb);                            // R1toR3: curve4q.py:119-126
     Fe2<2> N1 = fe2_add(q.X, q.Y);
-    Fe2<3> D1 = fe2_subx<CH>(q.Y, q.X);
+    Fe2<3> D1 = fe2_sub(q.Y, q.X);
     Fe2<1> tN, tD;
-    load_signed_nd<L>(entry, neg_mask, tN, tD);
-    Fe2<1> A = fe2_mulx<CH>(D1, tD);                               // ADD_core: curve4q.py:155-171
-    Fe2<1> B = fe2_mulx<CH>(N1, tN);
-    Fe2<1> C = fe2_mulx<CH>(fe2_cnegx<CH>(L::load(entry + 3 * L::COORD), neg_mask), T);
-    Fe2<1> D = fe2_mulx<CH>(L::load(entry + 2 * L::COORD), q.Z);
-    Fe2<3> E = fe2_subx<CH>(B, A);
-    Fe2<3> F = fe2_subx<CH>(D, C);
+    load_signed_nd<LimbSlots>(entry, neg_mask, tN, tD);
+    Fe2<1> A = fe2_mulx<M>(D1, tD);                                // ADD_core: curve4q.py:155-171
+    Fe2<1> B = fe2_mulx<M>(N1, tN);
+    Fe2<1> C = fe2_mulx<M>(fe2_cneg(load_fe2_limbs(entry + 3 * COORD_U32), neg_mask), T);
+    Fe2<1> D = fe2_mulx<M>(load_fe2_limbs(entry + 2 * COORD_U32), q.Z);
+    Fe2<3> E = fe2_sub(B, A);
+    Fe2<3> F = fe2_sub(D, C);
     Fe2<2> G = fe2_add(D, C);
     Fe2<2> H = fe2_add(B, A);
     R1 r;                      // 8*F shared by X and Z, -G.im shared by Z and Y
-    r.X = fe2_mulx<CH>(E, F);
-    r.Z = fe2_mulx<CH>(G, F);
-    r.Y = fe2_mulx<CH>(G, H);
+    r.X = fe2_mulx<M>(E, F);
+    r.Z = fe2_mulx<M>(G, F);
+    r.Y = fe2_mulx<M>(G, H);
     r.Ta = widen<4>(E);
     r.Tb = H;
     return r;
@@ -474,9 +460,8 @@ struct EntryRegs {
     Fe2<1> N, D, E, F;
 };
 // `ef` (kernels.hip.h: LdsEF / NoEF): where E and F come from -- the entry itself, or the lane's copy of them in LDS
-template <typename L = LimbSlots, typename P, typename EF> FQ_DEV EntryRegs load_entry(const P* entry, u32 neg_mask, u32 digit, const EF& ef) {
+template <typename L = LimbSlots, typename P, typename EF> FQ_DEV EntryRegs load_entry(const P* entry, u32 digit, const EF& ef) {
     EntryRegs t;
-    (void)neg_mask;
     load_nd<L>(entry, t.N, t.D);                                    // the sign is applied by add_asm, behind the doubling
     if constexpr (EF::ON) {
         t.E = ef.get(digit, 0); t.F = ef.get(digit, 1);
@@ -493,36 +478,31 @@ template <int B> FQ_DEV void fe2_here(Fe2<B>& x) {
 #pragma unroll
     for (int i = 0; i < 5; i++) { FQ_SIGN_UNKNOWN(x.re.l[i]); FQ_SIGN_UNKNOWN(x.im.l[i]); }
 }
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename P> FQ_DEV R1 add_affine_table(const R1& q, const P* entry, u32 neg_mask) {
+// Signed limbs (Mul::Signed, with dbl<Mul::Signed>): Q in and out are signed, the entry's limbs non-negative.
+template <typename P> FQ_DEV R1 add_affine_table(const R1& q, const P* entry, u32 neg_mask) {
     // In the comb's loop Q reaches this addition through a join (the doubling is conditional), and hipcc sign-extends the limbs
     // of Ta and Tb on the far side of it: instruction selection, which works block by block, then sees 64-bit operands and
     // expands each of 90 products into v_mad_u64_u32 + 2 v_mul_lo_u32 + v_add3_u32.  Opaque copies keep the limbs 32-bit here.
     Fe2<4> Ta = q.Ta;
     Fe2<2> Tb = q.Tb;
-    if constexpr (CH == 2) { fe2_here(Ta); fe2_here(Tb); }
-    Fe2<1> T = fe2_mulx<CH>(Ta, Tb);
+    fe2_here(Ta); fe2_here(Tb);
+    Fe2<1> T = fe2_mul_signed(Ta, Tb);
     Fe2<2> N1 = fe2_add(q.X, q.Y);
-    Fe2<3> D1 = fe2_subx<CH>(q.Y, q.X);
+    Fe2<2> D1 = fe2_sub_signed(q.Y, q.X);
     Fe2<1> tN, tD;
     load_signed_nd<LimbSlots>(entry, neg_mask, tN, tD);
-    Fe2<1> A = fe2_mulx<CH>(D1, tD);
-    Fe2<1> B = fe2_mulx<CH>(N1, tN);
-    Fe2<1> C = fe2_mulx<CH>(fe2_cnegx<CH>(load_fe2_limbs(entry + 2 * COORD_U32), neg_mask), T);
+    Fe2<1> A = fe2_mul_signed(D1, tD);
+    Fe2<1> B = fe2_mul_signed(N1, tN);
+    Fe2<1> C = fe2_mul_signed(fe2_cneg_signed(load_fe2_limbs(entry + 2 * COORD_U32), neg_mask), T);
     Fe2<2> D = fe2_dbl(q.Z);
-    Fe2<3> E = fe2_subx<CH>(B, A);
+    Fe2<2> E = fe2_sub_signed(B, A);
     Fe2<3> G = fe2_add(D, C);
     Fe2<2> H = fe2_add(B, A);
+    Fe2<3> F = fe2_sub_signed(D, C);                               // bound 3: fits the 8*b operand
     R1 r;
-    if constexpr (CH == 2) {       // signed: D - C has bound 3 and fits the 8*b operand
-        Fe2<3> F = fe2_sub_signed(D, C);
-        r.X = fe2_mulx<CH>(E, F);
-        r.Z = fe2_mulx<CH>(G, F);
-    } else {
-        Fe2<4> F = fe2_sub(D, C);
-        r.X = fe2_mulx<CH>(E, F);
-        r.Z = fe2_mulx<CH>(G, F);
-    }
-    r.Y = fe2_mulx<CH>(G, H);
+    r.X = fe2_mul_signed(E, F);
+    r.Z = fe2_mul_signed(G, F);
+    r.Y = fe2_mul_signed(G, H);
     r.Ta = widen<4>(E);
     r.Tb = H;
     return r;
@@ -680,34 +660,28 @@ template <typename SRC> FQ_DEV Proj<1, 1, 1> start_scan(const SRC& src, u32 digi
     return r;
 }
 // the comb's mixed addition and starting point with every one of the block's entries read (3 coordinates each)
-template <int CH, typename SRC> FQ_DEV R1 add_affine_scan(const R1& q, const SRC& src, u32 idx_value, u32 neg_mask) {
+template <typename SRC> FQ_DEV R1 add_affine_scan(const R1& q, const SRC& src, u32 idx_value, u32 neg_mask) {
     const typename SRC::Bits idx(idx_value);
     Fe2<4> Ta = q.Ta;
     Fe2<2> Tb = q.Tb;
-    if constexpr (CH == 2) { fe2_here(Ta); fe2_here(Tb); }      // as in add_affine_table: keeps the 90 products single instructions
-    Fe2<1> T = fe2_mulx<CH>(Ta, Tb);
+    fe2_here(Ta); fe2_here(Tb);                                 // as in add_affine_table: keeps the 90 products single instructions
+    Fe2<1> T = fe2_mul_signed(Ta, Tb);
     Fe2<2> N1 = fe2_add(q.X, q.Y);
-    Fe2<3> D1 = fe2_subx<CH>(q.Y, q.X);
+    Fe2<2> D1 = fe2_sub_signed(q.Y, q.X);
     Fe2<1> tN = src.coord(idx, 0), tD = src.coord(idx, 1);
     fe2_cswap(tN, tD, neg_mask);
-    Fe2<1> A = fe2_mulx<CH>(D1, tD);
-    Fe2<1> B = fe2_mulx<CH>(N1, tN);
-    Fe2<1> C = fe2_mulx<CH>(fe2_cnegx<CH>(src.coord(idx, 2), neg_mask), T);
+    Fe2<1> A = fe2_mul_signed(D1, tD);
+    Fe2<1> B = fe2_mul_signed(N1, tN);
+    Fe2<1> C = fe2_mul_signed(fe2_cneg_signed(src.coord(idx, 2), neg_mask), T);
     Fe2<2> D = fe2_dbl(q.Z);
-    Fe2<3> E = fe2_subx<CH>(B, A);
+    Fe2<2> E = fe2_sub_signed(B, A);
     Fe2<3> G = fe2_add(D, C);
     Fe2<2> H = fe2_add(B, A);
+    Fe2<3> F = fe2_sub_signed(D, C);
     R1 r;
-    if constexpr (CH == 2) {
-        Fe2<3> F = fe2_sub_signed(D, C);
-        r.X = fe2_mulx<CH>(E, F);
-        r.Z = fe2_mulx<CH>(G, F);
-    } else {
-        Fe2<4> F = fe2_sub(D, C);
-        r.X = fe2_mulx<CH>(E, F);
-        r.Z = fe2_mulx<CH>(G, F);
-    }
-    r.Y = fe2_mulx<CH>(G, H);
+    r.X = fe2_mul_signed(E, F);
+    r.Z = fe2_mul_signed(G, F);
+    r.Y = fe2_mul_signed(G, H);
     r.Ta = widen<4>(E);
     r.Tb = H;
     return r;

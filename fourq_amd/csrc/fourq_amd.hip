@@ -124,7 +124,7 @@ __global__ __launch_bounds__(BLOCK) void comb_table_kernel(const u64* p_r1, u32*
     build_table_endo(P, slot);
     u64 v[4];
     decompose(m, v);
-    R1 Q = ladder_endo(recode(v), slot, R2_LIMBS);
+    R1 Q = ladder_endo_hipcc(recode(v), slot, R2_LIMBS);
     Fe2<1> x, y;
     r1_to_affine(Q, x, y);
     u64* dst = comb + 12 * (size_t)t;
@@ -1525,7 +1525,7 @@ FQ_API int fourq_mul_endo_mixed_batch_dev(fourq_ctx* c, const uint64_t* s, const
         if ((rc = launch_ladder<ENDO, FUSED, false>(c, av))) return rc;
         const size_t tail_blocks = ((size_t)m + BLOCK - 1) / BLOCK, tail_max = c->lanes_w4 / BLOCK;
         HIPRC_TRY(c, ct_launch_mixed_tail((limit + BLOCK - 1) / BLOCK, (unsigned)(tail_blocks < tail_max ? tail_blocks : tail_max), c->stream, a,
-                                          c->part_fix, c->part_list, c->part_counter, over_scratch, (u32)c->lanes, limit));
+                                          c->part_fix, c->part_list, c->part_counter, over_scratch));
     }
     return FOURQ_OK;
 }

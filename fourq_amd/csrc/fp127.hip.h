@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ladder_asm_gfx950.inc"   // the generated instruction streams, as string macros: fe2_mul_asm / fe2_sqr_asm below, the rest in ladder_asm.hip.h
 
 namespace fq {
 
@@ -243,22 +244,60 @@ template <int A, int B> FQ_DEV Fe2<1> fe2_mul_plain(const Fe2<A>& a, const Fe2<B
     r.im = fe_mac2<true>(a.re.l, b.im.l, b1x8, a.im.l, b.re.l, b0x8);
     return r;
 }
-// MODE selects the variant per call site (0 plain, 1 chained carries, 2 chained carries on SIGNED limbs, see the
-// signed flavour at the end of this file); the plain name follows the translation unit's default
-template <int A, int B> FQ_DEV Fe2<1> fe2_mul_signed(const Fe2<A>& a, const Fe2<B>& b);
+// operands of the generated bodies (ladder_asm_gfx950.inc): the ten limbs of a GF(p^2) element, the five of a GF(p) element
+#define FQ_FE2_IO(p) "+v"(p.re.l[0]), "+v"(p.re.l[1]), "+v"(p.re.l[2]), "+v"(p.re.l[3]), "+v"(p.re.l[4]), "+v"(p.im.l[0]), "+v"(p.im.l[1]), "+v"(p.im.l[2]), "+v"(p.im.l[3]), "+v"(p.im.l[4])
+#define FQ_FE2_OUT(p) "=&v"(p.re.l[0]), "=&v"(p.re.l[1]), "=&v"(p.re.l[2]), "=&v"(p.re.l[3]), "=&v"(p.re.l[4]), "=&v"(p.im.l[0]), "=&v"(p.im.l[1]), "=&v"(p.im.l[2]), "=&v"(p.im.l[3]), "=&v"(p.im.l[4])
+#define FQ_FE2_IN(p) "v"(p.re.l[0]), "v"(p.re.l[1]), "v"(p.re.l[2]), "v"(p.re.l[3]), "v"(p.re.l[4]), "v"(p.im.l[0]), "v"(p.im.l[1]), "v"(p.im.l[2]), "v"(p.im.l[3]), "v"(p.im.l[4])
+#define FQ_FE_IN(p) "v"(p.l[0]), "v"(p.l[1]), "v"(p.l[2]), "v"(p.l[3]), "v"(p.l[4])
+// One GF(p^2) product / square of the UNSIGNED flavour as one generated body each (FQ_ASM_MULU 138 instructions, FQ_ASM_SQRU 88;
+// tools/asmgen/gen_ladder_step.py): the same operations as fe2_mul_plain / fe2_sqr_plain, same bounds checked here, no fences, no hazard
+// nops.  The negation and the sums stay with the compiler.
+template <int A, int B> FQ_DEV Fe2<1> fe2_mul_asm(const Fe2<A>& a, const Fe2<B>& b) {              // fields.py:167-173
+    static_assert(cols_ok((u64)(2 * A + 1) * B), "column overflow");
+    static_assert((u64)8 * B * UNIT < (1ull << 32), "8*b does not fit 32 bits");
+    const Fe<A + 1> na = fe_neg(a.im);
+    const u32 mask = LIMB_MASK;
+    Fe2<1> c;
+    asm(FQ_ASM_MULU : FQ_FE2_OUT(c) : FQ_FE2_IN(a), FQ_FE_IN(na), FQ_FE2_IN(b), "v"(mask) : FQ_ASM_SMALL_CLOBBERS);
+    return c;
+}
+template <int A> FQ_DEV Fe2<1> fe2_sqr_asm(const Fe2<A>& a) {                                         // fields.py:176-181
+    const Fe<2 * A> s = fe_add(a.re, a.im);
+    const Fe<2 * A + 1> d = fe_sub(a.re, a.im);
+    const Fe<2 * A> t = fe_dbl(a.re);
+    static_assert(cols_ok((u64)(2 * A + 1) * (2 * A)), "column overflow");
+    static_assert((u64)8 * (2 * A) * UNIT < (1ull << 32), "8*s does not fit 32 bits");
+    const u32 mask = LIMB_MASK;
+    Fe2<1> c;
+    asm(FQ_ASM_SQRU : FQ_FE2_OUT(c) : FQ_FE_IN(d), FQ_FE_IN(s), FQ_FE_IN(t), FQ_FE_IN(a.im), "v"(mask) : FQ_ASM_SMALL_CLOBBERS);
+    return c;
+}
+
+// ---- the flavours of a GF(p^2) product ------------------------------------------------------------
+// Every hot kernel is bound by VALU issue, so the same product exists in four flavours and a call site names the one it was measured with:
+enum class Mul {
+    Plain,    // fe2_mul_plain / fe2_sqr_plain: hipcc's own schedule, the carry a 64-bit addition per limb
+    Chain,    // fe2_mul_chain / fe2_sqr_chain: each column's carry kept inside the multiply-add chain
+    Signed,   // fe2_mul_signed / fe2_sqr_signed: chained carries on SIGNED limbs (the signed flavour at the end of this file); what
+              // hipcc's group law runs on in the combs.  Operands and results are signed: they leave through fe_unsign
+    Gen,      // fe2_mul_asm / fe2_sqr_asm: ONE generated unsigned product per call.  (A whole ladder step as generated signed bodies
+              // is not a flavour of the product: ladder_asm.hip.h)
+};
+// What a translation unit gets when it names no flavour.  FQ_CHAIN=1 units chain everywhere.  In FQ_CHAIN=0 units the two differ ON
+// PURPOSE: the field products (the table construction, add_core, the endomorphisms, DH's epilogue) are the generated streams, while the
+// group law written as dbl() / add_table() -- the cofactor chain, the primitive kernels, the comb table's ladder -- stays on hipcc's plain
+// products, as it was measured: clear_cofactor_392's doublings run Plain beside an add_core that runs Gen.
+constexpr Mul MUL_FIELD = (FQ_CHAIN != 0) ? Mul::Chain : Mul::Gen;     // fe2_mul(), fe2_sqr()
+constexpr Mul MUL_GROUP = (FQ_CHAIN != 0) ? Mul::Chain : Mul::Plain;   // dbl(), add_table() of curve.hip.h
+template <int A, int B> FQ_DEV Fe2<1> fe2_mul_signed(const Fe2<A>& a, const Fe2<B>& b);   // defined with the signed flavour, below
 template <int A> FQ_DEV Fe2<1> fe2_sqr_signed(const Fe2<A>& a);
-template <int A, int B> FQ_DEV Fe2<1> fe2_mul_asm(const Fe2<A>& a, const Fe2<B>& b);      // ladder_asm.hip.h
-template <int A> FQ_DEV Fe2<1> fe2_sqr_asm(const Fe2<A>& a);
-template <int MODE, int A, int B> FQ_DEV Fe2<1> fe2_mulx(const Fe2<A>& a, const Fe2<B>& b) {
-    if constexpr (MODE == 3) return fe2_mul_asm(a, b);
-    else if constexpr (MODE == 2) return fe2_mul_signed(a, b);
-    else if constexpr (MODE == 1) return fe2_mul_chain(a, b);
+template <Mul M, int A, int B> FQ_DEV Fe2<1> fe2_mulx(const Fe2<A>& a, const Fe2<B>& b) {
+    if constexpr (M == Mul::Gen) return fe2_mul_asm(a, b);
+    else if constexpr (M == Mul::Signed) return fe2_mul_signed(a, b);
+    else if constexpr (M == Mul::Chain) return fe2_mul_chain(a, b);
     else return fe2_mul_plain(a, b);
 }
-// FQ_CHAIN=0 units: the unsigned products and squares are the generated instruction streams FQ_ASM_MULU / FQ_ASM_SQRU
-// (ladder_asm.hip.h, tools/asmgen/gen_ladder_step.py): no fences, no hazard nops.  Mode 0 remains for the primitive kernels' dbl<0> / add_table<0>.
-constexpr int FE2_DEFAULT_MODE = (FQ_CHAIN != 0) ? 1 : 3;
-template <int A, int B> FQ_DEV Fe2<1> fe2_mul(const Fe2<A>& a, const Fe2<B>& b) { return fe2_mulx<FE2_DEFAULT_MODE>(a, b); }
+template <int A, int B> FQ_DEV Fe2<1> fe2_mul(const Fe2<A>& a, const Fe2<B>& b) { return fe2_mulx<MUL_FIELD>(a, b); }
 // (a0 + a1 i)^2 = (a0 + a1)(a0 - a1) + (2 a0 a1) i                               fields.py:176-181
 template <int A> FQ_DEV Fe2<1> fe2_sqr_chain(const Fe2<A>& a) {
     Fe<2 * A> s = fe_add(a.re, a.im);
@@ -301,13 +340,13 @@ template <int A> FQ_DEV Fe2<1> fe2_sqr_plain(const Fe2<A>& a) {
     return r;
 }
 
-template <int MODE, int A> FQ_DEV Fe2<1> fe2_sqrx(const Fe2<A>& a) {
-    if constexpr (MODE == 3) return fe2_sqr_asm(a);
-    else if constexpr (MODE == 2) return fe2_sqr_signed(a);
-    else if constexpr (MODE == 1) return fe2_sqr_chain(a);
+template <Mul M, int A> FQ_DEV Fe2<1> fe2_sqrx(const Fe2<A>& a) {
+    if constexpr (M == Mul::Gen) return fe2_sqr_asm(a);
+    else if constexpr (M == Mul::Signed) return fe2_sqr_signed(a);
+    else if constexpr (M == Mul::Chain) return fe2_sqr_chain(a);
     else return fe2_sqr_plain(a);
 }
-template <int A> FQ_DEV Fe2<1> fe2_sqr(const Fe2<A>& a) { return fe2_sqrx<FE2_DEFAULT_MODE>(a); }
+template <int A> FQ_DEV Fe2<1> fe2_sqr(const Fe2<A>& a) { return fe2_sqrx<MUL_FIELD>(a); }
 
 // ---- canonical form, packing --------------------------------------------------------------------
 // 128-bit little-endian container (what the C ABI carries) <-> limbs.

@@ -64,10 +64,6 @@ struct NoEF {
     static constexpr bool ON = false;
     FQ_DEV void put(int, const R2&) const {}
     FQ_DEV Fe2<1> get(u32, int) const { return Fe2<1>{}; }
-    FQ_DEV void park_nd(int, const Fe2<1>&, const Fe2<1>&) const {}
-    FQ_DEV void unpark_nd(int, Fe2<1>&, Fe2<1>&) const {}
-    FQ_DEV void park_xyz(int, const Fe2<1>&, const Fe2<1>&, const Fe2<1>&) const {}
-    FQ_DEV void unpark_xyz(int, Fe2<1>&, Fe2<1>&, Fe2<1>&) const {}
 };
 
 // entry k of a lane's table: with an LdsEF only N and D go to (come from) the HBM slot, E and F live in LDS alone
@@ -77,16 +73,6 @@ template <typename L, typename EF> FQ_DEV void store_entry(u32* slot, int k, con
         ef.put(k, t);
     } else {
         store_r2<L>(slot + k * L::ENTRY, t);
-    }
-}
-template <typename L, typename EF> FQ_DEV R2 load_entry_r2(const u32* slot, int k, const EF& ef) {
-    if constexpr (EF::ON) {
-        R2 t;
-        load_nd<L>(slot + k * L::ENTRY, t.N, t.D);
-        t.E = ef.get((u32)k, 0); t.F = ef.get((u32)k, 1);
-        return t;
-    } else {
-        return load_r2<L>(slot + k * L::ENTRY);
     }
 }
 
@@ -264,55 +250,41 @@ template <typename L = LimbSlots> FQ_DEV void build_table_endo_pipelined(const R
 }
 
 // ---- the ladders -------------------------------------------------------------------------------
-// Every ladder runs the products with chained carries on SIGNED limbs (fp127.hip.h "signed flavour": 5 % fewer instructions per
-// step; per-kernel A/Bs in DESIGN.md section 9), in one of two forms:
-//   CH = 3          the step as hand-scheduled asm bodies (ladder_asm.hip.h, tools/asmgen/gen_ladder_step.py), the entry in registers,
-//                   requested a doubling ahead.  The fused kernels, whose lone wave per SIMD pays for every issue slot
-//                   (profiles/r04_ladder_step.txt); the fixed-base ladders with the table in LDS (256 VGPRs, two waves per SIMD);
-//                   the constant-time ladders, where the whole-table scan (select trees, compiler code) produces the entry and
-//                   the bodies consume it.
-//   CH = LADDER_CH  hipcc's step on the same limbs, the entry read inside the addition: the comb.
-constexpr int LADDER_CH = 2;
-// a ladder on signed limbs (CH >= 2) hands its result back with non-negative limbs
-template <int CH> FQ_DEV R1 ladder_result(const R1& Q) {
-    if constexpr (CH >= 2) {
-        R1 r;
-        r.X = fe2_unsign(Q.X); r.Y = fe2_unsign(Q.Y); r.Z = fe2_unsign(Q.Z);
-        r.Ta = widen<4>(fe2_unsign(Q.Ta)); r.Tb = widen<2>(fe2_unsign(Q.Tb));
-        return r;
-    } else {
-        return Q;
-    }
+// Two forms exist:
+//   the bodies   Every product ladder: the step as hand-scheduled asm bodies on SIGNED limbs (ladder_asm.hip.h,
+//                tools/asmgen/gen_ladder_step.py; fp127.hip.h "signed flavour": 5 % fewer instructions per step, per-kernel A/Bs in DESIGN.md
+//                section 9), the entry in registers, requested a doubling ahead.  The fused kernels, whose lone wave per SIMD pays for
+//                every issue slot (profiles/r04_ladder_step.txt); the fixed-base ladders with the table in LDS (256 VGPRs, two waves per
+//                SIMD); the constant-time ladders, where the whole-table scan (select trees, compiler code) produces the entry and the
+//                bodies consume it.  Such a ladder leaves the signed flavour through r1_unsign or store_r1_signed.
+//   hipcc's      ladder_endo_hipcc: dbl() + add_table() on unsigned limbs with the unit's MUL_GROUP products, the entry read inside the
+//                addition.  Not a product ladder: comb_table_kernel runs it once per point of the comb when a context is created.
+// (The combs are no ladders: hipcc's dbl<Mul::Signed> + add_affine_table / add_affine_scan on signed limbs, left through r1_unsign too.)
+// signed limbs, every coordinate within its bound -> the same point on non-negative limbs
+FQ_DEV R1 r1_unsign(const R1& Q) {
+    R1 r;
+    r.X = fe2_unsign(Q.X); r.Y = fe2_unsign(Q.Y); r.Z = fe2_unsign(Q.Z);
+    r.Ta = widen<4>(fe2_unsign(Q.Ta)); r.Tb = widen<2>(fe2_unsign(Q.Tb));
+    return r;
 }
 // the ladder's first value: the starting entry (start_table / start_scan) as an R1 tuple, T = X * Y
 FQ_DEV R1 ladder_start(const Proj<1, 1, 1>& q4) {
     R1 Q; Q.X = q4.X; Q.Y = q4.Y; Q.Z = q4.Z; Q.Ta = widen<4>(q4.X); Q.Tb = widen<2>(q4.Y);
     return Q;
 }
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, typename TP> FQ_DEV R1 ladder_endo(const EndoDigits& e, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:436-442
-    Proj<1, 1, 1> q4 = start_table<L>(tbl + (e.top & 7) * stride, 0u);        // s[64] = 1: the entry itself
-    if constexpr (EF::ON) q4.Z = ef.get(e.top & 7, 0);
-    R1 Q = ladder_start(q4);
+template <typename TP> FQ_DEV R1 ladder_endo_hipcc(const EndoDigits& e, const TP* tbl, int stride) {   // curve4q.py:436-442
+    R1 Q = ladder_start(start_table(tbl + (e.top & 7) * stride, 0u));      // s[64] = 1: the entry itself
 #pragma unroll 1
     for (int i = 63; i >= 0; i--) {
-        const u32 digit = endo_digit(e, i);
-        const TP* entry = tbl + digit * stride;
-        if constexpr (CH == 3) {                  // the hand-scheduled bodies (ladder_asm.hip.h); the entry is requested ahead of the doubling
-            const u32 neg = endo_neg_mask(e, i);
-            EntryRegs t = load_entry<L>(entry, neg, digit, ef);
-            Fe2<1> T;
-            dblt_asm(Q.X, Q.Y, Q.Z, T);
-            add_asm(Q, T, t, neg);
-        } else {
-            Q = dbl<CH>(Q.X, Q.Y, Q.Z);
-            Q = add_table<CH, L>(Q, entry, endo_neg_mask(e, i));
-        }
+        const TP* entry = tbl + endo_digit(e, i) * stride;
+        Q = dbl(Q.X, Q.Y, Q.Z);
+        Q = add_table(Q, entry, endo_neg_mask(e, i));
     }
-    return ladder_result<CH>(Q);
+    return R1(Q);   // a copy: with Q itself built in the caller's result, hipcc allocates comb_table_kernel's registers another way
 }
-// The MUL_endo ladder on the nibble stream (recode_nibbles): same steps, same bodies, same R1 tuple as ladder_endo<3, L, EF>; what changes
-// is the glue between the bodies: per step one bit-field extract, one arithmetic shift (the negation mask) and one shift of the stream,
-// instead of four 64-bit shifts and five bit operations.  `at(digit)` is the address of an entry.
+// The MUL_endo ladder on the nibble stream (recode_nibbles): the bodies, one DBLT + ADD per digit.  The glue between them is per step one
+// bit-field extract, one arithmetic shift (the negation mask) and one shift of the stream (a walk over EndoDigits' digit words takes four
+// 64-bit shifts and five bit operations: VERDICT r5 item 4).  `at(digit)` is the address of an entry.
 // SIGNED_OUT: hand the ladder's point back on signed limbs (bound 1 each) -- for store_r1_signed, which folds the bias into the canonical
 // reduction of the final store
 template <typename L, typename EF, bool SIGNED_OUT, typename AT> FQ_DEV R1 ladder_endo_nibbles_by(const EndoNibbles& e, const AT& at, const EF& ef) {   // curve4q.py:436-442
@@ -332,14 +304,14 @@ template <typename L, typename EF, bool SIGNED_OUT, typename AT> FQ_DEV R1 ladde
             const u32 digit = (cur >> 28) & 7;                                    // top nibble, bits 0..2
             const u32 neg = (u32)((int32_t)cur >> 31);                            // its bit 3, spread: ~0 when the step subtracts
             cur <<= 4;
-            EntryRegs t = load_entry<L>(at(digit), neg, digit, ef);
+            EntryRegs t = load_entry<L>(at(digit), digit, ef);
             Fe2<1> T;
             dblt_asm(Q.X, Q.Y, Q.Z, T);
             add_asm(Q, T, t, neg);
         }
     }
     if constexpr (SIGNED_OUT) return Q;
-    else return ladder_result<3>(Q);
+    else return r1_unsign(Q);
 }
 // The fused kernels: the lane's entries addressed as a 32-bit dword offset on the kernel's scratch pointer (`base` is wave-uniform: the
 // loads take it as their scalar base) -- two multiply-adds for the two addresses of a step instead of two multiplications and a 64-bit
@@ -349,19 +321,20 @@ template <typename L, typename EF, bool SIGNED_OUT = false> FQ_DEV R1 ladder_end
     return ladder_endo_nibbles_by<L, EF, SIGNED_OUT>(e, [=](u32 d) { return base + (size_t)(lane_off + d * (u32)L::ENTRY); }, ef);
 }
 // Any table a pointer and an entry stride describe -- the shared fixed-base table in LDS (ladder_kernel<ENDO, LDS>) or in global memory
-// (the fixed-base items of mixed_queue_kernel): ladder_endo's addressing.
+// (the fixed-base items of mixed_queue_kernel).
 template <typename L, typename EF, typename TP> FQ_DEV R1 ladder_endo_nibbles_at(const EndoNibbles& e, const TP* tbl, int stride, const EF& ef = EF()) {
     return ladder_endo_nibbles_by<L, EF, false>(e, [=](u32 d) { return tbl + d * stride; }, ef);
 }
 // canonical words of a point the asm bodies left on SIGNED limbs (every limb of every coordinate within bound 1): bias, then fe_canon's
-// own carry -- what ladder_result<3> + store_r1 compute, with one carry chain per field element less
+// own carry -- what r1_unsign + store_r1 compute, with one carry chain per field element less
 template <int B> FQ_DEV void store_fe2_signed(u64* w, const Fe2<B>& a) {
     fe_canon(fe_unsign_wide(a.re), w[0], w[1]); fe_canon(fe_unsign_wide(a.im), w[2], w[3]);
 }
 FQ_DEV void store_r1_signed(u64* w, const R1& q) {
     store_fe2_signed(w, q.X); store_fe2_signed(w + 4, q.Y); store_fe2_signed(w + 8, q.Z); store_fe2_signed(w + 12, q.Ta); store_fe2_signed(w + 16, q.Tb);
 }
-template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF = NoEF, typename TP> FQ_DEV R1 ladder_windowed(const WinScalar& w, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:228-235
+// the windowed ladder on the bodies: three DBL, one DBLT + ADD per window
+template <typename L = LimbSlots, typename EF = NoEF, typename TP> FQ_DEV R1 ladder_windowed(const WinScalar& w, const TP* tbl, int stride, const EF& ef = EF()) {   // curve4q.py:228-235
     u32 code = win_top_code(w);
     Proj<1, 1, 1> q4 = start_table<L>(tbl + (code & 7) * stride, (code >> 3) - 1u);
     if constexpr (EF::ON) q4.Z = ef.get(code & 7, 0);
@@ -371,20 +344,14 @@ template <int CH = (FQ_CHAIN != 0) ? 1 : 0, typename L = LimbSlots, typename EF 
         code = win_code_from_window(win_window(w, i));
         const TP* entry = tbl + (code & 7) * stride;
         const u32 neg = (code >> 3) - 1u;
-        if constexpr (CH == 3) {
-            EntryRegs t = load_entry<L>(entry, neg, code & 7, ef);
+        EntryRegs t = load_entry<L>(entry, code & 7, ef);          // requested ahead of the doublings
 #pragma unroll 1
-            for (int k = 0; k < 3; k++) dbl_asm(Q.X, Q.Y, Q.Z);
-            Fe2<1> T;
-            dblt_asm(Q.X, Q.Y, Q.Z, T);
-            add_asm(Q, T, t, neg);
-        } else {
-#pragma unroll 1
-            for (int k = 0; k < 4; k++) Q = dbl<CH>(Q.X, Q.Y, Q.Z);
-            Q = add_table<CH, L>(Q, entry, neg);
-        }
+        for (int k = 0; k < 3; k++) dbl_asm(Q.X, Q.Y, Q.Z);
+        Fe2<1> T;
+        dblt_asm(Q.X, Q.Y, Q.Z, T);
+        add_asm(Q, T, t, neg);
     }
-    return ladder_result<CH>(Q);
+    return r1_unsign(Q);
 }
 
 // The ladders with constant-time selection (curve.hip.h, "constant-time selection"): `src` reads the whole table at
@@ -405,7 +372,7 @@ template <typename SRC> FQ_DEV R1 ladder_endo_scan(const EndoDigits& e, const SR
         dblt_asm(Q.X, Q.Y, Q.Z, T);
         add_asm(Q, T, scan_entry(src, endo_digit(e, i)), endo_neg_mask(e, i));
     }
-    return ladder_result<3>(Q);
+    return r1_unsign(Q);
 }
 template <typename SRC> FQ_DEV R1 ladder_windowed_scan(const WinScalar& w, const SRC& src) {
     u32 code = win_top_code(w);
@@ -419,7 +386,7 @@ template <typename SRC> FQ_DEV R1 ladder_windowed_scan(const WinScalar& w, const
         dblt_asm(Q.X, Q.Y, Q.Z, T);
         add_asm(Q, T, scan_entry(src, code & 7), (code >> 3) - 1u);
     }
-    return ladder_result<3>(Q);
+    return r1_unsign(Q);
 }
 
 // table_endo for the fused kernels that keep E, F in LDS (LdsEF): the same DAG and the same order as above, but nothing is
@@ -488,6 +455,13 @@ FQ_DEV void store_row(u64* row, const u64 o[20]) {
 #pragma unroll
     for (int k = 0; k < 10; k++) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
 }
+// the fused constant-time ladders' source: N, D of the lane's eight entries from its slot into registers, E, F where they are
+template <typename L, typename EF> FQ_DEV ScanSplit<EF> scan_split(const u32* slot, const EF& ef) {
+    ScanSplit<EF> regs;
+    regs.ef = ef;
+    regs.template load<L>(slot);
+    return regs;
+}
 
 namespace {   // kernels: one private copy per translation unit (their code objects differ by FQ_CHAIN)
 
@@ -540,16 +514,13 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC)) void ladder_kernel(Ladder
             if constexpr (ALGO == ENDO) build_table_endo_lds_asm<L>(P, slot, ef);
             else build_table_windowed<L>(P, slot, ef);
         }
-        R1 Q;                                                           // every ladder below runs the asm bodies (CH = 3, see "the ladders")
+        R1 Q;                                                           // every ladder below runs the asm bodies (see "the ladders")
         if constexpr (ALGO == ENDO) {
             u64 v[4];
             decompose(m, v);
             if constexpr (CT && SRC == FUSED) {
                 const EndoDigits e = recode(v);
-                ScanSplit<EF> regs;
-                regs.ef = ef;
-                regs.template load<L>(slot);
-                Q = ladder_endo_scan(e, regs);
+                Q = ladder_endo_scan(e, scan_split<L>(slot, ef));
             } else if constexpr (CT) {
                 Q = ladder_endo_scan(recode(v), ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
             } else if constexpr (SRC == FUSED) {
@@ -560,16 +531,13 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC)) void ladder_kernel(Ladder
         } else {
             const WinScalar w = win_reduce(m);
             if constexpr (CT && SRC == FUSED) {
-                ScanSplit<EF> regs;
-                regs.ef = ef;
-                regs.template load<L>(slot);
-                Q = ladder_windowed_scan(w, regs);
+                Q = ladder_windowed_scan(w, scan_split<L>(slot, ef));
             } else if constexpr (CT) {
                 Q = ladder_windowed_scan(w, ScanMem<8, u32>{ lds_table, LDS_ENTRY_U32 });
             } else if constexpr (SRC == LDS) {
-                Q = ladder_windowed<3>(w, lds_table, LDS_ENTRY_U32);
+                Q = ladder_windowed(w, lds_table, LDS_ENTRY_U32);
             } else {
-                Q = ladder_windowed<3, L, EF>(w, slot, L::ENTRY, ef);
+                Q = ladder_windowed<L, EF>(w, slot, L::ENTRY, ef);
             }
         }
         // One inversion per K elements, later (normalize_kernel).  FUSED: by a wave-uniform flag, no second instance -- DH batches of at least
@@ -768,10 +736,7 @@ __global__ __launch_bounds__(BLOCK, 1) void mixed_queue_kernel(LadderArgs a, con
             decompose(m, v);
             if constexpr (CT) {
                 const EndoDigits e = recode(v);
-                ScanSplit<LdsEF> regs;
-                regs.ef = ef;
-                regs.template load<NDSlots>(slot);
-                Q = ladder_endo_scan(e, regs);
+                Q = ladder_endo_scan(e, scan_split<NDSlots>(slot, ef));
             } else {                                                // the headline kernel's ladder (nibble stream, 32-bit entry offsets)
                 Q = ladder_endo_nibbles<NDSlots, LdsEF>(recode_nibbles(v), a.scratch, (blockIdx.x * BLOCK + threadIdx.x) * (u32)NDSlots::SLOT, ef);
             }
@@ -970,20 +935,16 @@ __global__ __launch_bounds__(BLOCK) void comb_quad_kernel(const u64* scalars, co
 #if FQ_CHAIN   // only fourq_chain.hip launches it
 // [m]B, affine, from the comb: 6 doublings + 27 mixed additions per element (constant-time mode: 9 + 49 on the small shape).
 // The block width is the launcher's choice (blockDim.x, a multiple of 64): the table is staged once per block.
-constexpr int COMB_MODE = LADDER_CH;                          // the comb's additions run on signed limbs like every ladder
+// The doublings and mixed additions are hipcc's, on signed limbs (dbl<Mul::Signed>, add_affine_table / add_affine_scan).
 template <bool DEFER, bool CT = false>
 __global__ __launch_bounds__(CT ? BLOCK : COMB_BLOCK_MAX, CT ? 4 : 1) void comb_kernel(const u64* scalars, const u32* comb_limbs, u64* out, uint8_t* status, uint4* proj, u32 proj_stride, u32 n) {
     using S = typename std::conditional<CT, CombScan, CombFast>::type;       // the constant-time mode scans the small sub-table
     extern __shared__ __attribute__((aligned(16))) u32 lds[];                // S::POINTS * COMB_LDS_U32 dwords, sized by the launcher
     const u32* sub = comb_limbs + (CT ? CombFast::POINTS * COMB_ENTRY_U32 : 0);
     const u32 width = blockDim.x;
-    if (COMB_LDS_U32 == COMB_ENTRY_U32) {
-        for (u32 i = threadIdx.x; i < (u32)(S::POINTS * COMB_ENTRY_U32 / 4); i += width)
-            reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(sub)[i];
-    } else {
-        for (u32 i = threadIdx.x; i < (u32)(S::POINTS * COMB_ENTRY_U32); i += width)
-            lds[(i / COMB_ENTRY_U32) * COMB_LDS_U32 + (i % COMB_ENTRY_U32)] = sub[i];
-    }
+    static_assert(COMB_LDS_U32 == COMB_ENTRY_U32, "a comb is staged as it lies");
+    for (u32 i = threadIdx.x; i < (u32)(S::POINTS * COMB_ENTRY_U32 / 4); i += width)
+        reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(sub)[i];
     __syncthreads();
     const u32 lanes = gridDim.x * width;
     const u32 n_round = (n + width - 1) / width * width;
@@ -1004,17 +965,17 @@ __global__ __launch_bounds__(CT ? BLOCK : COMB_BLOCK_MAX, CT ? 4 : 1) void comb_
                 if constexpr (CT) {                      // all entries of block j are read; the index only forms masks
                     const ScanMem<S::BLOCK_POINTS, u32> block{ lds + (j << (S::W - 1)) * COMB_LDS_U32, COMB_LDS_U32 };
                     if (i == S::E - 1 && j == 0) { Q = affine_scan_start(block, comb_index(c, col), neg); continue; }
-                    if (j == 0) Q = dbl<COMB_MODE>(Q.X, Q.Y, Q.Z);
-                    Q = add_affine_scan<COMB_MODE>(Q, block, comb_index(c, col), neg);
+                    if (j == 0) Q = dbl<Mul::Signed>(Q.X, Q.Y, Q.Z);
+                    Q = add_affine_scan(Q, block, comb_index(c, col), neg);
                 } else {
                     const u32* entry = lds + ((j << (S::W - 1)) + comb_index(c, col)) * COMB_LDS_U32;
                     if (i == S::E - 1 && j == 0) { Q = affine_table_start(entry, neg); continue; }
-                    if (j == 0) Q = dbl<COMB_MODE>(Q.X, Q.Y, Q.Z);
-                    Q = add_affine_table<COMB_MODE>(Q, entry, neg);
+                    if (j == 0) Q = dbl<Mul::Signed>(Q.X, Q.Y, Q.Z);
+                    Q = add_affine_table(Q, entry, neg);
                 }
             }
         }
-        Q = ladder_result<COMB_MODE>(Q);
+        Q = r1_unsign(Q);
         if (DEFER) {                                          // deferred normalisation, see normalize_kernel
             if (live) {
                 store_proj(proj, proj_stride, id, fe2_carry(fe2_cneg(Q.X, c.negate)), Q.Y, Q.Z);   // even scalar: -(x, y) = (-x, y)
@@ -1137,7 +1098,7 @@ int ct_launch_pair(int algo, bool dh, bool fixed, bool quad, unsigned grid, hipS
 int ct_launch_pair_mixed(bool quad, unsigned grid, hipStream_t stream, const LadderArgs& a);
 int ct_launch_comb_quad(bool quad, unsigned grid, hipStream_t stream, const u64* scalars, const u32* comb_limbs, u64* out, uint8_t* status, u32 n);
 int ct_launch_mixed_tail(unsigned prep_grid, unsigned tail_grid, hipStream_t stream, const LadderArgs& a, const u32* fix_list, const u32* var_list, u32* counts,
-                         u32* over_scratch, u32 lanes, u32 limit);     // split_counts_kernel must already have run: see fourq_ct_chain.hip
+                         u32* over_scratch);     // split_counts_kernel must already have run: see fourq_ct_chain.hip
 int ct_launch_split_counts(hipStream_t stream, u32* counts, u32 lanes, u32 limit);
 int ct_launch_mixed_queue(unsigned grid, hipStream_t stream, const LadderArgs& a, const u32* var_list, const u32* fix_list, const u32* counts, u32* queue_head);
 int ct_launch_lds(int algo, bool dh, unsigned grid, hipStream_t stream, const LadderArgs& a);        // defers when a.proj != NULL

@@ -83,13 +83,11 @@ FQ_DEV u32 keyset_next_digit(KeysetDigits& d) {            // the next column's 
 // entry's x + y and y - x against X and Y.  Left to itself the scheduler starts all three loads of the entry at once, and beside two
 // recodings that is more than a lane's 128 registers.
 template <typename P> FQ_DEV R1 keyset_add(const R1& q, const P* entry, u32 neg_mask) {
-    constexpr int CH = COMB_MODE;
-    static_assert(CH == 2, "the comb's additions run on signed limbs");
     Fe2<4> Ta = q.Ta;
     Fe2<2> Tb = q.Tb;
     fe2_here(Ta); fe2_here(Tb);                                // as add_affine_table: keeps the 90 products single instructions
-    const Fe2<1> T = fe2_mulx<CH>(Ta, Tb);
-    const Fe2<1> C = fe2_mulx<CH>(fe2_cnegx<CH>(load_fe2_limbs(entry + 2 * COORD_U32), neg_mask), T);
+    const Fe2<1> T = fe2_mul_signed(Ta, Tb);
+    const Fe2<1> C = fe2_mul_signed(fe2_cneg_signed(load_fe2_limbs(entry + 2 * COORD_U32), neg_mask), T);
     __builtin_amdgcn_sched_barrier(0);
     const Fe2<2> D = fe2_dbl(q.Z);
     const Fe2<3> G = fe2_add(D, C);
@@ -97,15 +95,15 @@ template <typename P> FQ_DEV R1 keyset_add(const R1& q, const P* entry, u32 neg_
     __builtin_amdgcn_sched_barrier(0);
     Fe2<1> tN, tD;
     load_signed_nd<LimbSlots>(entry, neg_mask, tN, tD);
-    const Fe2<1> B = fe2_mulx<CH>(fe2_add(q.X, q.Y), tN);
-    const Fe2<1> A = fe2_mulx<CH>(fe2_subx<CH>(q.Y, q.X), tD);
+    const Fe2<1> B = fe2_mul_signed(fe2_add(q.X, q.Y), tN);
+    const Fe2<1> A = fe2_mul_signed(fe2_sub_signed(q.Y, q.X), tD);
     __builtin_amdgcn_sched_barrier(0);
-    const Fe2<3> E = fe2_subx<CH>(B, A);
+    const Fe2<2> E = fe2_sub_signed(B, A);
     const Fe2<2> H = fe2_add(B, A);
     R1 r;
-    r.X = fe2_mulx<CH>(E, F);
-    r.Z = fe2_mulx<CH>(G, F);
-    r.Y = fe2_mulx<CH>(G, H);
+    r.X = fe2_mul_signed(E, F);
+    r.Z = fe2_mul_signed(G, F);
+    r.Y = fe2_mul_signed(G, H);
     r.Ta = widen<4>(E);
     r.Tb = H;
     return r;
@@ -141,7 +139,7 @@ __global__ __launch_bounds__(BLOCK, 4) void keyset_comb_kernel(const u64* k, con
                 if (i == S::E - 1 && j == 0) {
                     Q = affine_table_start(entry, 0u - (v >> 8));
                 } else {
-                    if (j == 0) Q = dbl<COMB_MODE>(Q.X, Q.Y, Q.Z);
+                    if (j == 0) Q = dbl<Mul::Signed>(Q.X, Q.Y, Q.Z);
                     Q = keyset_add(Q, entry, 0u - (v >> 8));
                 }
             }
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(BLOCK, 4) void keyset_comb_kernel(const u64* k, con
             }
         }
     }
-    Q = ladder_result<COMB_MODE>(Q);
+    Q = r1_unsign(Q);
     const u32 row = blockIdx.x * BLOCK + threadIdx.x;
     if (row >= n) return;
     u64 w[12];

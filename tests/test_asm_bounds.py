@@ -56,13 +56,12 @@ def test_restated_header_bounds_match_fp127_and_the_wrappers():
     """bounds.py restates fp127.hip.h's UNIT, LIMB_MASK, bias_limb and cols_ok, and the static_asserts of fe2_mul_asm / fe2_sqr_asm that
     select the admitted (A, B): a change to any of them must show up here"""
     fp = open(os.path.join(ROOT, "fourq_amd", "csrc", "fp127.hip.h")).read()
-    la = open(os.path.join(ROOT, "fourq_amd", "csrc", "ladder_asm.hip.h")).read()
     assert "constexpr u64 UNIT = (1ull << 26) + (1ull << 15);" in fp and bd.UNIT == (1 << 26) + (1 << 15)
     assert "constexpr u32 LIMB_BITS = 26;" in fp and "LIMB_MASK = (1u << LIMB_BITS) - 1;" in fp
     assert "return (u32)k * (i == 0 ? (LIMB_MASK - 7) : LIMB_MASK);" in fp
     assert "return weighted * 5 * 8 <= ((~0ull - (1ull << 41)) / (UNIT * UNIT));" in fp
-    mul = la[la.index("FQ_DEV Fe2<1> fe2_mul_asm"):la.index("FQ_DEV Fe2<1> fe2_sqr_asm")]
-    sqr = la[la.index("FQ_DEV Fe2<1> fe2_sqr_asm"):la.index("// ---- table_endo")]
+    mul = fp[fp.index("FQ_DEV Fe2<1> fe2_mul_asm"):fp.index("FQ_DEV Fe2<1> fe2_sqr_asm")]      # the wrappers live beside the products they replace
+    sqr = fp[fp.index("FQ_DEV Fe2<1> fe2_sqr_asm"):fp.index("// ---- the flavours of a GF(p^2) product")]
     assert re.findall(r"static_assert\((.*?), \"", mul) == ["cols_ok((u64)(2 * A + 1) * B)", "(u64)8 * B * UNIT < (1ull << 32)"]
     assert "fe_neg(a.im)" in mul
     assert re.findall(r"static_assert\((.*?), \"", sqr) == ["cols_ok((u64)(2 * A + 1) * (2 * A))", "(u64)8 * (2 * A) * UNIT < (1ull << 32)"]

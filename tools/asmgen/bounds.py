@@ -502,8 +502,8 @@ def within(ivs, contract):
 
 
 # ---- the chain: every edge where one body's output feeds another body or a C++ value of a given type ---------------------------------
-# (producer, output operand) -> (consumer, input operand), or a C++ consumer given by its limb intervals.  kernels.hip.h, ladder_endo and
-# its kin ("the ladders"): start_table -> DBLT / DBL, DBLT -> ADD, ADD -> DBLT / DBL, DBL -> DBL / DBLT, the result -> ladder_result<3> /
+# (producer, output operand) -> (consumer, input operand), or a C++ consumer given by its limb intervals.  kernels.hip.h, ladder_endo_nibbles_by and
+# its kin ("the ladders"): start_table -> DBLT / DBL, DBLT -> ADD, ADD -> DBLT / DBL, DBL -> DBL / DBLT, the result -> r1_unsign /
 # store_r1_signed (fe_unsign / fe_unsign_wide of Fe2<1>, Ta Fe2<4>, Tb Fe2<2>).  build_table_endo_lds_asm: R1TOR2 -> table,
 # TAU -> UPSILON / CHI (and parked in LDS as Fe2<1>), UPSILON / CHI -> TAUDUAL, TAUDUAL -> TAU (next step) and -> TABLEADD, TABLEADD ->
 # table -> TABLEADD / ADD / STEP.  Sources: fe_unpack of any input word, start_table's fe2_carry (bound-1 non-negative), table entries.
@@ -531,9 +531,9 @@ CHAINS = [
     (("entry", None), ("ADD", "N")), (("entry", None), ("ADD", "D")), (("entry", None), ("ADD", "E")), (("entry", None), ("ADD", "F")),
     (("entry", None), ("STEP", "N")), (("entry", None), ("STEP", "D")), (("entry", None), ("STEP", "E")), (("entry", None), ("STEP", "F")),
     (("fe_unpack", None), ("ADD", "N")), (("fe_unpack", None), ("ADD", "E")),                          # *_fixed: the caller's table words
-    (("ADD", "X"), _cpp("fe_unsign<1> (ladder_result / store_r1_signed)", signed(1))),
-    (("ADD", "Y"), _cpp("fe_unsign<1> (ladder_result / store_r1_signed)", signed(1))),
-    (("ADD", "Z"), _cpp("fe_unsign<1> (ladder_result / store_r1_signed)", signed(1))),
+    (("ADD", "X"), _cpp("fe_unsign<1> (r1_unsign / store_r1_signed)", signed(1))),
+    (("ADD", "Y"), _cpp("fe_unsign<1> (r1_unsign / store_r1_signed)", signed(1))),
+    (("ADD", "Z"), _cpp("fe_unsign<1> (r1_unsign / store_r1_signed)", signed(1))),
     (("ADD", "Ta"), _cpp("R1::Ta Fe2<4> -> fe_unsign<4>", signed(4))), (("ADD", "Tb"), _cpp("R1::Tb Fe2<2> -> fe_unsign<2>", signed(2))),
     (("STEP", "Ta"), _cpp("R1::Ta Fe2<4>", signed(4))), (("STEP", "Tb"), _cpp("R1::Tb Fe2<2>", signed(2))),
     # the table phase

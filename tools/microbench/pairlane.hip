@@ -1,6 +1,6 @@
 // Two lanes per element: the only lever against one-wave-per-SIMD at 2^16 elements that DESIGN.md had
 // costed but never measured.  One ladder step (DBL + ADD of a table entry, the DAG of curve4q.py:138-171) is run
-//   A  as shipped: one lane per element, dbl<2> of curve.hip.h + add_entry<2> (add_entry.hip.h here) (signed limbs, chained carries), ONE wave per SIMD;
+//   A  as shipped: one lane per element, dbl<Mul::Signed> of curve.hip.h + add_entry (add_entry.hip.h here) (signed limbs, chained carries), ONE wave per SIMD;
 //   B  pair-lane:  lane 2k holds the real parts, lane 2k+1 the imaginary parts of every GF(p^2) value of element k; a product
 //      r = u*v + w*z of 50 multiply-adds per lane gives the even lane its real and the odd lane its imaginary part, the partner's
 //      halves arrive by DPP quad_perm moves (no LDS, no waits), additions cost half; TWO waves per SIMD for the same elements.
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(256, 1) void single_kernel(uint64_t* out, uint32_t 
 #pragma unroll 1
     for (int it = 0; it < STEPS * REPS; ++it) {
         const u32 neg = 0u - ((elem >> (it & 15)) & 1);
-        Q = dbl<2>(Q.X, Q.Y, Q.Z);
-        Q = add_entry<2>(Q, t, neg);
+        Q = dbl<Mul::Signed>(Q.X, Q.Y, Q.Z);
+        Q = add_entry(Q, t, neg);
     }
     if (elem < 64) { u64 w[12]; store_fe2(w, fe2_unsign(Q.X)); store_fe2(w + 4, fe2_unsign(Q.Y)); store_fe2(w + 8, fe2_unsign(Q.Z)); for (int i = 0; i < 12; i++) out[elem * 12 + i] = w[i]; }
 }

@@ -18,8 +18,10 @@ using namespace fq;
 
 FQ_DEV uint64_t stamp() { uint64_t t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory"); return t; }
 
-// the product's MUL_endo ladder (ladder_endo<3, NDSlots, LdsEF> of kernels.hip.h) with the entry index of the HBM-side gather (N, D)
-// and of the LDS read (E, F) masked by run-time values: 7 = by digit as shipped, 0 = always entry 0 (same instructions, one address)
+// The MUL_endo ladder on the asm bodies with the entry index of the HBM-side gather (N, D) and of the LDS read (E, F) masked by run-time
+// values: 7 = by digit as shipped, 0 = always entry 0 (same instructions, one address).  The product's ladder has been
+// ladder_endo_nibbles (kernels.hip.h) since round 6; this probe keeps the digit-word form profiles/r04_phases.txt was taken with, for
+// every variant.
 FQ_DEV R1 ladder_probe(const EndoDigits& e, const u32* tbl, const LdsEF& ef, u32 gmask, u32 lmask) {
     Proj<1, 1, 1> q4 = start_table<NDSlots>(tbl + (e.top & 7) * NDSlots::ENTRY, 0u);
     q4.Z = ef.get(e.top & 7, 0);
@@ -28,12 +30,12 @@ FQ_DEV R1 ladder_probe(const EndoDigits& e, const u32* tbl, const LdsEF& ef, u32
     for (int i = 63; i >= 0; i--) {
         const u32 digit = endo_digit(e, i);
         const u32 neg = endo_neg_mask(e, i);
-        EntryRegs t = load_entry<NDSlots>(tbl + (digit & gmask) * NDSlots::ENTRY, neg, digit & lmask, ef);
+        EntryRegs t = load_entry<NDSlots>(tbl + (digit & gmask) * NDSlots::ENTRY, digit & lmask, ef);
         Fe2<1> T;
         dblt_asm(Q.X, Q.Y, Q.Z, T);
         add_asm(Q, T, t, neg);
     }
-    return ladder_result<3>(Q);
+    return r1_unsign(Q);
 }
 template <int VARIANT> __global__ __launch_bounds__(256, 1) void k(const u64* scalars, const u64* points, u64* out, u32* scratch, uint64_t* stamps, u32 gmask, u32 lmask) {
     __shared__ __attribute__((aligned(16))) u32 lds_mem[EF_LDS_U32];
@@ -54,8 +56,7 @@ template <int VARIANT> __global__ __launch_bounds__(256, 1) void k(const u64* sc
     EndoDigits e = recode(v);
     if (VARIANT == 1) { e.d[0] = e.d[1] = e.d[2] = 0; e.top = 0; }
     uint64_t t3 = stamp();
-    R1 Q = (VARIANT >= 3) ? ladder_probe(e, (const u32*)slot, ef, gmask, lmask)
-                          : ladder_endo<3, NDSlots>(e, (const u32*)slot, NDSlots::ENTRY, ef);      // the asm bodies, as the product kernel's ladder since round 4
+    R1 Q = (VARIANT >= 3) ? ladder_probe(e, (const u32*)slot, ef, gmask, lmask) : ladder_probe(e, (const u32*)slot, ef, 7, 7);
     uint64_t t4 = stamp();
     u64 o[20];
     store_r1(o, Q);
