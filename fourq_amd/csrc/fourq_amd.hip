@@ -1213,6 +1213,62 @@ template <class Launch> int host_call(fourq_ctx* c, size_t n, const HostCall& d,
     return host_call(c, n, d, [] { return FOURQ_OK; }, launch);
 }
 
+// ---- one grouped call, described once: one output row per GROUP of group_size elements (the grouped sums, the commitments, the proofs) ----
+// The grouped argument contract (include/fourq_amd.h), spelt here only and in the order every grouped call and *_reserve observes: the
+// call's own predicates first (`args_ok`: the context, NULL pointers, aligned16 for _dev, the window, the route, h2c_args_ok, ...), a failed
+// one is FOURQ_ERR_INVALID whatever the counts are; then groups == 0 is FOURQ_OK with *n == 0 and nothing touched; then group_size == 0 or
+// groups x group_size overflowing or above FOURQ_MAX_BATCH is FOURQ_ERR_INVALID.  Otherwise FOURQ_OK with *n = groups x group_size > 0.
+// Callers write `if (rc || !n) return rc;`.
+int grouped_rows(bool args_ok, size_t groups, size_t group_size, size_t* n) {
+    *n = 0;
+    if (!args_ok) return FOURQ_ERR_INVALID;
+    if (groups == 0) return FOURQ_OK;
+    size_t rows;
+    if (group_size == 0 || __builtin_mul_overflow(groups, group_size, &rows) || rows > FOURQ_MAX_BATCH) return FOURQ_ERR_INVALID;
+    *n = rows;
+    return FOURQ_OK;
+}
+// Host arrays of a grouped call: copy in through the staging buffer, the _dev call, copy out, synchronise, in one piece.  No chunk overlap:
+// run_pipeline's arrays are per element, and these outputs are per group.  c->host_stats describes the last PIPELINE call and is not written.
+// One array of a call: copied in where `in` is set (n rows with `per_row`, `groups` rows otherwise), copied out (`groups` rows) where `out`
+// is; an array the call does not have (the status of the affine flavours) is not listed.  `call` gets the device arrays in listed order.
+struct GroupedArray { const void* in; void* out; size_t row_bytes; bool per_row; };
+constexpr size_t GROUPED_MAX_ARRAYS = 8;
+int grouped_host(fourq_ctx* c, size_t n, size_t groups, const GroupedArray* arrays, size_t count, const std::function<int(char* const*)>& call) {
+    if (count > GROUPED_MAX_ARRAYS) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    size_t total = 0;
+    for (size_t k = 0; k < count; k++) total += (arrays[k].per_row ? n : groups) * arrays[k].row_bytes;
+    if (int rc = ensure_stage(c, total)) return rc;
+    // c->stage is carved here, after ensure_stage, and must stay where it is until the copies out: no _dev call that `call` makes may call
+    // ensure_stage (none does: they size the work buffer and the projective planes only; DLEQ's stage_comb runs BEFORE this function).
+    char* dev[GROUPED_MAX_ARRAYS] = {};
+    auto staged = [&]() -> int {
+        size_t used = 0;
+        for (size_t k = 0; k < count; k++) {                      // the caller lists the 32- and 64-byte rows first: every one of them starts 16-byte aligned
+            const size_t bytes = (arrays[k].per_row ? n : groups) * arrays[k].row_bytes;
+            dev[k] = (char*)c->stage + used;
+            if (arrays[k].in) HIP_TRY(c, hipMemcpyAsync(dev[k], arrays[k].in, bytes, hipMemcpyHostToDevice, c->stream));
+            used += bytes;
+        }
+        if (int rc = call(dev)) return rc;
+        for (size_t k = 0; k < count; k++)
+            if (arrays[k].out) HIP_TRY(c, hipMemcpyAsync(arrays[k].out, dev[k], groups * arrays[k].row_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return FOURQ_OK;
+    };
+    const int rc = staged();
+    if (rc != FOURQ_OK) (void)hipStreamSynchronize(c->stream);    // as run_pipeline: nothing of this call may still read or write the caller's arrays
+    return rc;
+}
+// The value of the last row of an ascending threshold table that `x` has reached; the first row is { 0, the value below every threshold }
+struct Threshold { size_t from; int value; };
+template <size_t K> int threshold_value(const Threshold (&table)[K], size_t x) {
+    int value = table[0].value;
+    for (const Threshold& row : table) if (x >= row.from) value = row.value;
+    return value;
+}
+
 int mul_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points, const uint64_t* table, uint64_t* out, size_t n) {
     const int v = algo == ENDO ? 0 : 1;
     const HostCall variable = { { { scalars, 32 }, { points, 160 } }, { { out, 160 } }, { PR_MUL_VAR, v, v ? KT_WIN_VAR : KT_ENDO_VAR }, pipe_chunk, pipe_chunk };
@@ -1892,78 +1948,65 @@ FQ_API int fourq_verify_bytes_batch(fourq_ctx* c, const uint64_t* k, const uint6
 // each turning m rows per group into ceil(m / MSM_FOLD), alternating between the layout's two regions until one row per group is left;
 // (3) lower_kernel over the `groups` rows, which also turns a group's largest decode code into its status.  The geometry of every launch
 // follows from (groups, group_size) on the host: nothing is staged and, once the work buffer is large enough, nothing allocated.
-static bool msm_count(size_t groups, size_t group_size, size_t* n) {
-    return !__builtin_mul_overflow(groups, group_size, n) && *n <= FOURQ_MAX_BATCH;
+// The fold passes: the first writes part_a, the next part_b, and so on, until one row per group is left; *rows, *stride and *st then name
+// it (they are unchanged where group_size == 1).  st_a / st_b: the status planes that ride along where *st is not NULL.
+struct FoldParts { uint64_t *a, *b; uint8_t *st_a, *st_b; };
+static int fold_to_one_row(fourq_ctx* c, const FoldParts& parts, size_t groups, size_t group_size, const uint64_t** rows, u32* stride, const uint8_t** st) {
+    bool to_a = true;
+    for (size_t m = group_size; m > 1; to_a = !to_a) {
+        uint64_t* part = to_a ? parts.a : parts.b;
+        uint8_t* part_st = to_a ? parts.st_a : parts.st_b;
+        HIPRC_TRY(c, chain_launch_msm_fold(c->stream, *rows, *stride, *st, part, part_st, groups, m));
+        m = (m + MSM_FOLD - 1) / MSM_FOLD;
+        *rows = part; *stride = 12;
+        if (*st) *st = part_st;
+    }
+    return FOURQ_OK;
 }
 static int msm_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
-    if (!c || !scalars || !points || !out || (encoded && !status)) return FOURQ_ERR_INVALID;
-    if (!aligned16(scalars) || !aligned16(points) || !aligned16(out)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
-    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    int rc = grouped_rows(c && scalars && points && out && (!encoded || status) && aligned16(scalars) && aligned16(points) && aligned16(out), groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    int rc = reserve_for<fq_work::Msm>(c, n);
-    if (rc) return rc;
+    if ((rc = reserve_for<fq_work::Msm>(c, n))) return rc;
     const fq_work::Msm w(c->work, n);
     u32 stride;
     if ((rc = mul_rows_dev(c, ENDO, scalars, points, encoded, w.rows_in, w.rows_out, encoded ? w.st_decode : nullptr, n, &stride))) return rc;
     const uint64_t* rows = w.rows_out;
     const uint8_t* st = encoded ? w.st_decode : nullptr;
-    bool to_a = true;
-    for (size_t m = group_size; m > 1; to_a = !to_a) {
-        uint64_t* part = to_a ? w.part_a : w.part_b;
-        uint8_t* part_st = to_a ? w.st_a : w.st_b;
-        HIPRC_TRY(c, chain_launch_msm_fold(c->stream, rows, stride, st, part, part_st, groups, m));
-        m = (m + MSM_FOLD - 1) / MSM_FOLD;
-        rows = part; stride = 12;
-        if (encoded) st = part_st;
-    }
+    if ((rc = fold_to_one_row(c, { w.part_a, w.part_b, w.st_a, w.st_b }, groups, group_size, &rows, &stride, &st))) return rc;
     return launch_lower(c, encoded, rows, stride, st, (uint64_t*)out, status, groups);
 }
-// Host arrays: copy in, the _dev call, copy out, synchronously through the staging buffer.  No chunk overlap: run_pipeline's arrays are per
-// element, and this output is per group.
-static int msm_host(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size) {
+// Host arrays of the grouped sums on either route (grouped_host).  sum_dev: the _dev call to make -- it gets msm_dev's five arguments behind the
+// context, over the staged arrays; args_ok: what that call asks beyond the arrays (the bucket route's window).
+using SumDev = std::function<int(const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status)>;
+static int sum_host(fourq_ctx* c, bool args_ok, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size,
+                    const SumDev& sum_dev) {
     size_t n;
-    if (!c || !scalars || !points || !out || (encoded && !status)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
-    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
-    CtxGuard g(c);
+    const int rc = grouped_rows(c && scalars && points && out && (!encoded || status) && args_ok, groups, group_size, &n);
+    if (rc || !n) return rc;
     const size_t point_bytes = encoded ? 32 : 64;
-    int rc = ensure_stage(c, n * (32 + point_bytes) + groups * (point_bytes + 1));
-    if (rc) return rc;
-    char* d_scalars = (char*)c->stage;
-    char* d_points = d_scalars + n * 32;
-    char* d_out = d_points + n * point_bytes;
-    char* d_status = d_out + groups * point_bytes;
-    HIP_TRY(c, hipMemcpyAsync(d_scalars, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_points, points, n * point_bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = msm_dev(c, (const uint64_t*)d_scalars, d_points, encoded, d_out, encoded ? (uint8_t*)d_status : nullptr, groups, group_size))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, d_out, groups * point_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (encoded) HIP_TRY(c, hipMemcpyAsync(status, d_status, groups, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FOURQ_OK;
+    const GroupedArray arrays[] = { { scalars, nullptr, 32, true }, { points, nullptr, point_bytes, true }, { nullptr, out, point_bytes, false }, { nullptr, status, 1, false } };
+    return grouped_host(c, n, groups, arrays, encoded ? 4 : 3, [&](char* const* d) {
+        return sum_dev((const uint64_t*)d[0], (const void*)d[1], encoded, (void*)d[2], encoded ? (uint8_t*)d[3] : nullptr);
+    });
 }
 FQ_API int fourq_msm_affine_batch_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size) { return msm_dev(c, s, p, false, o, nullptr, groups, group_size); }
 FQ_API int fourq_msm_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return msm_dev(c, s, p, true, o, st, groups, group_size); }
-FQ_API int fourq_msm_affine_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size) { return msm_host(c, s, p, false, o, nullptr, groups, group_size); }
-FQ_API int fourq_msm_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return msm_host(c, s, p, true, o, st, groups, group_size); }
+FQ_API int fourq_msm_affine_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size) { return sum_host(c, true, s, p, false, o, nullptr, groups, group_size, [&](auto... staged) { return msm_dev(c, staged..., groups, group_size); }); }
+FQ_API int fourq_msm_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return sum_host(c, true, s, p, true, o, st, groups, group_size, [&](auto... staged) { return msm_dev(c, staged..., groups, group_size); }); }
 
 // ---- the same sums by the bucket method (bucket.hip.h, bucket_layout.h): same arrays, same bytes, another route -------------------------
 // window 0: the window measured fastest for the group size, or the ladder route where no window beat it by more than msm_dev's own run-to-run
 // spread (profiles/bucket_sum_timing.txt: the ladder route up to one group of 2^18, 1.10 of it there; window 11 at 2^19, 0.72, and at 2^20,
 // 0.52).  The threshold is the smallest MEASURED group size at which a window won; the table is indexed by group_size alone.
-static const struct { size_t from; int window; } BUCKET_WINDOWS[] = { { 0, 0 }, { (size_t)1 << 19, 11 } };      // { smallest group_size, window }, ascending
-FQ_API int fourq_bucketsum_window(size_t group_size) {
-    int window = 0;
-    for (const auto& row : BUCKET_WINDOWS) if (group_size >= row.from) window = row.window;
-    return window;
-}
+static const Threshold BUCKET_WINDOWS[] = { { 0, 0 }, { (size_t)1 << 19, 11 } };      // { smallest group_size, window }, ascending
+FQ_API int fourq_bucketsum_window(size_t group_size) { return threshold_value(BUCKET_WINDOWS, group_size); }
 static bool bucket_window_ok(unsigned window) { return window == 0 || fq_work::BucketGeom::window_ok(window); }
 FQ_API int fourq_bucketsum_reserve(fourq_ctx* c, size_t groups, size_t group_size, unsigned window) {
     size_t n;
-    if (!c || !bucket_window_ok(window)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
-    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    const int rc = grouped_rows(c && bucket_window_ok(window), groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
     if (!window) window = (unsigned)fourq_bucketsum_window(group_size);
     if (!window) return reserve_for<fq_work::Msm>(c, n);
@@ -1972,15 +2015,13 @@ FQ_API int fourq_bucketsum_reserve(fourq_ctx* c, size_t groups, size_t group_siz
 // In constant-time selection mode the ladder route runs whatever the window is: a bucket's address is a digit of a scalar.
 static int bucket_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size, unsigned window) {
     size_t n;
-    if (!c || !scalars || !points || !out || (encoded && !status) || !bucket_window_ok(window)) return FOURQ_ERR_INVALID;
-    if (!aligned16(scalars) || !aligned16(points) || !aligned16(out)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
-    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    int rc = grouped_rows(c && scalars && points && out && (!encoded || status) && bucket_window_ok(window) && aligned16(scalars) && aligned16(points) && aligned16(out),
+                          groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
     if (!window) window = (unsigned)fourq_bucketsum_window(group_size);
     if (c->ct || !window) return msm_dev(c, scalars, points, encoded, out, status, groups, group_size);
-    int rc = ensure_work(c, fq_work::Bucket::bytes(groups, group_size, window));
-    if (rc) return rc;
+    if ((rc = ensure_work(c, fq_work::Bucket::bytes(groups, group_size, window)))) return rc;
     const fq_work::Bucket w(c->work, groups, group_size, window);
     if (encoded) {
         hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)points, w.affine, w.st_decode, (u32)n);
@@ -1989,32 +2030,14 @@ static int bucket_dev(fourq_ctx* c, const uint64_t* scalars, const void* points,
     HIPRC_TRY(c, chain_launch_bucket_sum(c->stream, w, scalars, encoded ? w.affine : (const u64*)points, encoded ? w.st_decode : nullptr));
     return launch_lower(c, encoded, w.sum, 12, w.st_sum, (uint64_t*)out, status, groups);
 }
-// Host arrays, as msm_host: copy in, the _dev call, copy out, in one piece.
-static int bucket_host(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size, unsigned window) {
-    size_t n;
-    if (!c || !scalars || !points || !out || (encoded && !status) || !bucket_window_ok(window)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
-    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
-    CtxGuard g(c);
-    const size_t point_bytes = encoded ? 32 : 64;
-    int rc = ensure_stage(c, n * (32 + point_bytes) + groups * (point_bytes + 1));
-    if (rc) return rc;
-    char* d_scalars = (char*)c->stage;
-    char* d_points = d_scalars + n * 32;
-    char* d_out = d_points + n * point_bytes;
-    char* d_status = d_out + groups * point_bytes;
-    HIP_TRY(c, hipMemcpyAsync(d_scalars, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_points, points, n * point_bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = bucket_dev(c, (const uint64_t*)d_scalars, d_points, encoded, d_out, encoded ? (uint8_t*)d_status : nullptr, groups, group_size, window))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, d_out, groups * point_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (encoded) HIP_TRY(c, hipMemcpyAsync(status, d_status, groups, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FOURQ_OK;
-}
 FQ_API int fourq_bucketsum_affine_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size, unsigned window) { return bucket_dev(c, s, p, false, o, nullptr, groups, group_size, window); }
 FQ_API int fourq_bucketsum_bytes_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) { return bucket_dev(c, s, p, true, o, st, groups, group_size, window); }
-FQ_API int fourq_bucketsum_affine(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size, unsigned window) { return bucket_host(c, s, p, false, o, nullptr, groups, group_size, window); }
-FQ_API int fourq_bucketsum_bytes(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) { return bucket_host(c, s, p, true, o, st, groups, group_size, window); }
+FQ_API int fourq_bucketsum_affine(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size, unsigned window) {
+    return sum_host(c, bucket_window_ok(window), s, p, false, o, nullptr, groups, group_size, [&](auto... staged) { return bucket_dev(c, staged..., groups, group_size, window); });
+}
+FQ_API int fourq_bucketsum_bytes(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) {
+    return sum_host(c, bucket_window_ok(window), s, p, true, o, st, groups, group_size, [&](auto... staged) { return bucket_dev(c, staged..., groups, group_size, window); });
+}
 
 // ---- commitments over a fixed generator set (commit.hip.h, commit_layout.h): out[g] = sum_j [k_gj]B_j, one comb per generator ------------
 static_assert(fq_work::Commit::FOLD == MSM_FOLD, "commit_layout.h sizes the fold regions for msm_fold_kernel's segment");
@@ -2068,70 +2091,49 @@ FQ_API int fourq_commit_bases_count(const fourq_ctx* c, size_t* m) {
 // own timings (profiles/commit_timing.txt: 1024 x 64, 0.1460 against 0.1494 ms, 2.3 % with a spread of 2.0 %; at 32768 x 2 and 65536 x 1 the two
 // are within the spread, at 64 x 1024 and 1 x 4096 the gather route is 2.8 and 44 times faster), the gather route below; the table is indexed
 // by `groups` alone, as BUCKET_WINDOWS is by group_size.
-static const struct { size_t from; int route; } COMMIT_ROUTES[] = { { 0, 2 }, { 1024, 1 } };      // { smallest groups, route }, ascending
-FQ_API int fourq_commit_route(size_t groups) {
-    int route = 2;
-    for (const auto& row : COMMIT_ROUTES) if (groups >= row.from) route = row.route;
-    return route;
-}
+static const Threshold COMMIT_ROUTES[] = { { 0, 2 }, { 1024, 1 } };      // { smallest groups, route }, ascending
+FQ_API int fourq_commit_route(size_t groups) { return threshold_value(COMMIT_ROUTES, groups); }
 FQ_API int fourq_commit_reserve(fourq_ctx* c, size_t groups, size_t group_size) {
     size_t n;
-    if (!c) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
-    if (group_size == 0 || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
+    const int rc = grouped_rows(c != nullptr, groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
     return ensure_work(c, fq_work::Commit::bytes(groups, group_size));
 }
 // The combs into w.rows, the fold passes of the grouped sums until one row per group is left, the lowering: affine words, or the encoding.
 static int commit_dev(fourq_ctx* c, const uint64_t* scalars, void* out, bool encoded, size_t groups, size_t group_size, int route) {
     size_t n;
-    if (!c) return FOURQ_ERR_INVALID;
-    if (!scalars || !out || route < 0 || route > 2) return FOURQ_ERR_INVALID;
-    if (!aligned16(scalars) || !aligned16(out)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    int rc = grouped_rows(c && scalars && out && route >= 0 && route <= 2 && aligned16(scalars) && aligned16(out), groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    if (group_size == 0 || group_size > c->commit_count || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;     // no set: count 0
+    if (group_size > c->commit_count) return FOURQ_ERR_INVALID;     // no set: count 0
     if (!route) route = fourq_commit_route(groups);
-    int rc = ensure_work(c, fq_work::Commit::bytes(groups, group_size));
-    if (rc) return rc;
+    if ((rc = ensure_work(c, fq_work::Commit::bytes(groups, group_size)))) return rc;
     const fq_work::Commit w(c->work, groups, group_size);
     if (c->ct) HIPRC_TRY(c, ct_launch_commit((unsigned)(c->lanes_w4 / BLOCK), c->stream, scalars, c->commit_combs, w.rows, groups, group_size));
     else HIPRC_TRY(c, chain_launch_commit(route, (unsigned)c->cus, c->stream, scalars, c->commit_combs, w.rows, groups, group_size));
     const uint64_t* rows = w.rows;
-    bool to_a = true;
-    for (size_t m = group_size; m > 1; to_a = !to_a) {
-        uint64_t* part = to_a ? w.part_a : w.part_b;
-        HIPRC_TRY(c, chain_launch_msm_fold(c->stream, rows, 12, nullptr, part, nullptr, groups, m));
-        m = (m + MSM_FOLD - 1) / MSM_FOLD;
-        rows = part;
-    }
-    if (!encoded) return launch_lower(c, false, rows, 12, nullptr, (uint64_t*)out, nullptr, groups);
+    const uint8_t* st = nullptr;
+    u32 stride = 12;
+    if ((rc = fold_to_one_row(c, { w.part_a, w.part_b, nullptr, nullptr }, groups, group_size, &rows, &stride, &st))) return rc;
+    if (!encoded) return launch_lower(c, false, rows, stride, nullptr, (uint64_t*)out, nullptr, groups);
     HIP_TRY(c, hipMemsetAsync(w.st_zero, 0, groups, c->stream));
-    return launch_lower(c, true, rows, 12, w.st_zero, (uint64_t*)out, w.st_out, groups);
+    return launch_lower(c, true, rows, stride, w.st_zero, (uint64_t*)out, w.st_out, groups);
 }
-// Host arrays, as msm_host: copy in, the _dev call, copy out, in one piece.
-static int commit_host(fourq_ctx* c, const uint64_t* scalars, void* out, bool encoded, size_t groups, size_t group_size, int route) {
+// Host arrays (grouped_host).  The set's size is read under the lock, as in commit_dev.
+static int commit_arrays(fourq_ctx* c, const uint64_t* scalars, void* out, bool encoded, size_t groups, size_t group_size, int route) {
     size_t n;
-    if (!c) return FOURQ_ERR_INVALID;
-    if (!scalars || !out || route < 0 || route > 2) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    const int rc = grouped_rows(c && scalars && out && route >= 0 && route <= 2, groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    if (group_size == 0 || group_size > c->commit_count || !msm_count(groups, group_size, &n)) return FOURQ_ERR_INVALID;
-    const size_t point_bytes = encoded ? 32 : 64;
-    int rc = ensure_stage(c, n * 32 + groups * point_bytes);
-    if (rc) return rc;
-    char* d_scalars = (char*)c->stage;
-    char* d_out = d_scalars + n * 32;
-    HIP_TRY(c, hipMemcpyAsync(d_scalars, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-    if ((rc = commit_dev(c, (const uint64_t*)d_scalars, d_out, encoded, groups, group_size, route))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, d_out, groups * point_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FOURQ_OK;
+    if (group_size > c->commit_count) return FOURQ_ERR_INVALID;
+    const GroupedArray arrays[] = { { scalars, nullptr, 32, true }, { nullptr, out, encoded ? (size_t)32 : 64, false } };
+    return grouped_host(c, n, groups, arrays, 2, [&](char* const* d) { return commit_dev(c, (const uint64_t*)d[0], d[1], encoded, groups, group_size, route); });
 }
 FQ_API int fourq_commit_affine_dev(fourq_ctx* c, const uint64_t* s, uint64_t* o, size_t groups, size_t group_size, int route) { return commit_dev(c, s, o, false, groups, group_size, route); }
 FQ_API int fourq_commit_bytes_dev(fourq_ctx* c, const uint64_t* s, uint8_t* o, size_t groups, size_t group_size, int route) { return commit_dev(c, s, o, true, groups, group_size, route); }
-FQ_API int fourq_commit_affine(fourq_ctx* c, const uint64_t* s, uint64_t* o, size_t groups, size_t group_size, int route) { return commit_host(c, s, o, false, groups, group_size, route); }
-FQ_API int fourq_commit_bytes(fourq_ctx* c, const uint64_t* s, uint8_t* o, size_t groups, size_t group_size, int route) { return commit_host(c, s, o, true, groups, group_size, route); }
+FQ_API int fourq_commit_affine(fourq_ctx* c, const uint64_t* s, uint64_t* o, size_t groups, size_t group_size, int route) { return commit_arrays(c, s, o, false, groups, group_size, route); }
+FQ_API int fourq_commit_bytes(fourq_ctx* c, const uint64_t* s, uint8_t* o, size_t groups, size_t group_size, int route) { return commit_arrays(c, s, o, true, groups, group_size, route); }
 
 // ---- signatures from bytes (include/fourq_amd.h): SHA-512 and the arithmetic modulo N on the device (sig.hip.h) around the comb, the
 // ladder and the combiner.  Every intermediate -- H(sk), the nonce, the challenge, s / h / R as rows -- lives in the context's work buffer.
@@ -2557,21 +2559,17 @@ FQ_API int fourq_oprf_eval_batch(fourq_ctx* c, const uint64_t* key, const uint8_
 // hash, reduce, split and compare in between.  The inner calls carve their own layouts at the start of the work buffer; this call's regions
 // lie behind the largest of them (dleq_layout.h), and the buffer and the projective planes are sized ONCE, here, for everything the inner
 // calls will ask, so that none of them moves the buffer under a value an earlier stage has left.
-static bool dleq_args_ok(const fourq_ctx* c, const uint8_t* dst, size_t dst_len, size_t groups, size_t group_size, bool pair, size_t* n) {
-    *n = 0;
-    if (!c || !h2c_args_ok(dst, dst_len, FOURQ_H2C_RO)) return false;
-    if (groups == 0) return true;
-    if (group_size == 0 || !msm_count(groups, group_size, n)) return false;
-    return !pair || 2 * groups <= FOURQ_MAX_BATCH;                // verify's sum of two is a grouped sum over 2 x groups rows
-}
+// what every call asks of its context and DST; verify and reserve ask dleq_pair_ok too: verify's sum of two is a grouped sum over 2 x groups rows
+static bool dleq_args_ok(const fourq_ctx* c, const uint8_t* dst, size_t dst_len) { return c && h2c_args_ok(dst, dst_len, FOURQ_H2C_RO); }
+static bool dleq_pair_ok(size_t groups) { return groups <= FOURQ_MAX_BATCH / 2; }
 static int dleq_size(fourq_ctx* c, size_t n, size_t groups) {
     if (int rc = ensure_proj(c, fq_work::Dleq::plane_rows(groups))) return rc;
     return ensure_work(c, fq_work::Dleq::bytes(n, groups));
 }
 FQ_API int fourq_dleq_reserve(fourq_ctx* c, size_t groups, size_t group_size) {
     size_t n;
-    if (!c || (groups && (group_size == 0 || !msm_count(groups, group_size, &n) || 2 * groups > FOURQ_MAX_BATCH))) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    const int rc = grouped_rows(c && dleq_pair_ok(groups), groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
     return dleq_size(c, n, groups);
 }
@@ -2586,12 +2584,11 @@ static int dleq_composites_stage(fourq_ctx* c, const fq_work::Dleq& w, const Opr
 FQ_API int fourq_dleq_composites_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* pk32, const uint8_t* blinded32, const uint8_t* evaluated32,
                                      uint8_t* m32, uint8_t* z32, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
-    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !pk32 || !blinded32 || !evaluated32 || !m32 || !z32 || !status) return FOURQ_ERR_INVALID;
-    if (!aligned16(blinded32) || !aligned16(evaluated32) || !aligned16(m32) || !aligned16(z32)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    int rc = grouped_rows(dleq_args_ok(c, dst, dst_len) && pk32 && blinded32 && evaluated32 && m32 && z32 && status && aligned16(blinded32) && aligned16(evaluated32) &&
+                          aligned16(m32) && aligned16(z32), groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    int rc = dleq_size(c, n, groups);
-    if (rc) return rc;
+    if ((rc = dleq_size(c, n, groups))) return rc;
     const fq_work::Dleq w(c->work, n, groups);
     HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w.pk, 1));
     if ((rc = dleq_composites_stage(c, w, dleq_make_tail("Composite", dst, dst_len), (const uint8_t*)w.pk, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
@@ -2601,12 +2598,11 @@ FQ_API int fourq_dleq_composites_dev(fourq_ctx* c, const uint8_t* dst, size_t ds
 FQ_API int fourq_dleq_prove_dev(fourq_ctx* c, const uint64_t* key, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
                                 const uint64_t* nonces, uint8_t* proof64, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
-    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !key || !blinded32 || !evaluated32 || !nonces || !proof64 || !status) return FOURQ_ERR_INVALID;
-    if (!aligned16(blinded32) || !aligned16(evaluated32) || !aligned16(nonces) || !aligned16(proof64)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    int rc = grouped_rows(dleq_args_ok(c, dst, dst_len) && key && blinded32 && evaluated32 && nonces && proof64 && status && aligned16(blinded32) && aligned16(evaluated32) &&
+                          aligned16(nonces) && aligned16(proof64), groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    int rc = stage_comb(c, comb);
-    if (rc) return rc;
+    if ((rc = stage_comb(c, comb))) return rc;
     if ((rc = dleq_size(c, n, groups))) return rc;
     const fq_work::Dleq w(c->work, n, groups);
     uint8_t *m32 = (uint8_t*)w.m32, *z32 = (uint8_t*)w.z32, *t2 = (uint8_t*)w.t2, *t3 = (uint8_t*)w.t3;
@@ -2625,12 +2621,11 @@ FQ_API int fourq_dleq_prove_dev(fourq_ctx* c, const uint64_t* key, const uint64_
 FQ_API int fourq_dleq_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
                                  const uint8_t* proof64, uint8_t* ok, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
-    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, true, &n) || !pk32 || !blinded32 || !evaluated32 || !proof64 || !ok || !status) return FOURQ_ERR_INVALID;
-    if (!aligned16(blinded32) || !aligned16(evaluated32) || !aligned16(proof64)) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    int rc = grouped_rows(dleq_args_ok(c, dst, dst_len) && dleq_pair_ok(groups) && pk32 && blinded32 && evaluated32 && proof64 && ok && status && aligned16(blinded32) &&
+                          aligned16(evaluated32) && aligned16(proof64), groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    int rc = stage_comb(c, comb);
-    if (rc) return rc;
+    if ((rc = stage_comb(c, comb))) return rc;
     if ((rc = dleq_size(c, n, groups))) return rc;
     const fq_work::Dleq w(c->work, n, groups);
     uint8_t *m32 = (uint8_t*)w.m32, *z32 = (uint8_t*)w.z32, *t2 = (uint8_t*)w.t2, *t3 = (uint8_t*)w.t3;
@@ -2644,63 +2639,38 @@ FQ_API int fourq_dleq_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint64
                                    (u32)groups));
     return FOURQ_OK;
 }
-// Host arrays, as msm_host: copy in through the staging buffer, the _dev call, copy out, synchronise.  No chunks: the outputs are per group.
-// One array of a call: copied in where `in` is set (n rows with `per_row`, `groups` rows otherwise), copied out (`groups` rows) where `out` is.
-struct DleqHostArray { const void* in; void* out; size_t row_bytes; bool per_row; };
-static int dleq_host(fourq_ctx* c, size_t n, size_t groups, std::initializer_list<DleqHostArray> arrays, const std::function<int(char**)>& call) {
-    CtxGuard g(c);
-    size_t total = 0;
-    for (const DleqHostArray& a : arrays) total += (a.per_row ? n : groups) * a.row_bytes;
-    int rc = ensure_stage(c, total);
-    if (rc) return rc;
-    char* dev[8];
-    size_t k = 0, used = 0;
-    for (const DleqHostArray& a : arrays) {                       // the caller lists the 32- and 64-byte rows first: every one of them starts 16-byte aligned
-        dev[k] = (char*)c->stage + used;
-        const size_t bytes = (a.per_row ? n : groups) * a.row_bytes;
-        if (a.in) HIP_TRY(c, hipMemcpyAsync(dev[k], a.in, bytes, hipMemcpyHostToDevice, c->stream));
-        used += bytes; k++;
-    }
-    if ((rc = call(dev))) return rc;
-    k = 0;
-    for (const DleqHostArray& a : arrays) {
-        if (a.out) HIP_TRY(c, hipMemcpyAsync(a.out, dev[k], groups * a.row_bytes, hipMemcpyDeviceToHost, c->stream));
-        k++;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FOURQ_OK;
-}
+// Host arrays (grouped_host), the 32- and 64-byte rows listed first.  prove and verify stage the comb BEFORE the arrays and pass comb == NULL on.
 FQ_API int fourq_dleq_composites(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* pk32, const uint8_t* blinded32, const uint8_t* evaluated32, uint8_t* m32,
                                  uint8_t* z32, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
-    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !pk32 || !blinded32 || !evaluated32 || !m32 || !z32 || !status) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
-    return dleq_host(c, n, groups, { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { nullptr, m32, 32, false }, { nullptr, z32, 32, false }, { nullptr, status, 1, false } },
-                     [&](char** d) {
+    const int rc = grouped_rows(dleq_args_ok(c, dst, dst_len) && pk32 && blinded32 && evaluated32 && m32 && z32 && status, groups, group_size, &n);
+    if (rc || !n) return rc;
+    const GroupedArray arrays[] = { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { nullptr, m32, 32, false }, { nullptr, z32, 32, false }, { nullptr, status, 1, false } };
+    return grouped_host(c, n, groups, arrays, 5, [&](char* const* d) {
         return fourq_dleq_composites_dev(c, dst, dst_len, pk32, (uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, group_size);
     });
 }
 FQ_API int fourq_dleq_prove(fourq_ctx* c, const uint64_t* key, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
                             const uint64_t* nonces, uint8_t* proof64, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
-    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, false, &n) || !key || !blinded32 || !evaluated32 || !nonces || !proof64 || !status) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    int rc = grouped_rows(dleq_args_ok(c, dst, dst_len) && key && blinded32 && evaluated32 && nonces && proof64 && status, groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;
-    return dleq_host(c, n, groups, { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { nonces, nullptr, 32, false }, { nullptr, proof64, 64, false }, { nullptr, status, 1, false } },
-                     [&](char** d) {
+    if ((rc = stage_comb(c, comb))) return rc;
+    const GroupedArray arrays[] = { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { nonces, nullptr, 32, false }, { nullptr, proof64, 64, false }, { nullptr, status, 1, false } };
+    return grouped_host(c, n, groups, arrays, 5, [&](char* const* d) {
         return fourq_dleq_prove_dev(c, key, nullptr, dst, dst_len, (uint8_t*)d[0], (uint8_t*)d[1], (uint64_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, group_size);
     });
 }
 FQ_API int fourq_dleq_verify(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
                              const uint8_t* proof64, uint8_t* ok, uint8_t* status, size_t groups, size_t group_size) {
     size_t n;
-    if (!dleq_args_ok(c, dst, dst_len, groups, group_size, true, &n) || !pk32 || !blinded32 || !evaluated32 || !proof64 || !ok || !status) return FOURQ_ERR_INVALID;
-    if (groups == 0) return FOURQ_OK;
+    int rc = grouped_rows(dleq_args_ok(c, dst, dst_len) && dleq_pair_ok(groups) && pk32 && blinded32 && evaluated32 && proof64 && ok && status, groups, group_size, &n);
+    if (rc || !n) return rc;
     CtxGuard g(c);
-    if (int rc = stage_comb(c, comb)) return rc;
-    return dleq_host(c, n, groups, { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { proof64, nullptr, 64, false }, { nullptr, ok, 1, false }, { nullptr, status, 1, false } },
-                     [&](char** d) {
+    if ((rc = stage_comb(c, comb))) return rc;
+    const GroupedArray arrays[] = { { blinded32, nullptr, 32, true }, { evaluated32, nullptr, 32, true }, { proof64, nullptr, 64, false }, { nullptr, ok, 1, false }, { nullptr, status, 1, false } };
+    return grouped_host(c, n, groups, arrays, 5, [&](char* const* d) {
         return fourq_dleq_verify_dev(c, pk32, nullptr, dst, dst_len, (uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, group_size);
     });
 }
