@@ -118,6 +118,13 @@ PROTOTYPES = {
     "fourq_msm_affine_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_msm_bytes_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_msm_bytes_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_raggedsum_shape_set": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "fourq_raggedsum_shape_count": (c_int, [c_void_p, POINTER(c_size_t), POINTER(c_size_t)]),
+    "fourq_raggedsum_shape_reserve": (c_int, [c_void_p]),
+    "fourq_raggedsum_affine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fourq_raggedsum_affine_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fourq_raggedsum_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fourq_raggedsum_bytes_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fourq_bucketsum_window": (c_int, [c_size_t]),
     "fourq_bucketsum_reserve": (c_int, [c_void_p, c_size_t, c_size_t, c_uint]),
     "fourq_bucketsum_affine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_uint]),

@@ -43,6 +43,7 @@
 #include "oprf.hip.h"
 #include "dleq_layout.h"
 #include "keyset_layout.h"
+#include "msm_shape.h"
 #include "dleq.hip.h"
 
 using namespace fq;
@@ -479,6 +480,8 @@ struct fourq_ctx {
     uint8_t* keyset_bytes = nullptr;   // ... the keys as registered, keyset_count x 32 bytes, and behind them one status byte per slot
     uint8_t* keyset_status = nullptr;
     size_t keyset_count = 0;
+    fq_work::ShapePlan shape;      // fourq_raggedsum_shape_set: the installed shape's passes (groups == 0: none was ever set) ...
+    uint2* shape_desc = nullptr;   // ... and every pass's descriptors on the device, back to back as in shape.desc (NULL where no pass is needed)
     uint64_t table_shadow[FOURQ_TABLE_WORDS];   // host copies of what table_limbs / comb_limbs currently hold
     uint64_t comb_shadow[FOURQ_COMB_WORDS];
     bool table_staged = false, comb_staged = false;
@@ -1419,7 +1422,7 @@ FQ_API int fourq_ctx_destroy(fourq_ctx* c) {
     DeviceGuard g(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     for (void* p : { (void*)c->scratch, (void*)c->proj, (void*)c->table_limbs, (void*)c->table_packed, (void*)c->part_counter, (void*)c->part_list,
-                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, (void*)c->commit_combs, (void*)c->keyset_combs, (void*)c->keyset_bytes, c->stage, (void*)c->work, (void*)c->pipe_dev })
+                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, (void*)c->commit_combs, (void*)c->keyset_combs, (void*)c->keyset_bytes, (void*)c->shape_desc, c->stage, (void*)c->work, (void*)c->pipe_dev })
         if (p) (void)hipFree(p);
     if (c->pipe_pin) (void)hipHostFree(c->pipe_pin);
     if (c->zero_copy) (void)hipHostFree(c->zero_copy);
@@ -1995,6 +1998,95 @@ FQ_API int fourq_msm_affine_batch_dev(fourq_ctx* c, const uint64_t* s, const uin
 FQ_API int fourq_msm_bytes_batch_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return msm_dev(c, s, p, true, o, st, groups, group_size); }
 FQ_API int fourq_msm_affine_batch(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size) { return sum_host(c, true, s, p, false, o, nullptr, groups, group_size, [&](auto... staged) { return msm_dev(c, staged..., groups, group_size); }); }
 FQ_API int fourq_msm_bytes_batch(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size) { return sum_host(c, true, s, p, true, o, st, groups, group_size, [&](auto... staged) { return msm_dev(c, staged..., groups, group_size); }); }
+
+// ---- ragged grouped sums (msm_shape.h): the same sums over groups of any length, 0 included, by a registered shape -----------------------
+// The offsets are public metadata: the host validates them and turns them into the geometry of every fold pass (fq_work::ShapePlan), and the
+// context holds that -- the passes here, their descriptors on the device -- the way it holds the commitment bases and the key set.  No
+// kernel reads an offset.  Route: mul_rows_dev over the shape's n rows (skipped where n == 0), the planned passes, launch_lower over `groups`.
+static_assert(fq_work::ShapePlan::FOLD == MSM_FOLD, "msm_shape.h plans the passes for msm_fold_desc_kernel's segment");
+static_assert(sizeof(fq_work::ShapeDesc) == sizeof(uint2), "a descriptor is the 8 bytes a team's lanes load");
+// Everything goes into a NEW plan and a NEW array, and the old shape is replaced once they are complete: a failure keeps it.
+FQ_API int fourq_raggedsum_shape_set(fourq_ctx* c, const uint32_t* offsets, size_t groups) {
+    if (!c || !offsets) return FOURQ_ERR_INVALID;
+    fq_work::ShapePlan plan;
+    const auto built = plan.build(offsets, groups, FOURQ_MAX_BATCH);
+    if (built != fq_work::ShapePlan::OK) return built == fq_work::ShapePlan::NOMEM ? FOURQ_ERR_NOMEM : FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    if (int rc = staging_allowed(c)) return rc;
+    uint2* desc = nullptr;
+    if (!plan.desc.empty()) {
+        const size_t bytes = plan.desc.size() * sizeof(fq_work::ShapeDesc);
+        hipError_t e = hipMalloc(&desc, bytes);
+        if (e != hipSuccess) return fail(c, e, "hipMalloc(the descriptors of the shape)");
+        e = hipMemcpyAsync(desc, plan.desc.data(), bytes, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); (void)hipFree(desc); return fail(c, e, "uploading the descriptors of the shape"); }
+    } else {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->shape_desc) (void)hipFree(c->shape_desc);          // the stream is idle: nothing reads the old descriptors any more
+    std::vector<fq_work::ShapeDesc>().swap(plan.desc);        // the device has them; the context keeps the passes only
+    c->shape = std::move(plan);
+    c->shape_desc = desc;
+    return FOURQ_OK;
+}
+FQ_API int fourq_raggedsum_shape_count(const fourq_ctx* c, size_t* groups, size_t* rows) {
+    if (!c || !groups || !rows) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    *groups = c->shape.groups;
+    *rows = c->shape.rows;
+    return FOURQ_OK;
+}
+FQ_API int fourq_raggedsum_shape_reserve(fourq_ctx* c) {
+    if (!c) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    if (c->shape.groups == 0) return FOURQ_ERR_INVALID;
+    return ensure_work(c, fq_work::MsmRagged::bytes(c->shape.rows, c->shape.groups));
+}
+// fold_to_one_row over the planned passes: the first writes part_a, the next part_b, and so on; *rows, *stride and *st then name the one row
+// per group (they are unchanged where the plan has no pass: every group has exactly one row).
+static int fold_planned(fourq_ctx* c, const FoldParts& parts, const uint64_t** rows, u32* stride, const uint8_t** st) {
+    bool to_a = true;
+    for (const fq_work::ShapePass& pass : c->shape.passes) {
+        uint64_t* part = to_a ? parts.a : parts.b;
+        uint8_t* part_st = to_a ? parts.st_a : parts.st_b;
+        HIPRC_TRY(c, chain_launch_msm_fold_desc(c->stream, *rows, *stride, *st, part, part_st, c->shape_desc + pass.desc_at, pass.rows_out, pass.team, pass.iters));
+        *rows = part; *stride = 12;
+        if (*st) *st = part_st;
+        to_a = !to_a;
+    }
+    return FOURQ_OK;
+}
+static int ragged_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status) {
+    if (!c || !scalars || !points || !out || (encoded && !status) || !aligned16(scalars) || !aligned16(points) || !aligned16(out)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    const size_t groups = c->shape.groups, n = c->shape.rows;
+    if (groups == 0) return FOURQ_ERR_INVALID;                // no shape
+    int rc = ensure_work(c, fq_work::MsmRagged::bytes(n, groups));
+    if (rc) return rc;
+    const fq_work::MsmRagged w(c->work, n, groups);
+    u32 stride = 12;
+    if (n && (rc = mul_rows_dev(c, ENDO, scalars, points, encoded, w.rows_in, w.rows_out, encoded ? w.st_decode : nullptr, n, &stride))) return rc;
+    const uint64_t* rows = w.rows_out;
+    const uint8_t* st = encoded ? w.st_decode : nullptr;
+    if ((rc = fold_planned(c, { w.part_a, w.part_b, w.st_a, w.st_b }, &rows, &stride, &st))) return rc;
+    return launch_lower(c, encoded, rows, stride, st, (uint64_t*)out, status, groups);
+}
+// Host arrays (grouped_host): n rows in, `groups` rows out.  The shape is read under the lock, which grouped_host takes again around the copies.
+static int ragged_host(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status) {
+    if (!c || !scalars || !points || !out || (encoded && !status)) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    if (c->shape.groups == 0) return FOURQ_ERR_INVALID;
+    const size_t point_bytes = encoded ? 32 : 64;
+    const GroupedArray arrays[] = { { scalars, nullptr, 32, true }, { points, nullptr, point_bytes, true }, { nullptr, out, point_bytes, false }, { nullptr, status, 1, false } };
+    return grouped_host(c, c->shape.rows, c->shape.groups, arrays, encoded ? 4 : 3, [&](char* const* d) {
+        return ragged_dev(c, (const uint64_t*)d[0], (const void*)d[1], encoded, (void*)d[2], encoded ? (uint8_t*)d[3] : nullptr);
+    });
+}
+FQ_API int fourq_raggedsum_affine_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o) { return ragged_dev(c, s, p, false, o, nullptr); }
+FQ_API int fourq_raggedsum_bytes_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st) { return ragged_dev(c, s, p, true, o, st); }
+FQ_API int fourq_raggedsum_affine(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o) { return ragged_host(c, s, p, false, o, nullptr); }
+FQ_API int fourq_raggedsum_bytes(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st) { return ragged_host(c, s, p, true, o, st); }
 
 // ---- the same sums by the bucket method (bucket.hip.h, bucket_layout.h): same arrays, same bytes, another route -------------------------
 // window 0: the window measured fastest for the group size, or the ladder route where no window beat it by more than msm_dev's own run-to-run

@@ -1,7 +1,7 @@
 // Second translation unit of libfourq_amd.so: the kernels that profit from chained carries (FQ_CHAIN=1, see
 // kernels.hip.h): fixed-base ladders (table in LDS), the fixed-base comb and the batched normalisation.  Only launchers are exported to the other
 // translation unit; the C ABI lives in fourq_amd.hip.  combine.hip.h adds the kernel that joins the comb's and the ladder's halves of [k]B + [l]P,
-// msm.hip.h the one that folds the ladder's rows of a group into one, bucket.hip.h the bucket route of the same sums, commit.hip.h the combs of a
+// msm.hip.h the ones that fold the ladder's rows of a group into one (equal lengths, and by descriptors), bucket.hip.h the bucket route of the same sums, commit.hip.h the combs of a
 // fixed generator set, keyset.hip.h the two combs in one accumulator of a signature check over registered keys.
 #ifndef FQ_CHAIN
 #define FQ_CHAIN 1
@@ -81,6 +81,15 @@ int chain_launch_msm_fold(hipStream_t stream, const u64* rows, u32 stride, const
     if (blocks == 0 || blocks > 0x7fffffffu || m_in > 0xffffffffu) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(msm_fold_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, stream, rows, stride, st_in, rows_out, st_out, (u32)m_in, (u32)m_out, team,
                        (u32)((segment + team - 1) / team), teams);
+    return (int)hipGetLastError();
+}
+// One planned pass of a ragged sum: the geometry is the plan's (fq_work::ShapePass), checked once more where it becomes a launch
+int chain_launch_msm_fold_desc(hipStream_t stream, const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out, const uint2* desc, size_t teams,
+                               u32 team, u32 iters) {
+    const u64 blocks = ((u64)teams * team + BLOCK - 1) / BLOCK;
+    if (!desc || blocks == 0 || blocks > 0x7fffffffu || teams > 0xffffffffu || team == 0 || team > 16 || (team & (team - 1)) || iters == 0 || (u64)team * iters > MSM_FOLD)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(msm_fold_desc_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, stream, rows, stride, st_in, rows_out, st_out, desc, team, iters, (u32)teams);
     return (int)hipGetLastError();
 }
 // The combs of a commitment (commit.hip.h): row g * group_size + j from comb j, canonical (X, Y, Z) rows.  route: COMMIT_STAGED or COMMIT_GATHER

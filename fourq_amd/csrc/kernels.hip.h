@@ -1077,6 +1077,10 @@ int chain_launch_combine(int k, int out_kind, hipStream_t stream, const uint4* p
 // st_in (NULL: none) / st_out: one raw decode code per row, folded as a maximum
 constexpr u32 MSM_FOLD = 64;
 int chain_launch_msm_fold(hipStream_t stream, const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out, size_t groups, size_t m_in);
+// ... and one planned pass of a RAGGED sum (msm_shape.h): output row t sums the rows desc[t] = { first, count } names; `teams` output rows, teams
+// of `team` lanes (a power of two, at most 16) that each sum `iters` rows before the butterfly
+int chain_launch_msm_fold_desc(hipStream_t stream, const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out, const uint2* desc, size_t teams,
+                               u32 team, u32 iters);
 // bucket.hip.h: the grouped sums by the bucket method, from the sub-scalars to one projective row (and decode code) per group in w.sum / w.st_sum
 int chain_launch_bucket_sum(hipStream_t stream, const fq_work::Bucket& w, const u64* scalars, const u64* points_affine, const uint8_t* st_decode);
 // commit.hip.h: the combs of a commitment, row g * group_size + j from comb j of `combs` as a canonical 12-word (X, Y, Z) row; route 1 = staged, 2 = gather

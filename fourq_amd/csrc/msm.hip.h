@@ -71,6 +71,57 @@ __global__ __launch_bounds__(BLOCK, 2) void msm_fold_kernel(const u64* rows, u32
     if (st_in) st_out[team] = (uint8_t)st;
 }
 
+// The same pass over groups of ANY length (the ragged grouped sums; msm_shape.h): team t owns output row t and reads desc[t] = { first, count },
+// the rows first .. first + count - 1 of the level below, 0 <= count <= MSM_FOLD.  The host built the descriptors from validated offsets
+// (fq_work::ShapePlan::build) so that those of a pass partition the level below exactly: every first + r with r < count lies inside it, and
+// this kernel derives no address from anything else.  A wave holds 64 / T teams, so the descriptor is not wave-uniform: every lane of a
+// team loads the same 8 bytes (one dwordx2 per lane, the wave's 64 / T descriptors in one or two cache lines).
+//
+// The invariants of msm_fold_kernel hold.  No lane leaves before the last cross-lane step.  Lanes past a short segment, teams past the last
+// descriptor and EVERY lane of a team whose count is 0 carry the neutral (0, 1, 1), read a row that exists (row 0; the layout keeps one
+// even where the call has no element at all); a live team stores what its descriptor says -- for count 0 the neutral, with code 0 -- and
+// a team past the last descriptor stores nothing.  No branch and no address depends on a scalar or a coordinate.
+// teams: the pass's output rows; iters = max(1, ceil(largest count of the pass / T))
+__global__ __launch_bounds__(BLOCK, 2) void msm_fold_desc_kernel(const u64* rows, u32 stride, const uint8_t* st_in, u64* rows_out, uint8_t* st_out,
+                                                                 const uint2* desc, u32 T, u32 iters, u32 teams) {
+    const u64 lane = (u64)blockIdx.x * BLOCK + threadIdx.x;
+    const u64 team = lane / T;
+    const u32 j = (u32)(lane % T);
+    const bool live = team < teams;
+    const uint2 d = desc[live ? team : 0];
+    const u32 first = d.x, count = live ? d.y : 0;
+    Fe2<1> zero;
+#pragma unroll
+    for (int i = 0; i < 5; i++) zero.re.l[i] = zero.im.l[i] = 0;
+    const Fe2<1> one = fe2_one();
+    XYZ acc;
+    u32 st = 0;
+    for (u32 k = 0; k < iters; k++) {
+        const u32 r = j + k * T;
+        const bool have = r < count;
+        const u64 at = have ? (u64)first + r : 0;
+        const u32 keep = have ? ~0u : 0u;
+        const u64* row = rows + stride * at;
+        const Fe2<1> X = fe2_select(keep, load_fe2(row), zero), Y = fe2_select(keep, load_fe2(row + 4), one), Z = fe2_select(keep, load_fe2(row + 8), one);
+        if (st_in) { const u32 s = st_in[at]; st = (have && s > st) ? s : st; }
+        if (k == 0) { acc.X = X; acc.Y = Y; acc.Z = Z; }
+        else acc = add_projective(acc.X, acc.Y, acc.Z, X, Y, Z);
+    }
+    for (u32 step = T >> 1; step; step >>= 1) {                    // every lane of the wave takes every step
+        const Fe2<1> X = shfl_xor_fe2(acc.X, (int)step), Y = shfl_xor_fe2(acc.Y, (int)step), Z = shfl_xor_fe2(acc.Z, (int)step);
+        const u32 s = (u32)__shfl_xor((int)st, (int)step);
+        st = s > st ? s : st;
+        acc = add_projective(acc.X, acc.Y, acc.Z, X, Y, Z);
+    }
+    if (!live || j != 0) return;
+    u64 w[12];
+    store_fe2(w, acc.X); store_fe2(w + 4, acc.Y); store_fe2(w + 8, acc.Z);
+    uint4* dst = reinterpret_cast<uint4*>(rows_out + 12 * team);
+#pragma clang loop unroll(full)
+    for (int k = 0; k < 6; k++) dst[k] = make_uint4((u32)w[2 * k], (u32)(w[2 * k] >> 32), (u32)w[2 * k + 1], (u32)(w[2 * k + 1] >> 32));
+    if (st_in) st_out[team] = (uint8_t)st;
+}
+
 }  // namespace
 
 }  // namespace fq

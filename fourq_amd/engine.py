@@ -386,7 +386,7 @@ class Engine:
 
     def msm(self, scalars, points_affine, group_size, out=None):
         """Canonical affine sums, (n // group_size, 8) words: out[g] = sum of [k_i]P_i over the group_size elements of group g, laid out
-        group after group.  Checks nothing, like MUL_*; the neutral point (0, 1) is an ordinary result.  Ragged groups: pad with scalar 0."""
+        group after group.  Checks nothing, like MUL_*; the neutral point (0, 1) is an ordinary result.  Ragged groups: msm_ragged, or pad with scalar 0."""
         k, p = _host(scalars, 4), _host(points_affine, 8)
         if len(k) != len(p):
             raise ValueError("the scalar and point arrays differ in length")
@@ -411,6 +411,73 @@ class Engine:
 
     def msm_bytes_dev(self, scalars, points32, out32, status, groups, group_size):
         self._ck(self._lib.fourq_msm_bytes_batch_dev(self._ctx, _ptr(scalars), _ptr(points32), _ptr(out32), _ptr(status), groups, group_size))
+
+    # ---- ragged grouped sums (fourq_raggedsum_*): the same sums over groups of any length, 0 included, by a shape the context holds -----
+    # offsets: groups + 1 ascending row offsets from 0; group g owns rows offsets[g] .. offsets[g + 1] - 1.
+    @staticmethod
+    def _offsets(offsets):
+        a = np.asarray(offsets)
+        if a.ndim != 1 or len(a) < 2 or a.dtype.kind not in "iu" or (a < 0).any() or (a > 0xffffffff).any():
+            raise ValueError("offsets must be groups + 1 >= 2 row offsets that fit 32 bits")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def msm_shape(self, offsets):
+        """Install the shape (fourq_raggedsum_shape_set): validated and planned on the host, its descriptors uploaded.  Replaces the old
+        shape once the new one is complete; an invalid one (offsets[0] != 0, a descending pair, too many rows) raises and the old one stays."""
+        a = self._offsets(offsets)
+        self._ck(self._lib.fourq_raggedsum_shape_set(self._ctx, _ptr(a), len(a) - 1))
+        self._shape = a.copy()
+
+    def msm_shape_count(self):
+        """(groups, rows) of the installed shape, (0, 0) when none was ever set."""
+        groups, rows = ctypes.c_size_t(), ctypes.c_size_t()
+        self._ck(self._lib.fourq_raggedsum_shape_count(self._ctx, ctypes.byref(groups), ctypes.byref(rows)))
+        return int(groups.value), int(rows.value)
+
+    def msm_shape_reserve(self):
+        """Size the work buffer for the installed shape (fourq_raggedsum_shape_reserve; reserve() is not enough): the `_dev` calls then
+        only enqueue."""
+        self._ck(self._lib.fourq_raggedsum_shape_reserve(self._ctx))
+
+    def _ragged(self, offsets, n):
+        """(groups, rows) of the shape a call runs on: `offsets` installed first unless it equals the one this Engine installed last"""
+        if offsets is not None:
+            a = self._offsets(offsets)
+            last = getattr(self, "_shape", None)
+            if last is None or not np.array_equal(last, a):
+                self.msm_shape(a)
+        groups, rows = self.msm_shape_count()
+        if groups and n != rows:
+            raise ValueError("%d elements, but the shape has %d rows" % (n, rows))
+        return groups
+
+    def msm_ragged(self, scalars, points_affine, offsets=None, out=None):
+        """Canonical affine sums, (groups, 8) words: out[g] = sum of [k_i]P_i over the rows of group g; an empty group gives the neutral
+        (0, 1).  offsets=None runs on the installed shape.  Byte for byte msm() on each group alone."""
+        k, p = _host(scalars, 4), _host(points_affine, 8)
+        if len(k) != len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        groups = self._ragged(offsets, len(k))
+        out = _out(out, groups, 8)
+        self._ck(self._lib.fourq_raggedsum_affine(self._ctx, _ptr(k), _ptr(p), _ptr(out)))
+        return out
+
+    def msm_ragged_bytes(self, scalars, points32, offsets=None, out=None, status=None):
+        """encode(sum of [k_i]decode(points32[i])) per group: ((groups, 32) bytes, status); status[g] = 0 or BYTES_DECODE_BASE + the largest
+        DECODE_* among the group's rows (out[g] is zero then).  An empty group gives 01 00 .. 00 with status 0."""
+        k, p = _host(scalars, 4), _host(points32, 32, np.uint8)
+        if len(k) != len(p):
+            raise ValueError("the scalar and point arrays differ in length")
+        groups = self._ragged(offsets, len(k))
+        out, status = _out(out, groups, 32, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_raggedsum_bytes(self._ctx, _ptr(k), _ptr(p), _ptr(out), _ptr(status)))
+        return out, status
+
+    def msm_ragged_dev(self, scalars, points_affine, out_affine):
+        self._ck(self._lib.fourq_raggedsum_affine_dev(self._ctx, _ptr(scalars), _ptr(points_affine), _ptr(out_affine)))
+
+    def msm_ragged_bytes_dev(self, scalars, points32, out32, status):
+        self._ck(self._lib.fourq_raggedsum_bytes_dev(self._ctx, _ptr(scalars), _ptr(points32), _ptr(out32), _ptr(status)))
 
     # ---- the same sums by the bucket method (fourq_bucketsum_*): same arrays, same bytes, for large groups ----------------------------
     # window: 0 = the library picks (bucket_sum_window; the ladder route where no window beat it), 4..12 = the bucket route with that window.

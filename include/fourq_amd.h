@@ -337,7 +337,8 @@ int fourq_verify_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *k_scalars, cons
 
 /* ---- grouped multi-scalar multiplication: out[g] = sum_j [k_gj]P_gj, the only call that adds across elements ----------------------------
  * groups x group_size = n elements laid out group after group (element i belongs to group i / group_size); every group has the same
- * length.  A caller with ragged groups pads with scalar 0: the addition is complete, so the neutral [0]P is an ordinary operand.  The pad
+ * length.  A caller with ragged groups pads with scalar 0 (or calls fourq_raggedsum_* below, which takes the groups as they are and pays
+ * for no pad): the addition is complete, so the neutral [0]P is an ordinary operand.  The pad
  * point is the neutral (0, 1) or any other point on the affine flavour, and any string that DECODES on the bytes flavour (a valid key;
  * the neutral's own encoding 01 00 .. 00 is refused by decode, FOURQ_DECODE_REF_ATTRIBUTE_ERROR, and would mark its group).
  *
@@ -363,6 +364,51 @@ int fourq_msm_bytes_batch(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t
                           size_t group_size);
 int fourq_msm_bytes_batch_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status,
                               size_t groups, size_t group_size);
+
+/* ---- ragged grouped sums: out[g] = sum over group g of [k_i]P_i, groups of ANY length, by a shape the context holds ---------------------
+ * The sums of fourq_msm_* over groups whose lengths differ, 0 included, without padding: a padded row is a whole MUL_endo ladder, the pad
+ * of the bytes flavour has to be a string that decodes, and an empty group cannot be padded into existence at all.  (The names say
+ * raggedsum, not msm_ragged, for the reason the bucket route's say bucketsum: fourq_msm_* is, by name, the equal-length family of four.)
+ *
+ * The shape: groups + 1 ascending uint32 row offsets on the HOST with offsets[0] == 0; group g owns rows offsets[g] .. offsets[g + 1] - 1
+ * of the n = offsets[groups] rows, and a length of 0 is legal anywhere -- first, last, several in a row, all of them.  The offsets are
+ * public metadata.  fourq_raggedsum_shape_set validates them, plans every fold pass on the host -- level p holds max(1, ceil(L / 64)) rows
+ * for a group of L rows in level p - 1, passes repeat until every group has one row, and each output row of a pass gets one descriptor
+ * { first input row, count <= 64 } -- and uploads the descriptors (8 bytes per output row, beside 96-byte rows).  No kernel reads an offset or
+ * derives an address from anything but a descriptor, so the geometry of every launch is known on the host, as for fourq_msm_*.
+ * Synchronous; replaces the old shape only once the new one is complete.  FOURQ_ERR_INVALID, and the old shape stays: a NULL context
+ * (refused before anything else is looked at) or NULL offsets; groups == 0; groups or n above FOURQ_MAX_BATCH; offsets[0] != 0; a descending
+ * pair; a level of 2^32 rows or more (billions of groups shorter than two rows).  The shape is the context's own, like the key set: the
+ * commitment bases, the key set, the staged comb and the staged tables are untouched, it survives fourq_ctx_set_stream and is freed with the
+ * context.  fourq_raggedsum_shape_count: the installed shape's groups and rows, 0 and 0 when none was ever set.
+ *
+ * The calls take n and groups from the installed shape; with no shape they are FOURQ_ERR_INVALID.
+ * out_affine[g] = R1toAffine(sum over the rows i of group g of MUL_endo(k_i, AffineToR1(P_i)))  canonical, groups x 8 words; scalars: any
+ * value in [0, 2^256); checks nothing, like fourq_msm_affine_batch.  out32[g]: the encoding of that point; status[g]: 0 |
+ * FOURQ_BYTES_DECODE_BASE + the LARGEST FOURQ_DECODE_* among the group's rows (out32[g] is all zero then; the other groups are not affected).
+ * An EMPTY group yields the neutral as an ordinary result: (0, 1), or 01 00 .. 00 with status 0.  For every group the row is, byte for
+ * byte, what fourq_msm_* returns on that group alone with group_size = its length, and on a shape of equal lengths the result is what
+ * fourq_msm_* returns on the whole arrays.  A shape of nothing but empty groups is legal and launches no ladder.
+ *
+ * _dev: enqueues on the context's stream and returns; every array pointer 16-byte aligned (status need not be).  The work buffer of these
+ * calls holds up to groups + n / 64 partial rows after the first pass -- more than fourq_msm_* keeps where groups are short or empty -- so
+ * fourq_ctx_reserve does not cover it; fourq_raggedsum_shape_reserve(ctx) sizes it for the installed shape, and after it a _dev call
+ * allocates and synchronises nothing and can be captured into a graph.  The host-array calls copy in, run and copy out in one piece,
+ * as fourq_msm_* do.
+ *
+ * Cost, measured against fourq_msm_affine_batch_dev (profiles/msm_ragged_timing.txt, time as a fraction of msm_dev's, and msm_dev's own
+ * run-to-run spread).  Against the same groups padded to the longest with scalar 0: 1 024 groups of 1 .. 127 rows (67 207 rows against
+ * 130 048 padded) 0.80, spread 8.5 % -- both sides need two generations of 65 536 lanes, so the ladder saves less than the row count says;
+ * 1 023 groups of 8 rows and one of 8 192: 0.25 ms against 36.6 ms, 0.007; 65 536 groups of 0 .. 2 rows: 0.54, spread 0.5 %.  Against
+ * fourq_msm_* itself at equal lengths, which is what the descriptors cost: 1024 x 64 1.000, 256 x 256 1.001, 1 x 65536 0.998, each inside
+ * msm_dev's spread (0.4, 0.1, 0.6 %).  fourq_raggedsum_shape_set takes 0.02 ms on the host for 1 024 groups and 0.19 ms for 65 536. */
+int fourq_raggedsum_shape_set(fourq_ctx *ctx, const uint32_t *offsets, size_t groups);
+int fourq_raggedsum_shape_count(const fourq_ctx *ctx, size_t *groups, size_t *rows);
+int fourq_raggedsum_shape_reserve(fourq_ctx *ctx);
+int fourq_raggedsum_affine(fourq_ctx *ctx, const uint64_t *scalars, const uint64_t *points_affine, uint64_t *out_affine);
+int fourq_raggedsum_affine_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint64_t *points_affine, uint64_t *out_affine);
+int fourq_raggedsum_bytes(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status);
+int fourq_raggedsum_bytes_dev(fourq_ctx *ctx, const uint64_t *scalars, const uint8_t *points32, uint8_t *out32, uint8_t *status);
 
 /* ---- sums across elements: the bucket route ---------------------------------------------------------------------------------------------
  * The same arrays and, byte for byte, the same outputs and status as fourq_msm_affine_batch / fourq_msm_bytes_batch above -- the neutral
