@@ -30,6 +30,7 @@ H2C_RO, H2C_NU, H2C_MAX_DST = 0, 1, 255                       # FOURQ_H2C_*
 OPRF_BLIND_ZERO = 48                                          # FOURQ_OPRF_BLIND_ZERO
 DLEQ_NONCE_ZERO = 80                                          # FOURQ_DLEQ_NONCE_ZERO
 KEYSET_MAX_KEYS, KEYSET_NOT_ORDER_N, KEYSET_ID_RANGE = 4096, 96, 112   # FOURQ_KEYSET_*
+VRF_GAMMA_NEUTRAL = 128                                       # FOURQ_VRF_GAMMA_NEUTRAL
 
 
 class HostStats(ctypes.Structure):
@@ -180,6 +181,15 @@ PROTOTYPES = {
     "fourq_dleq_prove_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_dleq_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_dleq_verify_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_vrf_reserve": (c_int, [c_void_p, c_size_t]),
+    "fourq_vrf_prove": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "fourq_vrf_prove_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "fourq_vrf_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_vrf_verify_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_vrf_verify_keyed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_vrf_verify_keyed_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_vrf_proof_to_hash": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_vrf_proof_to_hash_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_encode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_decode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),

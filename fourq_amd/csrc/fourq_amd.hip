@@ -45,6 +45,8 @@
 #include "keyset_layout.h"
 #include "msm_shape.h"
 #include "dleq.hip.h"
+#include "vrf_layout.h"
+#include "vrf.hip.h"
 
 using namespace fq;
 
@@ -459,7 +461,8 @@ const PrimShape* find_prim(int op) {
 // (ENDO / WINDOWED, RO / NU, without / with table392) names the flavour in PipeRoute::variant, 0 or 1.
 enum PipeRouteId { PR_MUL_VAR, PR_MUL_FIX, PR_DH_VAR, PR_DH_FIX, PR_MIXED, PR_COMB, PR_ENCODE, PR_DECODE, PR_DHB_VAR, PR_DHB_FIX, PR_AFF, PR_BYTES, PR_EXCH, PR_EXCH_COMB,
                    PR_DOUBLE_AFF, PR_DOUBLE_BYTES, PR_DOUBLE_VERIFY, PR_SHA512, PR_SIG_KEYGEN, PR_SIG_SIGN, PR_SIG_VERIFY, PR_H2F, PR_H2C_MAP, PR_H2C, PR_H2C_AFFINE,
-                   PR_OPRF_BLIND, PR_OPRF_EVALUATE, PR_OPRF_FINALIZE, PR_OPRF_EVAL, PR_SC_INV, PR_KEYSET_DOUBLE, PR_KEYSET_VERIFY, PR_COUNT };
+                   PR_OPRF_BLIND, PR_OPRF_EVALUATE, PR_OPRF_FINALIZE, PR_OPRF_EVAL, PR_SC_INV, PR_KEYSET_DOUBLE, PR_KEYSET_VERIFY, PR_VRF_PROVE, PR_VRF_VERIFY, PR_VRF_KEYED, PR_VRF_HASH,
+                   PR_COUNT };
 constexpr int PIPE_SLOTS_MAX = 6;
 struct fourq_ctx {
     int device = 0;
@@ -2765,6 +2768,134 @@ FQ_API int fourq_dleq_verify(fourq_ctx* c, const uint8_t* pk32, const uint64_t* 
     return grouped_host(c, n, groups, arrays, 5, [&](char* const* d) {
         return fourq_dleq_verify_dev(c, pk32, nullptr, dst, dst_len, (uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, group_size);
     });
+}
+
+// ---- verifiable random function (include/fourq_amd.h, "verifiable random function"): prove, verify, proof_to_hash under SchnorrQ keys ------
+// Every curve operation is one of the calls above -- the Elligator map, MUL_endo on encodings (Gamma = [x]Hpt, [r]Hpt), the comb with its
+// encoding ([r]G), [k]B + [l]P or its keyed sibling ([s]G + [c]Y), the grouped sum over groups of two ([s]Hpt + [c / 392]W) -- and
+// vrf.hip.h's kernels hash, reduce, clear Gamma's cofactor, split and compare in between.  As the DLEQ proofs: the inner calls carve their own
+// layouts at the start of the work buffer, this call's regions lie behind the largest of them (vrf_layout.h), and the buffer and the
+// projective planes are sized ONCE per call for everything the inner calls will ask.
+static bool vrf_args_ok(const fourq_ctx* c, const uint8_t* dst, size_t dst_len) { return c && h2c_args_ok(dst, dst_len, FOURQ_H2C_RO); }
+static bool vrf_pair_ok(size_t n) { return n <= FOURQ_MAX_BATCH / 2; }        // verify's sum of two is a grouped sum over 2 n rows
+FQ_API int fourq_vrf_reserve(fourq_ctx* c, size_t n) {
+    if (!c || !vrf_pair_ok(n)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    return reserve_for<fq_work::Vrf>(c, n);
+}
+// h32 = encode(hash to curve, RO, of pk32 || alpha): pk32 is a register prefix of the message loop, nothing is concatenated
+static int vrf_hash_stage(fourq_ctx* c, const fq_work::Vrf& w, const uint8_t* pk32, const SigMsgs& m, const uint8_t* dst, size_t dst_len, size_t n) {
+    HIPRC_TRY(c, vrf_launch_h2f(c->stream, pk32, m, h2c_make_dst(dst, dst_len, 2), w.u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_BYTES, w.u, w.h32, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_vrf_prove_dev(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride,
+                               const uint32_t* lens, size_t msg_len, uint8_t* proof96, size_t n) {
+    if (!vrf_args_ok(c, dst, dst_len) || !sk32 || !pk32 || !proof96 || n > FOURQ_MAX_BATCH || !aligned16(sk32) || !aligned16(pk32) || !aligned16(proof96)) return FOURQ_ERR_INVALID;
+    if (!sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = reserve_for<fq_work::Vrf>(c, n))) return rc;
+    const fq_work::Vrf w(c->work, n);
+    uint8_t *h32 = (uint8_t*)w.h32, *g32 = (uint8_t*)w.g32, *t_u = (uint8_t*)w.u32, *t_v = (uint8_t*)w.v32;
+    if ((rc = vrf_hash_stage(c, w, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, dst, dst_len, n))) return rc;
+    HIPRC_TRY(c, vrf_launch_scalars(c->stream, sk32, h32, w.sc_a, w.sc_b, (u32)n));                          // x and r
+    if ((rc = comb_encode(c, w.sc_b, w.affine, w.st_u, t_u, n))) return rc;                                // u32 = encode([r]G)
+    if ((rc = mul_bytes_dev(c, ENDO, w.sc_a, h32, g32, w.st_a, n))) return rc;                             // gamma32 = encode([x]Hpt)
+    if ((rc = mul_bytes_dev(c, ENDO, w.sc_b, h32, t_v, w.st_b, n))) return rc;                             // v32 = encode([r]Hpt)
+    HIPRC_TRY(c, vrf_launch_prove(c->stream, pk32, h32, g32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), w.sc_a, w.sc_b, proof96, (u32)n));
+    return FOURQ_OK;
+}
+// Both verify calls.  key_ids == NULL: the keys are the rows of pk32.  Otherwise the rows' key bytes are gathered by index (the hashes read
+// them exactly as registered), and [s]G + [c]Y goes through the two combs -- or, with constant-time selection, through the unkeyed route on
+// the gathered bytes; the check kernel puts the key set's statuses in front of every other.
+static int vrf_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint32_t* key_ids, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride,
+                          const uint32_t* lens, size_t msg_len, const uint8_t* proof96, uint8_t* beta64, uint8_t* ok, uint8_t* status, size_t n) {
+    const void* keys = key_ids ? (const void*)key_ids : (const void*)pk32;
+    if (!vrf_args_ok(c, dst, dst_len) || !keys || !proof96 || !beta64 || !ok || !status || !vrf_pair_ok(n) || !aligned16(keys) || !aligned16(proof96) || !aligned16(beta64))
+        return FOURQ_ERR_INVALID;
+    if (!sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    if (key_ids && c->keyset_count == 0) return FOURQ_ERR_INVALID;
+    int rc = stage_comb(c, comb);
+    if (rc) return rc;
+    if ((rc = reserve_for<fq_work::Vrf>(c, n))) return rc;
+    const fq_work::Vrf w(c->work, n);
+    uint8_t *h32 = (uint8_t*)w.h32, *w32 = (uint8_t*)w.g32, *t_u = (uint8_t*)w.u32, *t_v = (uint8_t*)w.v32;
+    const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
+    const u32 count = (u32)c->keyset_count;
+    if (key_ids) {
+        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, (uint8_t*)w.pk32, (u32)n));
+        pk32 = (const uint8_t*)w.pk32;
+    }
+    if ((rc = vrf_hash_stage(c, w, pk32, m, dst, dst_len, n))) return rc;
+    HIPRC_TRY(c, vrf_launch_gamma(c->stream, proof96, h32, w.g32, w.sc_a, w.sc_b, w.pair_sc, w.pair_pt, w.st_a, w.st_pre, (u32)n));
+    if (key_ids && !c->ct) rc = fourq_keyset_double_mul_bytes_dev(c, w.sc_a, nullptr, w.sc_b, key_ids, t_u, w.st_u, n);                  // u32' = [s]G + [c]A_id
+    else rc = double_mul_dev(c, w.sc_a, nullptr, w.sc_b, pk32, true, COMBINE_ENCODE, nullptr, t_u, w.st_u, nullptr, n);                 // u32' = [s]G + [c]Y
+    if (rc) return rc;
+    if ((rc = msm_dev(c, w.pair_sc, w.pair_pt, true, t_v, w.st_v, n, 2))) return rc;                                                   // v32' = [s]Hpt + [c / 392]W
+    const VrfKeys set = { key_ids, c->keyset_status, count };
+    HIPRC_TRY(c, vrf_launch_check(c->stream, pk32, h32, proof96, w32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), dleq_make_tail("VrfOutput", dst, dst_len), w.sc_b, set, m,
+                                  w.st_u, w.st_a, w.st_pre, w.st_v, beta64, ok, status, (u32)n));
+    return FOURQ_OK;
+}
+FQ_API int fourq_vrf_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens,
+                                size_t msg_len, const uint8_t* proof96, uint8_t* beta64, uint8_t* ok, uint8_t* status, size_t n) {
+    return vrf_verify_dev(c, pk32, nullptr, comb, dst, dst_len, msgs, stride, lens, msg_len, proof96, beta64, ok, status, n);
+}
+FQ_API int fourq_vrf_verify_keyed_dev(fourq_ctx* c, const uint32_t* key_ids, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride,
+                                       const uint32_t* lens, size_t msg_len, const uint8_t* proof96, uint8_t* beta64, uint8_t* ok, uint8_t* status, size_t n) {
+    if (!key_ids) return FOURQ_ERR_INVALID;
+    return vrf_verify_dev(c, nullptr, key_ids, comb, dst, dst_len, msgs, stride, lens, msg_len, proof96, beta64, ok, status, n);
+}
+FQ_API int fourq_vrf_proof_to_hash_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* proof96, uint8_t* beta64, uint8_t* status, size_t n) {
+    if (!vrf_args_ok(c, dst, dst_len) || !proof96 || !beta64 || !status || n > FOURQ_MAX_BATCH || !aligned16(proof96) || !aligned16(beta64)) return FOURQ_ERR_INVALID;
+    if (n == 0) return FOURQ_OK;
+    CtxGuard g(c);
+    HIPRC_TRY(c, vrf_launch_proof_to_hash(c->stream, proof96, dleq_make_tail("VrfOutput", dst, dst_len), beta64, status, (u32)n));
+    return FOURQ_OK;
+}
+// host-pointer twins: copy in, the _dev call, copy out, through the pipeline's chunks; the comb is staged once, before the arrays
+static double vrf_kt_hash(size_t stride, size_t dst_len) { return h2c_kt_hash(stride + 32, dst_len, 2) + 2 * KT_ELL2 + KT_LIFT_LOWER + KT_SHA_BLOCK * (double)(2 + (160 + dst_len + 27 + 127) / 128); }
+FQ_API int fourq_vrf_prove(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride,
+                           const uint32_t* lens, size_t msg_len, uint8_t* proof96, size_t n) {
+    const double kt = vrf_kt_hash(stride, dst_len) + KT_COMB + KT_ENCODE + 2 * (KT_ENDO_VAR + KT_LIFT_LOWER + KT_CODEC);
+    const HostCall d = { { { sk32, 32 }, { pk32, 32 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { proof96, 96 } }, { PR_VRF_PROVE, 0, kt }, pipe_chunk, nullptr,
+                         reserve_for<fq_work::Vrf>, h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
+        return fourq_vrf_prove_dev(c, k.in<uint8_t>(0), k.in<uint8_t>(1), nullptr, dst, dst_len, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.out<uint8_t>(0), k.m);
+    });
+}
+FQ_API int fourq_vrf_verify(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens,
+                            size_t msg_len, const uint8_t* proof96, uint8_t* beta64, uint8_t* ok, uint8_t* status, size_t n) {
+    const double kt = vrf_kt_hash(stride, dst_len) + KT_DOUBLE + KT_DECODE + 2 * (KT_ENDO_VAR + KT_DECODE) + KT_LIFT_LOWER;
+    const HostCall d = { { { pk32, 32 }, { proof96, 96 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { beta64, 64 }, { ok, 1 }, { status, 1 } }, { PR_VRF_VERIFY, 0, kt },
+                         pipe_chunk, nullptr, reserve_for<fq_work::Vrf>,
+                         h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) && vrf_pair_ok(n) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
+    return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
+        return fourq_vrf_verify_dev(c, k.in<uint8_t>(0), nullptr, dst, dst_len, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.in<uint8_t>(1), k.out<uint8_t>(0),
+                                    k.out<uint8_t>(1), k.out<uint8_t>(2), k.m);
+    });
+}
+FQ_API int fourq_vrf_verify_keyed(fourq_ctx* c, const uint32_t* key_ids, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride,
+                                   const uint32_t* lens, size_t msg_len, const uint8_t* proof96, uint8_t* beta64, uint8_t* ok, uint8_t* status, size_t n) {
+    const double kt = vrf_kt_hash(stride, dst_len) + 2 * KT_COMB + KT_ENCODE + 2 * (KT_ENDO_VAR + KT_DECODE) + KT_LIFT_LOWER;
+    const HostCall d = { { { key_ids, 4 }, { proof96, 96 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { beta64, 64 }, { ok, 1 }, { status, 1 } }, { PR_VRF_KEYED, 0, kt },
+                         pipe_chunk, nullptr, reserve_for<fq_work::Vrf>,
+                         h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) && vrf_pair_ok(n) && sig_msgs_host_ok(msgs, stride, lens, msg_len, n) && keyset_ids_host_ok(c, key_ids, n), stride };
+    return host_call(c, n, d, [&] { return keyset_prepare(c, comb); }, [&](const Chunk& k) {
+        return fourq_vrf_verify_keyed_dev(c, k.in<uint32_t>(0), nullptr, dst, dst_len, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.in<uint8_t>(1), k.out<uint8_t>(0),
+                                           k.out<uint8_t>(1), k.out<uint8_t>(2), k.m);
+    });
+}
+FQ_API int fourq_vrf_proof_to_hash(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* proof96, uint8_t* beta64, uint8_t* status, size_t n) {
+    const HostCall d = { { { proof96, 96 } }, { { beta64, 64 }, { status, 1 } }, { PR_VRF_HASH, 0, KT_DECODE + KT_LIFT_LOWER + KT_SHA_BLOCK * (double)((32 + dst_len + 27 + 127) / 128) },
+                         unit_w4, nullptr, nullptr, h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) };
+    return host_call(c, n, d, [&](const Chunk& k) { return fourq_vrf_proof_to_hash_dev(c, dst, dst_len, k.in<uint8_t>(0), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m); });
 }
 
 // ---- pinned host memory and transfer statistics of the host-pointer calls ---------------------------------------

@@ -895,6 +895,81 @@ class Engine:
         self._ck(self._lib.fourq_dleq_verify_dev(self._ctx, _ptr(self._pk32(pk32_host)), _ptr(self._comb_arg(comb_host)), buf, dst_len, _ptr(blinded32), _ptr(evaluated32),
                                                  _ptr(proof64), _ptr(ok), _ptr(status), groups, group_size))
 
+    # ---- verifiable random function (fourq_vrf_*, fourq_vrf_verify_keyed*; the construction: include/fourq_amd.h): one row per
+    # (key, alpha), keys the signature scheme's; a proof is gamma32 || c || s, 96 bytes; beta is 64 bytes ------------------------------------
+    def vrf_reserve(self, n):
+        """Size the context's buffers for `vrf_*_dev` calls of at most n rows (fourq_vrf_reserve; reserve() is not enough for them):
+        such calls then only enqueue, with the comb staged."""
+        self._ck(self._lib.fourq_vrf_reserve(self._ctx, int(n)))
+
+    def vrf_prove(self, sk32, pk32, alphas, lens=None, dst=b"", comb=None, out=None):
+        """Proofs (n, 96) uint8 of the rows of `alphas` under the key pairs (sk32[i], pk32[i]).  Deterministic: the nonce is hashed from
+        the secret key and the input.  pk32 is an input; it is not checked against sk32."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        sk, pk = _host(sk32, 32, np.uint8), _host(pk32, 32, np.uint8)
+        if len(sk) != len(pk):
+            raise ValueError("the secret and public key arrays differ in length")
+        m, stride, lens, msg_len = self._msgs(alphas, lens, len(sk))
+        out = _out(out, len(sk), 96, np.uint8)
+        self._ck(self._lib.fourq_vrf_prove(self._ctx, _ptr(sk), _ptr(pk), _ptr(self._comb_arg(comb)), buf, dst_len, _ptr(m) if stride else None, stride, _ptr(lens), msg_len,
+                                           _ptr(out), len(sk)))
+        return out
+
+    def vrf_prove_dev(self, sk32, pk32, alphas, stride, lens, msg_len, proof96, n, dst=b"", comb_host=None):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_vrf_prove_dev(self._ctx, _ptr(sk32), _ptr(pk32), _ptr(self._comb_arg(comb_host)), buf, dst_len, _ptr(alphas), stride, _ptr(lens), msg_len,
+                                               _ptr(proof96), n))
+
+    def vrf_verify(self, pk32, alphas, proofs96, lens=None, dst=b"", comb=None, beta=None, ok=None, status=None):
+        """(beta, ok, status) per row: ok[i] = 1 iff proofs96[i] proves alphas[i] under pk32[i]; beta[i], (64,) uint8, is the VRF's output
+        then and all zero otherwise.  status says why a 0 is a 0: 0 = the proof does not hold, BYTES_DECODE_BASE + DECODE_* = the key or
+        Gamma does not decode, SIG_S_RANGE = c or s >= N, VRF_GAMMA_NEUTRAL = [392]Gamma is the neutral point."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        pk, p = _host(pk32, 32, np.uint8), _host(proofs96, 96, np.uint8)
+        if len(pk) != len(p):
+            raise ValueError("the key and proof arrays differ in length")
+        m, stride, lens, msg_len = self._msgs(alphas, lens, len(pk))
+        beta, ok, status = _out(beta, len(pk), 64, np.uint8), _out(ok, len(pk), None, np.uint8), _out(status, len(pk), None, np.uint8)
+        self._ck(self._lib.fourq_vrf_verify(self._ctx, _ptr(pk), _ptr(self._comb_arg(comb)), buf, dst_len, _ptr(m) if stride else None, stride, _ptr(lens), msg_len,
+                                            _ptr(p), _ptr(beta), _ptr(ok), _ptr(status), len(pk)))
+        return beta, ok, status
+
+    def vrf_verify_dev(self, pk32, alphas, stride, lens, msg_len, proof96, beta64, ok, status, n, dst=b"", comb_host=None):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_vrf_verify_dev(self._ctx, _ptr(pk32), _ptr(self._comb_arg(comb_host)), buf, dst_len, _ptr(alphas), stride, _ptr(lens), msg_len,
+                                                _ptr(proof96), _ptr(beta64), _ptr(ok), _ptr(status), n))
+
+    def vrf_verify_keyed(self, ids, alphas, proofs96, lens=None, dst=b"", comb=None, beta=None, ok=None, status=None):
+        """vrf_verify() with pk32[i] = the registered key ids[i] (keyset_set): (beta, ok, status).  status as vrf_verify's, or the key's
+        own status; an index outside the set is an error."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        i, p = np.ascontiguousarray(ids, dtype=np.uint32).ravel(), _host(proofs96, 96, np.uint8)
+        if len(i) != len(p):
+            raise ValueError("the index and proof arrays differ in length")
+        m, stride, lens, msg_len = self._msgs(alphas, lens, len(i))
+        beta, ok, status = _out(beta, len(i), 64, np.uint8), _out(ok, len(i), None, np.uint8), _out(status, len(i), None, np.uint8)
+        self._ck(self._lib.fourq_vrf_verify_keyed(self._ctx, _ptr(i), _ptr(self._comb_arg(comb)), buf, dst_len, _ptr(m) if stride else None, stride, _ptr(lens), msg_len,
+                                                   _ptr(p), _ptr(beta), _ptr(ok), _ptr(status), len(i)))
+        return beta, ok, status
+
+    def vrf_verify_keyed_dev(self, ids, alphas, stride, lens, msg_len, proof96, beta64, ok, status, n, dst=b"", comb_host=None):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_vrf_verify_keyed_dev(self._ctx, _ptr(ids), _ptr(self._comb_arg(comb_host)), buf, dst_len, _ptr(alphas), stride, _ptr(lens), msg_len,
+                                                       _ptr(proof96), _ptr(beta64), _ptr(ok), _ptr(status), n))
+
+    def vrf_proof_to_hash(self, proofs96, dst=b"", beta=None, status=None):
+        """(beta, status) per row from the proof alone (c and s are not looked at): what vrf_verify returns for a proof it accepts.
+        status: 0, BYTES_DECODE_BASE + DECODE_*, VRF_GAMMA_NEUTRAL; beta[i] is all zero unless it is 0."""
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        p = _host(proofs96, 96, np.uint8)
+        beta, status = _out(beta, len(p), 64, np.uint8), _out(status, len(p), None, np.uint8)
+        self._ck(self._lib.fourq_vrf_proof_to_hash(self._ctx, buf, dst_len, _ptr(p), _ptr(beta), _ptr(status), len(p)))
+        return beta, status
+
+    def vrf_proof_to_hash_dev(self, proof96, beta64, status, n, dst=b""):
+        buf, dst_len, _ = self._h2c(dst, "ro")
+        self._ck(self._lib.fourq_vrf_proof_to_hash_dev(self._ctx, buf, dst_len, _ptr(proof96), _ptr(beta64), _ptr(status), n))
+
     def dh_exchange_dev(self, a_scalars, b_scalars, base_affine_host, table392_host, out_affine, status, n):
         base = _host(base_affine_host, None).ravel()
         t = None if table392_host is None else _host(table392_host, None).ravel()

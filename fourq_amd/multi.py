@@ -299,6 +299,29 @@ class MultiEngine:
         return self._sharded_groups(lambda e, b, z, p, o, st: e.dleq_verify(pk32, b, z, p, group_size, dst, comb, ok=o, status=st), [b, z], [p],
                                     [_out(ok, groups, None, np.uint8), _out(status, groups, None, np.uint8)], group_size)
 
+    # ---- verifiable random function: rows are independent; dst, and for the keyed call the set, are replicated -----------------------------
+    def vrf_prove(self, sk32, pk32, alphas, lens=None, dst=b"", comb=None, out=None):
+        sk, pk, (m, ln) = _host(sk32, 32, np.uint8), _host(pk32, 32, np.uint8), self._msg_rows(alphas, lens)
+        self._same_len(sk, pk, m, ln)
+        return self._sharded(lambda e, sk, pk, m, ln, o: e.vrf_prove(sk, pk, m, ln, dst, comb, out=o), [sk, pk, m, ln], [_out(out, len(sk), 96, np.uint8)])
+
+    def vrf_verify(self, pk32, alphas, proofs96, lens=None, dst=b"", comb=None, beta=None, ok=None, status=None):
+        pk, p, (m, ln) = _host(pk32, 32, np.uint8), _host(proofs96, 96, np.uint8), self._msg_rows(alphas, lens)
+        self._same_len(pk, p, m, ln)
+        return self._sharded(lambda e, pk, m, p, ln, b, o, st: e.vrf_verify(pk, m, p, ln, dst, comb, beta=b, ok=o, status=st), [pk, m, p, ln],
+                             [_out(beta, len(pk), 64, np.uint8), _out(ok, len(pk), None, np.uint8), _out(status, len(pk), None, np.uint8)])
+
+    def vrf_verify_keyed(self, ids, alphas, proofs96, lens=None, dst=b"", comb=None, beta=None, ok=None, status=None):
+        i, p, (m, ln) = np.ascontiguousarray(ids, dtype=np.uint32).ravel(), _host(proofs96, 96, np.uint8), self._msg_rows(alphas, lens)
+        self._same_len(i, p, m, ln)
+        return self._sharded(lambda e, i, m, p, ln, b, o, st: e.vrf_verify_keyed(i, m, p, ln, dst, comb, beta=b, ok=o, status=st), [i, m, p, ln],
+                             [_out(beta, len(i), 64, np.uint8), _out(ok, len(i), None, np.uint8), _out(status, len(i), None, np.uint8)])
+
+    def vrf_proof_to_hash(self, proofs96, dst=b"", beta=None, status=None):
+        p = _host(proofs96, 96, np.uint8)
+        return self._sharded(lambda e, p, b, st: e.vrf_proof_to_hash(p, dst, beta=b, status=st), [p],
+                             [_out(beta, len(p), 64, np.uint8), _out(status, len(p), None, np.uint8)])
+
     # ---- commitments over a fixed generator set: the set is replicated, WHOLE groups are sharded as for the proofs -----------------------
     def commit_generators(self, count, dst):
         return self.engines[0].commit_generators(count, dst)

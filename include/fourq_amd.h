@@ -766,6 +766,95 @@ int fourq_dleq_verify(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb,
 int fourq_dleq_verify_dev(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb, const uint8_t *dst, size_t dst_len, const uint8_t *blinded32,
                           const uint8_t *evaluated32, const uint8_t *proof64, uint8_t *ok, uint8_t *status, size_t groups, size_t group_size);
 
+/* ---- verifiable random function: prove, verify and proof-to-hash in batches, under the signature scheme's keys ---------------------------------
+ * What leader election and sortition over a validator set, verifiable lotteries and authenticated denial ask for: the key holder maps a
+ * public input alpha to a pseudorandom output beta and a proof; everyone else checks the proof and gets the same beta from it.  One row
+ * per (key, alpha); rows are independent.
+ * Suite.  The suite is this library's own, as the OPRF's and the DLEQ's are: its structure is that of ECVRF (RFC 9381) with Elligator 2;
+ * interoperability with anything else is NOT claimed.  The yardstick is the CPU restatement tests/vrf_ref.py and the fixture
+ * tests/golden/vrf.json made with the reference's point functions.
+ * Notation.  H = SHA-512, LE(x) the little-endian integer of a byte string, G the generator, N the group order, dst 1..FOURQ_H2C_MAX_DST
+ * bytes, tail(L) = L || dst || I2OSP(len(dst), 1) as in fourq_dleq_*, INV392 = 1 / 392 mod N.  Keys are fourq_sig_*'s, so one key pair
+ * serves signing and the VRF: k = H(sk32), x = LE(k[0:32]) (unreduced), pk32 = fourq_sig_keygen_batch(sk32).  alpha is the row's message,
+ * under the rules fourq_sig_* has for `stride`, `lens`, `msg_len` and FOURQ_SIG_MAX_MSG.
+ *   Hpt      = hash to curve, RO mode, under dst, of the string pk32 || alpha (affine, in the subgroup of order N);  h32 = encode(Hpt)
+ *   prove(sk32, pk32, alpha) -> proof96
+ *     Gamma  = R1toAffine(MUL_endo(x, AffineToR1(Hpt)));  gamma32 = encode(Gamma)
+ *     r      = LE(H(k[32:64] || h32)) mod N                  (64 bytes hashed: deterministic, no RNG, no nonce from the caller)
+ *     u32    = encode([r]G) (the comb);  v32 = encode(R1toAffine(MUL_endo(r, AffineToR1(Hpt))))
+ *     c      = LE(H(pk32 || h32 || gamma32 || u32 || v32 || tail("VrfVerify"))) mod N        (160 fixed bytes, then the tail)
+ *     s      = (r - c x) mod N;  proof96 = gamma32 || LE32(c) || LE32(s)
+ *     pk32 is an input, as in fourq_sig_sign_batch: neither derived again nor checked against sk32.
+ *   verify(pk32, alpha, proof96) -> ok, status, beta64
+ *     Y      = decode(pk32);  Gamma = decode(proof96[0:32]);  c, s = LE(proof96[32:64]), LE(proof96[64:96])
+ *     W      = [392]Gamma by the x392 chain (curve4q.py:450-455, FOURQ_PT_COFACTOR392);  w32 = encode(W)
+ *     u32'   = encode([s]G + [c]Y)                     (fourq_double_mul_bytes_batch with k = s, l = c)
+ *     v32'   = encode([s]Hpt + [c INV392 mod N]W)      (fourq_msm_bytes_batch over the groups of two (s, h32), (c INV392 mod N, w32))
+ *     ok     = (LE(H(pk32 || h32 || proof96[0:32] || u32' || v32' || tail("VrfVerify"))) mod N == c)
+ *     beta64 = H(w32 || tail("VrfOutput")) when ok, else 64 zero bytes
+ *   proof_to_hash(proof96) -> beta64 = H(encode([392]decode(proof96[0:32])) || tail("VrfOutput"));  c and s are not looked at
+ * The label "VrfVerify" differs from the DLEQ's "Challenge" on purpose: both prefixes are 160 bytes of five encodings, and a VRF proof must
+ * not double as an OPRF proof under the same dst.
+ * Why W and INV392.  Gamma comes from the prover, who is the adversary for uniqueness, and MUL_endo is not [k]P outside the subgroup of
+ * order N.  So the verifier never feeds Gamma to a ladder: it clears the cofactor first and divides the challenge by 392 to compensate
+ * ([c INV392]W = [c]Gamma for an honest Gamma).  The output hashes W, not Gamma, so a torsion component of Gamma cannot change beta: a
+ * prover who shifts Gamma by a point of order 7 or 14 and hashes the challenge again is accepted, with the same beta.
+ * pk32 is NOT checked for order N by fourq_vrf_verify, exactly as fourq_sig_verify_batch does not check it; callers who need uniqueness
+ * against adversarially generated keys use fourq_vrf_verify_keyed: registration checks the order.
+ * fourq_vrf_verify_keyed[_dev]: the keys named by their index in the set of fourq_keyset_set.  Every hash reads the key bytes exactly as
+ * registered, u32' goes through fourq_keyset_double_mul_bytes_dev, and for an accepted key beta64, ok and status equal fourq_vrf_verify on
+ * pk32[i] = key[id_i] byte for byte.  With constant-time selection the rows' key bytes are gathered by index and the unkeyed route runs on
+ * them, as in fourq_keyset_sig_verify; the answers are identical in both modes.
+ * status, one byte per row; verify's ok is 0 and beta64 all zero unless it is 0.  A bad row never affects another.  Verify, in this order
+ * of precedence:
+ *     FOURQ_KEYSET_ID_RANGE, then the key's own status   (the keyed call only, exactly as fourq_keyset_sig_verify orders them; the host
+ *                                                         flavour refuses an index outside the set with FOURQ_ERR_INVALID, the _dev
+ *                                                         flavour clamps it before it becomes an address)
+ *     FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_* of pk32
+ *     the same code of gamma32
+ *     FOURQ_SIG_MSG_CLAMPED                              (_dev only)
+ *     FOURQ_SIG_S_RANGE                                  LE(c) >= N or LE(s) >= N
+ *     FOURQ_VRF_GAMMA_NEUTRAL                            W is the neutral point: Gamma has no component of order N
+ *   proof_to_hash reports the code of gamma32 and FOURQ_VRF_GAMMA_NEUTRAL only.  prove has no status, like fourq_sig_sign_batch; its _dev
+ *   flavour hashes a clamped row; x = 0 or r = 0 (mod N) would take a SHA-512 preimage and has no code.  An Hpt that is the neutral point
+ *   takes a hash accident: the sum of two refuses its encoding (FOURQ_BYTES_DECODE_BASE + FOURQ_DECODE_REF_ATTRIBUTE_ERROR, last in order).
+ * Secrets.  k, x and r meet no branch and no address that depends on their value in the VRF's own kernels (one reduction, the mul-sub);
+ * in the ladders and the comb that holds under fourq_ctx_set_ct_select, as everywhere.  h32, Gamma, c and s are public.
+ * Arguments.  `dst` is a HOST pointer in both flavours; `comb` is the generator's comb, or NULL = the staged one.  n == 0: FOURQ_OK,
+ * nothing touched.  FOURQ_ERR_INVALID: a NULL array, a dst of 0 or more than FOURQ_H2C_MAX_DST bytes, n above FOURQ_MAX_BATCH -- for
+ * verify and reserve above FOURQ_MAX_BATCH / 2, its sum of two has 2 n rows --, the keyed call with no set installed.  _dev array pointers
+ * are 16-byte aligned (ok and status need not be).
+ * Work buffer.  The inner calls carve their own layouts; this call's regions lie behind the largest of them (vrf_layout.h), which is more
+ * than fourq_ctx_reserve sizes: fourq_vrf_reserve(ctx, n) is the reservation.  After it, with the comb staged, a _dev call of at most n
+ * rows allocates nothing and synchronises nothing.  The host-pointer calls run the chunked pipeline: copy in, the _dev call, copy out.
+ * Names.  The entry points carry no _batch, as fourq_keyset_sig_verify does not: names ending in _batch belong to the per-element calls
+ * whose argument contract one table enumerates.  The keyed call is fourq_vrf_verify_keyed, not fourq_keyset_*: that prefix names the
+ * calls of the key set's own section.
+ * Cost: tools/vrf_timing.py measures verify against the sum of its inner calls, keyed against unkeyed, and prove
+ * (profiles/vrf_timing.txt); nothing of it is quoted here. */
+#define FOURQ_VRF_GAMMA_NEUTRAL 128   /* status of verify and proof_to_hash: [392]Gamma is the neutral point */
+int fourq_vrf_reserve(fourq_ctx *ctx, size_t n);
+/* sk32, pk32: n x 32 bytes; proof96: n x 96 bytes */
+int fourq_vrf_prove(fourq_ctx *ctx, const uint8_t *sk32, const uint8_t *pk32, const uint64_t *comb, const uint8_t *dst, size_t dst_len,
+                    const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *proof96, size_t n);
+int fourq_vrf_prove_dev(fourq_ctx *ctx, const uint8_t *sk32, const uint8_t *pk32, const uint64_t *comb, const uint8_t *dst, size_t dst_len,
+                        const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len, uint8_t *proof96, size_t n);
+/* beta64: n x 64 bytes */
+int fourq_vrf_verify(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb, const uint8_t *dst, size_t dst_len,
+                     const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                     const uint8_t *proof96, uint8_t *beta64, uint8_t *ok, uint8_t *status, size_t n);
+int fourq_vrf_verify_dev(fourq_ctx *ctx, const uint8_t *pk32, const uint64_t *comb, const uint8_t *dst, size_t dst_len,
+                         const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                         const uint8_t *proof96, uint8_t *beta64, uint8_t *ok, uint8_t *status, size_t n);
+int fourq_vrf_verify_keyed(fourq_ctx *ctx, const uint32_t *key_ids, const uint64_t *comb, const uint8_t *dst, size_t dst_len,
+                            const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                            const uint8_t *proof96, uint8_t *beta64, uint8_t *ok, uint8_t *status, size_t n);
+int fourq_vrf_verify_keyed_dev(fourq_ctx *ctx, const uint32_t *key_ids, const uint64_t *comb, const uint8_t *dst, size_t dst_len,
+                                const uint8_t *msgs, size_t stride, const uint32_t *lens, size_t msg_len,
+                                const uint8_t *proof96, uint8_t *beta64, uint8_t *ok, uint8_t *status, size_t n);
+int fourq_vrf_proof_to_hash(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *proof96, uint8_t *beta64, uint8_t *status, size_t n);
+int fourq_vrf_proof_to_hash_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *proof96, uint8_t *beta64, uint8_t *status, size_t n);
+
 /* ---- primitives (one reference function per op, batched) --------------------------------------
  * Used by the Python mirror of the reference's helper API (GFp.*, GFp2.*, DBL, ADD, phi, ...) and by
  * the parity tests to check every layer of the path on the GPU.  in/out are HOST pointers;
