@@ -47,7 +47,7 @@ struct BucketGeom {
 
 inline size_t round4(size_t x) { return (x + 3) & ~(size_t)3; }
 
-struct Bucket {
+struct Bucket : Leaf {
     BucketGeom g;
     char* inner;                    // Msm, carved by msm_dev itself when the call takes the ladder route
     uint64_t* v;                    // step 1: the four sub-scalars of decompose(k): n x 4 words

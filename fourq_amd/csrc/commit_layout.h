@@ -32,7 +32,7 @@ struct CommitGeom {
     size_t first_item(unsigned block) const { return (size_t)((unsigned long long)block * items / grid); }
 };
 
-struct Commit {
+struct Commit : Leaf {
     static constexpr size_t FOLD = 64;                          // msm.hip.h, MSM_FOLD (fourq_amd.hip asserts that they agree)
     uint64_t* rows;                 // the combs' results: n rows of 12 words
     uint64_t *part_a, *part_b;      // partial sums, rows of 12 words: groups x ceil(group_size / 64), and groups x ceil of that / 64 again

@@ -28,6 +28,7 @@
 #include <functional>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -502,10 +503,11 @@ struct fourq_ctx {
     size_t proj_capacity = 0;
     int scinv_k = 0;               // fourq_ctx_set_scinv_group (test hook): 1 / 8 / 16 = that many elements per inversion modulo N whatever the batch size; 0 = by batch size
     int norm_k = -1;               // FOURQ_NORM_K: 0 = always invert per element, 2/4/8 = always batch; -1 = by batch size
-    void* stage = nullptr;         // staging for the small host-pointer calls (tables, primitives)
+    char* stage = nullptr;         // staging for the small host-pointer calls (tables, primitives) and the grouped calls' host arrays
     size_t stage_bytes = 0;
-    char* work = nullptr;          // intermediates of the protocol-level calls (decoded points, first-half results)
+    char* work = nullptr;          // intermediates of the protocol-level calls (decoded points, first-half results): WorkScope
     size_t work_bytes = 0;
+    fq_work::Hold work_hold, proj_hold, stage_hold;    // who is using work / proj / stage right now (work_layout.h): a held buffer does not grow
     // host-pointer batches: pipe_slots device slots (and pinned bounce slots for pageable callers) cycled through
     // H2D copy -> kernels -> D2H copy on three streams
     hipStream_t copy_in = nullptr, copy_out = nullptr;
@@ -564,17 +566,68 @@ struct CtxGuard {
     explicit CtxGuard(const fourq_ctx* c) : lock(c->mu), dev(c->device) {}
 };
 
-int ensure_stage(fourq_ctx* c, size_t bytes) {
-    if (bytes <= c->stage_bytes) return FOURQ_OK;
-    if (c->stage) { HIP_TRY(c, hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
-    size_t want = bytes + bytes / 4;
-    HIP_TRY(c, hipMalloc(&c->stage, want));
-    c->stage_bytes = want;
-    return FOURQ_OK;
-}
-
 // device arrays are accessed as 16-byte vectors: every array pointer of the _dev API must be 16-byte aligned
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- the buffers that grow on demand, and who may grow them (the rule: work_layout.h).  A user that fq_work::Hold does not admit would free the buffer
+// under its caller's values and return FOURQ_OK with wrong bytes: refused like a staging under capture (staging_allowed).  Only a wrong layout header leads here.
+int refuse_held(fourq_ctx* c, const char* what, const char* who, size_t need, const fq_work::Hold& hold) {
+    snprintf(c->err, sizeof c->err, "%s: %s needs %zu, but %s is using it and admits %zu of the %zu it holds (a layout header is wrong)", what, who, need, hold.who,
+             hold.extent, hold.held);
+    return FOURQ_ERR_HIP;
+}
+// Grow by free + allocate once the stream has run dry; a buffer somebody holds stays where it is.  *have and want count units of `unit` bytes.
+template <class T> int grow(fourq_ctx* c, T** buf, size_t* have, size_t want, const char* what = nullptr, const fq_work::Hold* hold = nullptr, size_t unit = 1, bool pinned = false) {
+    if (want <= *have) return FOURQ_OK;
+    if (hold && hold->depth) return refuse_held(c, what, "a call made meanwhile", want, *hold);
+    if (*buf) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, pinned ? hipHostFree(*buf) : hipFree(*buf));
+        *buf = nullptr; *have = 0;
+    }
+    void* p = nullptr;
+    HIP_TRY(c, pinned ? hipHostMalloc(&p, want * unit, hipHostMallocDefault) : hipMalloc(&p, want * unit));
+    *buf = (T*)p; *have = want;
+    return FOURQ_OK;
+}
+// The staging buffer and the planes (in rows) grow when the request exceeds them, to a quarter more; the work buffer when a quarter more does, to that.
+int ensure_stage(fourq_ctx* c, size_t bytes) { return bytes <= c->stage_bytes ? FOURQ_OK : grow(c, &c->stage, &c->stage_bytes, bytes + bytes / 4, "the staging buffer", &c->stage_hold); }
+int ensure_proj(fourq_ctx* c, size_t n) {
+    return n <= c->proj_capacity ? FOURQ_OK : grow(c, &c->proj, &c->proj_capacity, n + n / 4, "the projective planes", &c->proj_hold, PROJ_PLANES * sizeof(uint4));
+}
+int ensure_work(fourq_ctx* c, size_t bytes) { return grow(c, &c->work, &c->work_bytes, bytes + bytes / 4, "the work buffer", &c->work_hold); }
+// What a layout's call sizes: the work buffer, and the planes as the layout says.  PLANES_BY_DH: the _dev call leaves them to dh_dev, while its
+// host twin and the *_reserve calls, which must leave nothing to allocate in mid-pipeline or under a capture, size both (reserve_for: a PipeReserve).
+template <class L, class... A> int size_for(fourq_ctx* c, bool dev_call, A... a) {
+    if (L::planes == fq_work::PLANES_SIZED || (L::planes == fq_work::PLANES_BY_DH && !dev_call)) if (int rc = ensure_proj(c, L::plane_rows(a...))) return rc;
+    return ensure_work(c, L::bytes(a...));
+}
+template <class L> int reserve_for(fourq_ctx* c, size_t big) { return size_for<L>(c, false, big); }
+// The one place that sizes the work buffer for a _dev call and carves it: WORK_SCOPE(w, Vrf, n); then w->h32.  The outermost scope on a context may
+// move the buffers; a scope opened inside it -- a call made by a call -- must fit what its parent admits, or the call is refused.  A scope that sized
+// the planes holds them too.  bucket_dev hands over to msm_dev before it opens a scope; dh_dev, mul_dev and the comb have no layout and keep no book.
+template <class L> struct WorkScope {
+    fourq_ctx* c;
+    const char* name;
+    fq_work::Hold work_parent, proj_parent;
+    std::optional<L> carving;
+    ~WorkScope() { if (carving) { c->work_hold = work_parent; if (L::planes == fq_work::PLANES_SIZED) c->proj_hold = proj_parent; } }
+    template <class... A> int open(A... a) {
+        const fq_work::Hold& held = c->work_hold;
+        const size_t need = L::bytes(a...) - L::lent(a...);
+        if (!held.admits(need)) return refuse_held(c, "the work buffer", name, need, held);
+        if (held.depth == 0) { if (int rc = size_for<L>(c, true, a...)) return rc; }
+        else if (L::planes == fq_work::PLANES_SIZED) { if (int rc = ensure_proj(c, L::plane_rows(a...))) return rc; }
+        work_parent = held; proj_parent = c->proj_hold;
+        c->work_hold = work_parent.opened(name, c->work_bytes, L::inner_extent(a...));
+        if (L::planes == fq_work::PLANES_SIZED) c->proj_hold = proj_parent.opened(name, c->proj_capacity, c->proj_capacity);
+        carving.emplace(c->work, a...);
+        return FOURQ_OK;
+    }
+    const L* operator->() const { return &*carving; }
+    const L& operator*() const { return *carving; }
+};
+#define WORK_SCOPE(w, Layout, ...) WorkScope<fq_work::Layout> w{ c, #Layout }; if (int rc_ = w.open(__VA_ARGS__)) return rc_
 
 #define HIPRC_TRY(c, expr) do { hipError_t e_ = (hipError_t)(expr); if (e_ != hipSuccess) return fail((c), e_, #expr); } while (0)
 
@@ -668,14 +721,6 @@ int normalize_group(const fourq_ctx* c, size_t n) {
     if (c->norm_k >= 0) return n >= (size_t)c->norm_k ? c->norm_k : 0;
     for (int k = 8; k >= 2; k >>= 1) if (n >= (size_t)k * c->lanes) return k;
     return 0;
-}
-int ensure_proj(fourq_ctx* c, size_t n) {
-    if (n <= c->proj_capacity) return FOURQ_OK;
-    if (c->proj) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(c->proj)); c->proj = nullptr; c->proj_capacity = 0; }
-    size_t want = n + n / 4;
-    HIP_TRY(c, hipMalloc(&c->proj, want * PROJ_PLANES * sizeof(uint4)));
-    c->proj_capacity = want;
-    return FOURQ_OK;
 }
 
 // The working-limb copy of the caller's fixed-base table stays staged between calls: a call with the same 1 KiB
@@ -815,26 +860,6 @@ void host_copy(char* dst, const char* src, size_t bytes) {
     for (auto& th : pool) th.join();
     if (done_to < bytes) memcpy(dst + done_to, src + done_to, bytes - done_to);
 }
-int grow(fourq_ctx* c, char** buf, size_t* have, size_t want, bool pinned) {
-    if (want <= *have) return FOURQ_OK;
-    if (*buf) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, pinned ? hipHostFree(*buf) : hipFree(*buf));
-        *buf = nullptr; *have = 0;
-    }
-    void* p = nullptr;
-    HIP_TRY(c, pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want));
-    *buf = (char*)p; *have = want;
-    return FOURQ_OK;
-}
-// Intermediates of the protocol-level calls: each call carves c->work by its layout in work_layout.h and asks for that layout's bytes(n)
-int ensure_work(fourq_ctx* c, size_t bytes) { return grow(c, &c->work, &c->work_bytes, bytes + bytes / 4, false); }
-// What a host-array call sizes for its largest chunk BEFORE the first chunk is enqueued (PipeReserve; ensure_proj is one of them as it stands):
-// the projective planes where the _dev call behind it defers a normalisation (Layout::planes), and that call's layout of the work buffer
-template <class Layout> int reserve_for(fourq_ctx* c, size_t big) {
-    if (int r = Layout::planes ? ensure_proj(c, big) : FOURQ_OK) return r;
-    return ensure_work(c, Layout::bytes(big));
-}
 
 int ensure_ticks(fourq_ctx* c, size_t count) {
     while (c->ticks.size() < count) {
@@ -920,7 +945,7 @@ int pipe_zero_copy(const PipeCall& p, const SlotLayout& s, const fourq_host_stat
 int pipe_single_chunk(const PipeCall& p, const SlotLayout& s, fourq_host_stats st) {
     fourq_ctx* c = p.c;
     const size_t n = p.n;
-    int rc = grow(c, &c->pipe_dev, &c->pipe_dev_bytes, s.bytes, false);
+    int rc = grow(c, &c->pipe_dev, &c->pipe_dev_bytes, s.bytes);
     if (rc) return rc;
     const bool timed = c->host_timing;
     if (timed && (rc = ensure_ticks(c, 4))) return rc;
@@ -1040,9 +1065,9 @@ int pipe_chunked(const PipeCall& p, size_t chunk, PipeRoute route, PipeReserve r
     // ON THE GPU never leaves that queue without a successor, and does not show it.
     const int want_slots = c->pipe_slots ? c->pipe_slots : ((host_wait && !bounce) ? 3 : 4);
     const int slots = pieces < (size_t)want_slots ? (int)pieces : want_slots;
-    int rc = grow(c, &c->pipe_dev, &c->pipe_dev_bytes, slot * slots, false);
+    int rc = grow(c, &c->pipe_dev, &c->pipe_dev_bytes, slot * slots);
     if (rc) return rc;
-    if (bounce && (rc = grow(c, &c->pipe_pin, &c->pipe_pin_bytes, slot * slots, true))) return rc;
+    if (bounce && (rc = grow(c, &c->pipe_pin, &c->pipe_pin_bytes, slot * slots, nullptr, nullptr, 1, true))) return rc;
     const size_t timed_pieces = c->host_timing ? (pieces < TIMED_MAX ? pieces : TIMED_MAX) : 0;
     if (timed_pieces && (rc = ensure_ticks(c, TK * timed_pieces))) return rc;
     uint64_t timed_h2d = 0, timed_d2h = 0;
@@ -1246,14 +1271,15 @@ int grouped_host(fourq_ctx* c, size_t n, size_t groups, const GroupedArray* arra
     size_t total = 0;
     for (size_t k = 0; k < count; k++) total += (arrays[k].per_row ? n : groups) * arrays[k].row_bytes;
     if (int rc = ensure_stage(c, total)) return rc;
-    // c->stage is carved here, after ensure_stage, and must stay where it is until the copies out: no _dev call that `call` makes may call
-    // ensure_stage (none does: they size the work buffer and the projective planes only; DLEQ's stage_comb runs BEFORE this function).
+    // c->stage is carved here and held until the copies out: an ensure_stage that would have to move it meanwhile is refused
+    const fq_work::Hold stage_parent = c->stage_hold;
+    c->stage_hold = stage_parent.opened("grouped_host's arrays", c->stage_bytes, c->stage_bytes);
     char* dev[GROUPED_MAX_ARRAYS] = {};
     auto staged = [&]() -> int {
         size_t used = 0;
         for (size_t k = 0; k < count; k++) {                      // the caller lists the 32- and 64-byte rows first: every one of them starts 16-byte aligned
             const size_t bytes = (arrays[k].per_row ? n : groups) * arrays[k].row_bytes;
-            dev[k] = (char*)c->stage + used;
+            dev[k] = c->stage + used;
             if (arrays[k].in) HIP_TRY(c, hipMemcpyAsync(dev[k], arrays[k].in, bytes, hipMemcpyHostToDevice, c->stream));
             used += bytes;
         }
@@ -1264,6 +1290,7 @@ int grouped_host(fourq_ctx* c, size_t n, size_t groups, const GroupedArray* arra
         return FOURQ_OK;
     };
     const int rc = staged();
+    c->stage_hold = stage_parent;
     if (rc != FOURQ_OK) (void)hipStreamSynchronize(c->stream);    // as run_pipeline: nothing of this call may still read or write the caller's arrays
     return rc;
 }
@@ -1425,7 +1452,7 @@ FQ_API int fourq_ctx_destroy(fourq_ctx* c) {
     DeviceGuard g(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     for (void* p : { (void*)c->scratch, (void*)c->proj, (void*)c->table_limbs, (void*)c->table_packed, (void*)c->part_counter, (void*)c->part_list,
-                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, (void*)c->commit_combs, (void*)c->keyset_combs, (void*)c->keyset_bytes, (void*)c->shape_desc, c->stage, (void*)c->work, (void*)c->pipe_dev })
+                     (void*)c->part_fix, (void*)c->comb_limbs, (void*)c->comb_packed, (void*)c->commit_combs, (void*)c->keyset_combs, (void*)c->keyset_bytes, (void*)c->shape_desc, (void*)c->stage, (void*)c->work, (void*)c->pipe_dev })
         if (p) (void)hipFree(p);
     if (c->pipe_pin) (void)hipHostFree(c->pipe_pin);
     if (c->zero_copy) (void)hipHostFree(c->zero_copy);
@@ -1731,12 +1758,10 @@ static int dh_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const u
     if (!aligned16(scalars) || !aligned16(keys32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::DhBytes::bytes(n));       // the planes only if dh_dev defers: not reserve_for<DhBytes>
-    if (rc) return rc;
-    const fq_work::DhBytes w(c->work, n);
-    if ((rc = fourq_decode_batch_dev(c, keys32, w.pts, w.st_decode, n))) return rc;
-    if ((rc = dh_dev(c, algo, scalars, w.pts, table, w.shared, w.st_dh, n))) return rc;    // an undecodable key is (0, 0): rejected again here
-    hipLaunchKernelGGL(encode_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, w.shared, w.st_decode, w.st_dh,
+    WORK_SCOPE(w, DhBytes, n);
+    if (int rc = fourq_decode_batch_dev(c, keys32, w->pts, w->st_decode, n)) return rc;
+    if (int rc = dh_dev(c, algo, scalars, w->pts, table, w->shared, w->st_dh, n)) return rc;    // an undecodable key is (0, 0): rejected again here
+    hipLaunchKernelGGL(encode_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, w->shared, w->st_decode, w->st_dh,
                        (u64*)out32, status, (u32)n);
     HIP_TRY(c, hipGetLastError());
     return FOURQ_OK;
@@ -1794,12 +1819,10 @@ static int mul_affine_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const
     if (!aligned16(scalars) || !aligned16(points_affine) || !aligned16(out_affine)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_for<fq_work::MulRows>(c, n);
-    if (rc) return rc;
-    const fq_work::MulRows w(c->work, n);
+    WORK_SCOPE(w, MulRows, n);
     u32 stride;
-    if ((rc = mul_rows_dev(c, algo, scalars, points_affine, false, w.rows_in, w.rows_out, nullptr, n, &stride))) return rc;
-    return launch_lower(c, false, w.rows_out, stride, nullptr, out_affine, nullptr, n);
+    if (int rc = mul_rows_dev(c, algo, scalars, points_affine, false, w->rows_in, w->rows_out, nullptr, n, &stride)) return rc;
+    return launch_lower(c, false, w->rows_out, stride, nullptr, out_affine, nullptr, n);
 }
 static int mul_affine_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint64_t* points_affine, uint64_t* out_affine, size_t n) {
     const int v = algo == ENDO ? 0 : 1;
@@ -1813,12 +1836,10 @@ static int mul_bytes_dev(fourq_ctx* c, int algo, const uint64_t* scalars, const 
     if (!aligned16(scalars) || !aligned16(points32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_for<fq_work::MulRows>(c, n);
-    if (rc) return rc;
-    const fq_work::MulRows w(c->work, n);
+    WORK_SCOPE(w, MulRows, n);
     u32 stride;
-    if ((rc = mul_rows_dev(c, algo, scalars, points32, true, w.rows_in, w.rows_out, w.st_decode, n, &stride))) return rc;
-    return launch_lower(c, true, w.rows_out, stride, w.st_decode, (uint64_t*)out32, status, n);
+    if (int rc = mul_rows_dev(c, algo, scalars, points32, true, w->rows_in, w->rows_out, w->st_decode, n, &stride)) return rc;
+    return launch_lower(c, true, w->rows_out, stride, w->st_decode, (uint64_t*)out32, status, n);
 }
 static int mul_bytes_host(fourq_ctx* c, int algo, const uint64_t* scalars, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n) {
     const int v = algo == ENDO ? 0 : 1;
@@ -1847,17 +1868,15 @@ FQ_API int fourq_dh_exchange_batch_dev(fourq_ctx* c, const uint64_t* a, const ui
     if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_for<Exchange>
-    if (rc) return rc;
-    const fq_work::Exchange w(c->work, n);                     // mid = DH(b_i, base): the public keys
+    WORK_SCOPE(w, Exchange, n);      // mid = DH(b_i, base): the public keys
     AffineArg point;
     memcpy(point.w, base_affine, sizeof point.w);             // read once, here: the launch carries it
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(broadcast_point_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, point, w.base_pts, (u32)n);
+    hipLaunchKernelGGL(broadcast_point_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, point, w->base_pts, (u32)n);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = dh_dev(c, ENDO, b, w.base_pts, table392, w.mid, w.st_first, n))) return rc;
-    if ((rc = dh_dev(c, ENDO, a, w.mid, nullptr, out, status, n))) return rc;
-    hipLaunchKernelGGL(merge_status_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, w.st_first, status, (u32)n);
+    if (int rc = dh_dev(c, ENDO, b, w->base_pts, table392, w->mid, w->st_first, n)) return rc;
+    if (int rc = dh_dev(c, ENDO, a, w->mid, nullptr, out, status, n)) return rc;
+    hipLaunchKernelGGL(merge_status_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, w->st_first, status, (u32)n);
     HIP_TRY(c, hipGetLastError());
     return FOURQ_OK;
 }
@@ -1878,12 +1897,10 @@ FQ_API int fourq_dh_exchange_comb_batch_dev(fourq_ctx* c, const uint64_t* a, con
     if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::Exchange::bytes(n));      // the planes only if dh_dev defers: not reserve_for<Exchange>
-    if (rc) return rc;
-    const fq_work::Exchange w(c->work, n);                     // mid = [b_i]B: the public keys
-    if ((rc = fourq_comb_mul_batch_dev(c, b, comb, w.mid, w.st_first, n))) return rc;
-    if ((rc = dh_dev(c, ENDO, a, w.mid, nullptr, out, status, n))) return rc;
-    hipLaunchKernelGGL(merge_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, w.st_first, status, (u32)n);
+    WORK_SCOPE(w, Exchange, n);      // mid = [b_i]B: the public keys
+    if (int rc = fourq_comb_mul_batch_dev(c, b, comb, w->mid, w->st_first, n)) return rc;
+    if (int rc = dh_dev(c, ENDO, a, w->mid, nullptr, out, status, n)) return rc;
+    hipLaunchKernelGGL(merge_status_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, w->st_first, status, (u32)n);
     HIP_TRY(c, hipGetLastError());
     return FOURQ_OK;
 }
@@ -1912,16 +1929,15 @@ static int double_mul_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb,
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::DoubleMul>(c, n))) return rc;
-    const fq_work::DoubleMul w(c->work, n);
+    WORK_SCOPE(w, DoubleMul, n);
     // (1) [k_i]B, projective
-    if ((rc = launch_comb_deferred(c, k, w.st_comb, n))) return rc;
+    if ((rc = launch_comb_deferred(c, k, w->st_comb, n))) return rc;
     // (2) [l_i]P_i, projective
     u32 stride;
-    if ((rc = mul_rows_dev(c, ENDO, l, points, encoded, w.rows_in, w.rows_out, w.st_decode, n, &stride))) return rc;
+    if ((rc = mul_rows_dev(c, ENDO, l, points, encoded, w->rows_in, w->rows_out, w->st_decode, n, &stride))) return rc;
     // (3) the sum, lowered
-    HIPRC_TRY(c, chain_launch_combine(n > 2 * c->lanes ? 2 : 1, out_kind, c->stream, c->proj, (u32)c->proj_capacity, w.rows_out, stride,
-                                      encoded ? w.st_decode : nullptr, (const u64*)expect32, (u64*)out, status, ok, (u32)n));
+    HIPRC_TRY(c, chain_launch_combine(n > 2 * c->lanes ? 2 : 1, out_kind, c->stream, c->proj, (u32)c->proj_capacity, w->rows_out, stride,
+                                      encoded ? w->st_decode : nullptr, (const u64*)expect32, (u64*)out, status, ok, (u32)n));
     return FOURQ_OK;
 }
 FQ_API int fourq_double_mul_affine_batch_dev(fourq_ctx* c, const uint64_t* k, const uint64_t* comb, const uint64_t* l, const uint64_t* p, uint64_t* o, size_t n) { return double_mul_dev(c, k, comb, l, p, false, COMBINE_AFFINE, nullptr, o, nullptr, nullptr, n); }
@@ -1974,13 +1990,12 @@ static int msm_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bo
     int rc = grouped_rows(c && scalars && points && out && (!encoded || status) && aligned16(scalars) && aligned16(points) && aligned16(out), groups, group_size, &n);
     if (rc || !n) return rc;
     CtxGuard g(c);
-    if ((rc = reserve_for<fq_work::Msm>(c, n))) return rc;
-    const fq_work::Msm w(c->work, n);
+    WORK_SCOPE(w, Msm, n);
     u32 stride;
-    if ((rc = mul_rows_dev(c, ENDO, scalars, points, encoded, w.rows_in, w.rows_out, encoded ? w.st_decode : nullptr, n, &stride))) return rc;
-    const uint64_t* rows = w.rows_out;
-    const uint8_t* st = encoded ? w.st_decode : nullptr;
-    if ((rc = fold_to_one_row(c, { w.part_a, w.part_b, w.st_a, w.st_b }, groups, group_size, &rows, &stride, &st))) return rc;
+    if ((rc = mul_rows_dev(c, ENDO, scalars, points, encoded, w->rows_in, w->rows_out, encoded ? w->st_decode : nullptr, n, &stride))) return rc;
+    const uint64_t* rows = w->rows_out;
+    const uint8_t* st = encoded ? w->st_decode : nullptr;
+    if ((rc = fold_to_one_row(c, { w->part_a, w->part_b, w->st_a, w->st_b }, groups, group_size, &rows, &stride, &st))) return rc;
     return launch_lower(c, encoded, rows, stride, st, (uint64_t*)out, status, groups);
 }
 // Host arrays of the grouped sums on either route (grouped_host).  sum_dev: the _dev call to make -- it gets msm_dev's five arguments behind the
@@ -2044,7 +2059,7 @@ FQ_API int fourq_raggedsum_shape_reserve(fourq_ctx* c) {
     if (!c) return FOURQ_ERR_INVALID;
     CtxGuard g(c);
     if (c->shape.groups == 0) return FOURQ_ERR_INVALID;
-    return ensure_work(c, fq_work::MsmRagged::bytes(c->shape.rows, c->shape.groups));
+    return size_for<fq_work::MsmRagged>(c, false, c->shape.rows, c->shape.groups);
 }
 // fold_to_one_row over the planned passes: the first writes part_a, the next part_b, and so on; *rows, *stride and *st then name the one row
 // per group (they are unchanged where the plan has no pass: every group has exactly one row).
@@ -2065,14 +2080,13 @@ static int ragged_dev(fourq_ctx* c, const uint64_t* scalars, const void* points,
     CtxGuard g(c);
     const size_t groups = c->shape.groups, n = c->shape.rows;
     if (groups == 0) return FOURQ_ERR_INVALID;                // no shape
-    int rc = ensure_work(c, fq_work::MsmRagged::bytes(n, groups));
-    if (rc) return rc;
-    const fq_work::MsmRagged w(c->work, n, groups);
+    WORK_SCOPE(w, MsmRagged, n, groups);
+    int rc;
     u32 stride = 12;
-    if (n && (rc = mul_rows_dev(c, ENDO, scalars, points, encoded, w.rows_in, w.rows_out, encoded ? w.st_decode : nullptr, n, &stride))) return rc;
-    const uint64_t* rows = w.rows_out;
-    const uint8_t* st = encoded ? w.st_decode : nullptr;
-    if ((rc = fold_planned(c, { w.part_a, w.part_b, w.st_a, w.st_b }, &rows, &stride, &st))) return rc;
+    if (n && (rc = mul_rows_dev(c, ENDO, scalars, points, encoded, w->rows_in, w->rows_out, encoded ? w->st_decode : nullptr, n, &stride))) return rc;
+    const uint64_t* rows = w->rows_out;
+    const uint8_t* st = encoded ? w->st_decode : nullptr;
+    if ((rc = fold_planned(c, { w->part_a, w->part_b, w->st_a, w->st_b }, &rows, &stride, &st))) return rc;
     return launch_lower(c, encoded, rows, stride, st, (uint64_t*)out, status, groups);
 }
 // Host arrays (grouped_host): n rows in, `groups` rows out.  The shape is read under the lock, which grouped_host takes again around the copies.
@@ -2105,7 +2119,7 @@ FQ_API int fourq_bucketsum_reserve(fourq_ctx* c, size_t groups, size_t group_siz
     CtxGuard g(c);
     if (!window) window = (unsigned)fourq_bucketsum_window(group_size);
     if (!window) return reserve_for<fq_work::Msm>(c, n);
-    return ensure_work(c, fq_work::Bucket::bytes(groups, group_size, window));
+    return size_for<fq_work::Bucket>(c, false, groups, group_size, window);
 }
 // In constant-time selection mode the ladder route runs whatever the window is: a bucket's address is a digit of a scalar.
 static int bucket_dev(fourq_ctx* c, const uint64_t* scalars, const void* points, bool encoded, void* out, uint8_t* status, size_t groups, size_t group_size, unsigned window) {
@@ -2116,14 +2130,13 @@ static int bucket_dev(fourq_ctx* c, const uint64_t* scalars, const void* points,
     CtxGuard g(c);
     if (!window) window = (unsigned)fourq_bucketsum_window(group_size);
     if (c->ct || !window) return msm_dev(c, scalars, points, encoded, out, status, groups, group_size);
-    if ((rc = ensure_work(c, fq_work::Bucket::bytes(groups, group_size, window)))) return rc;
-    const fq_work::Bucket w(c->work, groups, group_size, window);
+    WORK_SCOPE(w, Bucket, groups, group_size, window);
     if (encoded) {
-        hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)points, w.affine, w.st_decode, (u32)n);
+        hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)points, w->affine, w->st_decode, (u32)n);
         HIP_TRY(c, hipGetLastError());
     }
-    HIPRC_TRY(c, chain_launch_bucket_sum(c->stream, w, scalars, encoded ? w.affine : (const u64*)points, encoded ? w.st_decode : nullptr));
-    return launch_lower(c, encoded, w.sum, 12, w.st_sum, (uint64_t*)out, status, groups);
+    HIPRC_TRY(c, chain_launch_bucket_sum(c->stream, *w, scalars, encoded ? w->affine : (const u64*)points, encoded ? w->st_decode : nullptr));
+    return launch_lower(c, encoded, w->sum, 12, w->st_sum, (uint64_t*)out, status, groups);
 }
 FQ_API int fourq_bucketsum_affine_dev(fourq_ctx* c, const uint64_t* s, const uint64_t* p, uint64_t* o, size_t groups, size_t group_size, unsigned window) { return bucket_dev(c, s, p, false, o, nullptr, groups, group_size, window); }
 FQ_API int fourq_bucketsum_bytes_dev(fourq_ctx* c, const uint64_t* s, const uint8_t* p, uint8_t* o, uint8_t* st, size_t groups, size_t group_size, unsigned window) { return bucket_dev(c, s, p, true, o, st, groups, group_size, window); }
@@ -2193,9 +2206,9 @@ FQ_API int fourq_commit_reserve(fourq_ctx* c, size_t groups, size_t group_size) 
     const int rc = grouped_rows(c != nullptr, groups, group_size, &n);
     if (rc || !n) return rc;
     CtxGuard g(c);
-    return ensure_work(c, fq_work::Commit::bytes(groups, group_size));
+    return size_for<fq_work::Commit>(c, false, groups, group_size);
 }
-// The combs into w.rows, the fold passes of the grouped sums until one row per group is left, the lowering: affine words, or the encoding.
+// The combs into w->rows, the fold passes of the grouped sums until one row per group is left, the lowering: affine words, or the encoding.
 static int commit_dev(fourq_ctx* c, const uint64_t* scalars, void* out, bool encoded, size_t groups, size_t group_size, int route) {
     size_t n;
     int rc = grouped_rows(c && scalars && out && route >= 0 && route <= 2 && aligned16(scalars) && aligned16(out), groups, group_size, &n);
@@ -2203,17 +2216,16 @@ static int commit_dev(fourq_ctx* c, const uint64_t* scalars, void* out, bool enc
     CtxGuard g(c);
     if (group_size > c->commit_count) return FOURQ_ERR_INVALID;     // no set: count 0
     if (!route) route = fourq_commit_route(groups);
-    if ((rc = ensure_work(c, fq_work::Commit::bytes(groups, group_size)))) return rc;
-    const fq_work::Commit w(c->work, groups, group_size);
-    if (c->ct) HIPRC_TRY(c, ct_launch_commit((unsigned)(c->lanes_w4 / BLOCK), c->stream, scalars, c->commit_combs, w.rows, groups, group_size));
-    else HIPRC_TRY(c, chain_launch_commit(route, (unsigned)c->cus, c->stream, scalars, c->commit_combs, w.rows, groups, group_size));
-    const uint64_t* rows = w.rows;
+    WORK_SCOPE(w, Commit, groups, group_size);
+    if (c->ct) HIPRC_TRY(c, ct_launch_commit((unsigned)(c->lanes_w4 / BLOCK), c->stream, scalars, c->commit_combs, w->rows, groups, group_size));
+    else HIPRC_TRY(c, chain_launch_commit(route, (unsigned)c->cus, c->stream, scalars, c->commit_combs, w->rows, groups, group_size));
+    const uint64_t* rows = w->rows;
     const uint8_t* st = nullptr;
     u32 stride = 12;
-    if ((rc = fold_to_one_row(c, { w.part_a, w.part_b, nullptr, nullptr }, groups, group_size, &rows, &stride, &st))) return rc;
+    if ((rc = fold_to_one_row(c, { w->part_a, w->part_b, nullptr, nullptr }, groups, group_size, &rows, &stride, &st))) return rc;
     if (!encoded) return launch_lower(c, false, rows, stride, nullptr, (uint64_t*)out, nullptr, groups);
-    HIP_TRY(c, hipMemsetAsync(w.st_zero, 0, groups, c->stream));
-    return launch_lower(c, true, rows, stride, w.st_zero, (uint64_t*)out, w.st_out, groups);
+    HIP_TRY(c, hipMemsetAsync(w->st_zero, 0, groups, c->stream));
+    return launch_lower(c, true, rows, stride, w->st_zero, (uint64_t*)out, w->st_out, groups);
 }
 // Host arrays (grouped_host).  The set's size is read under the lock, as in commit_dev.
 static int commit_arrays(fourq_ctx* c, const uint64_t* scalars, void* out, bool encoded, size_t groups, size_t group_size, int route) {
@@ -2259,10 +2271,9 @@ FQ_API int fourq_sig_keygen_batch_dev(fourq_ctx* c, const uint8_t* sk32, const u
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::Sig>(c, n))) return rc;
-    const fq_work::Sig w(c->work, n);
-    HIPRC_TRY(c, sig_launch_nonce(c->stream, false, sk32, SigMsgs{ nullptr, 0, nullptr, 0 }, w.a, nullptr, (u32)n));
-    return comb_encode(c, w.a, w.affine, w.st_comb, pk32, n);      // [a]G; the projective neutral would need a = 0 mod N
+    WORK_SCOPE(w, Sig, n);
+    HIPRC_TRY(c, sig_launch_nonce(c->stream, false, sk32, SigMsgs{ nullptr, 0, nullptr, 0 }, w->a, nullptr, (u32)n));
+    return comb_encode(c, w->a, w->affine, w->st_comb, pk32, n);      // [a]G; the projective neutral would need a = 0 mod N
 }
 FQ_API int fourq_sig_sign_batch_dev(fourq_ctx* c, const uint8_t* sk32, const uint8_t* pk32, const uint64_t* comb,
                                     const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len, uint8_t* sig64, size_t n) {
@@ -2272,12 +2283,11 @@ FQ_API int fourq_sig_sign_batch_dev(fourq_ctx* c, const uint8_t* sk32, const uin
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::Sig>(c, n))) return rc;
-    const fq_work::Sig w(c->work, n);
+    WORK_SCOPE(w, Sig, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
-    HIPRC_TRY(c, sig_launch_nonce(c->stream, true, sk32, m, w.a, w.r, (u32)n));
-    if ((rc = comb_encode(c, w.r, w.affine, w.st_comb, w.r32, n))) return rc;
-    HIPRC_TRY(c, sig_launch_finish(c->stream, w.r32, pk32, m, w.a, w.r, sig64, (u32)n));
+    HIPRC_TRY(c, sig_launch_nonce(c->stream, true, sk32, m, w->a, w->r, (u32)n));
+    if ((rc = comb_encode(c, w->r, w->affine, w->st_comb, w->r32, n))) return rc;
+    HIPRC_TRY(c, sig_launch_finish(c->stream, w->r32, pk32, m, w->a, w->r, sig64, (u32)n));
     return FOURQ_OK;
 }
 FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
@@ -2288,8 +2298,8 @@ FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const u
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::DoubleMul>(c, n))) return rc;                         // SigVerify is DoubleMul with its tail carved: double_mul_dev below asks for the same and moves nothing
-    const fq_work::SigTail w = fq_work::SigVerify(c->work, n).sig;
+    WORK_SCOPE(scope, SigVerify, n);
+    const fq_work::SigTail& w = scope->sig;
     HIPRC_TRY(c, sig_launch_challenge(c->stream, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w.s, w.h, w.r32, w.pre, (u32)n));
     if ((rc = double_mul_dev(c, w.s, nullptr, w.h, pk32, true, COMBINE_VERIFY, (const uint8_t*)w.r32, nullptr, status, ok, n))) return rc;
     HIPRC_TRY(c, sig_launch_merge(c->stream, w.pre, ok, status, (u32)n));
@@ -2319,7 +2329,7 @@ FQ_API int fourq_sig_sign_batch(fourq_ctx* c, const uint8_t* sk32, const uint8_t
 FQ_API int fourq_sig_verify_batch(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
                                   const uint8_t* sig64, uint8_t* ok, uint8_t* status, size_t n) {
     const HostCall d = { { { pk32, 32 }, { sig64, 64 }, { msgs, stride }, { lens, 4, MAY_BE_NULL } }, { { ok, 1 }, { status, 1 } },
-                         { PR_SIG_VERIFY, 0, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, pipe_chunk, nullptr, reserve_for<fq_work::DoubleMul>,
+                         { PR_SIG_VERIFY, 0, KT_DOUBLE + KT_DECODE + sig_kt_hash(stride, 64) }, pipe_chunk, nullptr, reserve_for<fq_work::SigVerify>,
                          sig_msgs_host_ok(msgs, stride, lens, msg_len, n), stride };
     return host_call(c, n, d, [&] { return stage_comb(c, comb); }, [&](const Chunk& k) {
         return fourq_sig_verify_batch_dev(c, k.in<uint8_t>(0), nullptr, k.in<uint8_t>(2), stride, k.in<uint32_t>(3), msg_len, k.in<uint8_t>(1), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m);
@@ -2398,17 +2408,16 @@ FQ_API int fourq_keyset_double_mul_bytes_dev(fourq_ctx* c, const uint64_t* k, co
     if (c->keyset_count == 0) return FOURQ_ERR_INVALID;
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::Keyset>(c, n))) return rc;
-    const fq_work::Keyset w(c->work, n);
+    WORK_SCOPE(w, Keyset, n);
     const u32 count = (u32)c->keyset_count;
     if (c->ct) {
-        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, w.pk32, (u32)n));
-        if ((rc = double_mul_dev(c, k, nullptr, l, w.pk32, true, COMBINE_ENCODE, nullptr, out32, status, nullptr, n))) return rc;
+        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, w->pk32, (u32)n));
+        if ((rc = double_mul_dev(c, k, nullptr, l, w->pk32, true, COMBINE_ENCODE, nullptr, out32, status, nullptr, n))) return rc;
         HIPRC_TRY(c, chain_launch_keyset_fix(c->stream, key_ids, c->keyset_status, count, (u64*)out32, nullptr, status, (u32)n));
         return FOURQ_OK;
     }
-    HIPRC_TRY(c, chain_launch_keyset_comb(c->stream, k, l, key_ids, c->comb_limbs, c->keyset_combs, c->keyset_status, count, w.rows, w.pre, (u32)n));
-    HIPRC_TRY(c, chain_launch_keyset_lower(c->stream, false, w.rows, w.pre, nullptr, (u64*)out32, nullptr, status, (u32)n));
+    HIPRC_TRY(c, chain_launch_keyset_comb(c->stream, k, l, key_ids, c->comb_limbs, c->keyset_combs, c->keyset_status, count, w->rows, w->pre, (u32)n));
+    HIPRC_TRY(c, chain_launch_keyset_lower(c->stream, false, w->rows, w->pre, nullptr, (u64*)out32, nullptr, status, (u32)n));
     return FOURQ_OK;
 }
 FQ_API int fourq_keyset_sig_verify_dev(fourq_ctx* c, const uint32_t* key_ids, const uint64_t* comb, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
@@ -2421,19 +2430,18 @@ FQ_API int fourq_keyset_sig_verify_dev(fourq_ctx* c, const uint32_t* key_ids, co
     if (c->keyset_count == 0) return FOURQ_ERR_INVALID;
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::Keyset>(c, n))) return rc;
-    const fq_work::Keyset w(c->work, n);
+    WORK_SCOPE(w, Keyset, n);
     const u32 count = (u32)c->keyset_count;
     if (c->ct) {
-        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, w.pk32, (u32)n));
-        if ((rc = fourq_sig_verify_batch_dev(c, w.pk32, nullptr, msgs, stride, lens, msg_len, sig64, ok, status, n))) return rc;
+        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, w->pk32, (u32)n));
+        if ((rc = fourq_sig_verify_batch_dev(c, w->pk32, nullptr, msgs, stride, lens, msg_len, sig64, ok, status, n))) return rc;
         HIPRC_TRY(c, chain_launch_keyset_fix(c->stream, key_ids, c->keyset_status, count, nullptr, ok, status, (u32)n));
         return FOURQ_OK;
     }
-    HIPRC_TRY(c, sig_launch_challenge_keyed(c->stream, key_ids, c->keyset_bytes, c->keyset_status, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w.s, w.h, w.r32,
-                                            w.pre, (u32)n));
-    HIPRC_TRY(c, chain_launch_keyset_comb(c->stream, w.s, w.h, key_ids, c->comb_limbs, c->keyset_combs, c->keyset_status, count, w.rows, nullptr, (u32)n));
-    HIPRC_TRY(c, chain_launch_keyset_lower(c->stream, true, w.rows, w.pre, w.r32, nullptr, ok, status, (u32)n));
+    HIPRC_TRY(c, sig_launch_challenge_keyed(c->stream, key_ids, c->keyset_bytes, c->keyset_status, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w->s, w->h, w->r32,
+                                            w->pre, (u32)n));
+    HIPRC_TRY(c, chain_launch_keyset_comb(c->stream, w->s, w->h, key_ids, c->comb_limbs, c->keyset_combs, c->keyset_status, count, w->rows, nullptr, (u32)n));
+    HIPRC_TRY(c, chain_launch_keyset_lower(c->stream, true, w->rows, w->pre, w->r32, nullptr, ok, status, (u32)n));
     return FOURQ_OK;
 }
 // host-pointer twins: key_ids is a 4-byte-per-row input in place of the key bytes
@@ -2486,11 +2494,10 @@ static int hash_to_curve_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, i
     if (!c || !out || n > FOURQ_MAX_BATCH || !aligned16(out) || !h2c_args_ok(dst, dst_len, mode) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    if (int rc = reserve_for<fq_work::H2c>(c, n)) return rc;
+    WORK_SCOPE(w, H2c, n);
     const int count = mode == FOURQ_H2C_RO ? 2 : 1;
-    uint64_t* u = fq_work::H2c(c->work, n).u;
-    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), u, (u32)n));
-    HIPRC_TRY(c, h2c_launch_ell2(c->stream, count, out_kind, u, (uint64_t*)out, (u32)n));
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), w->u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, count, out_kind, w->u, (uint64_t*)out, (u32)n));
     return FOURQ_OK;
 }
 FQ_API int fourq_hash_to_curve_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dl, int mode, const uint8_t* m, size_t st, const uint32_t* ln, size_t ml, uint8_t* o, size_t n) { return hash_to_curve_dev(c, dst, dl, mode, m, st, ln, ml, H2C_OUT_BYTES, o, n); }
@@ -2555,16 +2562,14 @@ FQ_API int fourq_oprf_blind_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t d
     if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_for<fq_work::OprfBlind>(c, n);
-    if (rc) return rc;
-    const fq_work::OprfBlind w(c->work, n);
+    WORK_SCOPE(w, OprfBlind, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
-    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w.u, (u32)n));
-    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w.u, w.pts, (u32)n));
-    HIP_TRY(c, hipMemsetAsync(w.st_decode, 0, n, c->stream));              // the lowering reads a decode code per row: these points were never decoded
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w->u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w->u, w->pts, (u32)n));
+    HIP_TRY(c, hipMemsetAsync(w->st_decode, 0, n, c->stream));              // the lowering reads a decode code per row: these points were never decoded
     u32 row_words;
-    if ((rc = mul_rows_dev(c, ENDO, blinds, w.pts, false, w.rows_in, w.rows_out, nullptr, n, &row_words))) return rc;
-    if ((rc = launch_lower(c, true, w.rows_out, row_words, w.st_decode, (uint64_t*)out32, status, n))) return rc;
+    if (int rc = mul_rows_dev(c, ENDO, blinds, w->pts, false, w->rows_in, w->rows_out, nullptr, n, &row_words)) return rc;
+    if (int rc = launch_lower(c, true, w->rows_out, row_words, w->st_decode, (uint64_t*)out32, status, n)) return rc;
     HIPRC_TRY(c, oprf_launch_blind_merge(c->stream, blinds, m, out32, status, (u32)n));
     return FOURQ_OK;
 }
@@ -2572,11 +2577,9 @@ FQ_API int fourq_oprf_evaluate_batch_dev(fourq_ctx* c, const uint64_t* key, cons
     if (!c || !key || !blinded32 || !out32 || !status || n > FOURQ_MAX_BATCH || !aligned16(blinded32) || !aligned16(out32)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::OprfEvaluate::bytes(n));               // the planes only if dh_dev defers, as dh_bytes_dev
-    if (rc) return rc;
-    const fq_work::OprfEvaluate w(c->work, n);
-    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w.keys, (u32)n));
-    return dh_bytes_dev(c, ENDO, w.keys, blinded32, nullptr, out32, status, n);     // carves DhBytes at the buffer's start: w.dh
+    WORK_SCOPE(w, OprfEvaluate, n);
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w->keys, (u32)n));
+    return dh_bytes_dev(c, ENDO, w->keys, blinded32, nullptr, out32, status, n);     // carves DhBytes at the buffer's start: w->dh
 }
 FQ_API int fourq_oprf_finalize_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens, size_t msg_len,
                                          const uint64_t* blinds, const uint8_t* evaluated32, uint8_t* out64, uint8_t* status, size_t n) {
@@ -2584,14 +2587,12 @@ FQ_API int fourq_oprf_finalize_batch_dev(fourq_ctx* c, const uint8_t* dst, size_
     if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = reserve_for<fq_work::OprfFinalize>(c, n);
-    if (rc) return rc;
-    const fq_work::OprfFinalize w(c->work, n);
-    HIPRC_TRY(c, oprf_launch_sc_inv(c->stream, scinv_group(c, n), blinds, w.inv, w.st_zero, (u32)n));
+    WORK_SCOPE(w, OprfFinalize, n);
+    HIPRC_TRY(c, oprf_launch_sc_inv(c->stream, scinv_group(c, n), blinds, w->inv, w->st_zero, (u32)n));
     u32 row_words;
-    if ((rc = mul_rows_dev(c, ENDO, w.inv, evaluated32, true, w.rows_in, w.rows_out, w.st_decode, n, &row_words))) return rc;
-    if ((rc = launch_lower(c, true, w.rows_out, row_words, w.st_decode, w.e32, w.st_lower, n))) return rc;
-    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w.e32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, oprf_make_tail(dst, dst_len), w.st_lower, w.st_zero,
+    if (int rc = mul_rows_dev(c, ENDO, w->inv, evaluated32, true, w->rows_in, w->rows_out, w->st_decode, n, &row_words)) return rc;
+    if (int rc = launch_lower(c, true, w->rows_out, row_words, w->st_decode, w->e32, w->st_lower, n)) return rc;
+    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w->e32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, oprf_make_tail(dst, dst_len), w->st_lower, w->st_zero,
                                    out64, status, (u32)n));
     return FOURQ_OK;
 }
@@ -2601,16 +2602,14 @@ FQ_API int fourq_oprf_eval_batch_dev(fourq_ctx* c, const uint64_t* key, const ui
     if (!h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) || !sig_msgs_dev_ok(msgs, stride, lens, msg_len)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    int rc = ensure_work(c, fq_work::OprfEval::bytes(n));
-    if (rc) return rc;
-    const fq_work::OprfEval w(c->work, n);
+    WORK_SCOPE(w, OprfEval, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
-    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w.u, (u32)n));
-    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w.u, w.pts, (u32)n));
-    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w.keys, (u32)n));
-    if ((rc = dh_dev(c, ENDO, w.keys, w.pts, nullptr, w.shared, w.st_dh, n))) return rc;
-    if ((rc = fourq_encode_batch_dev(c, w.shared, (uint8_t*)w.e32, n))) return rc;
-    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w.e32, m, oprf_make_tail(dst, dst_len), w.st_dh, nullptr, out64, status, (u32)n));
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w->u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w->u, w->pts, (u32)n));
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w->keys, (u32)n));
+    if (int rc = dh_dev(c, ENDO, w->keys, w->pts, nullptr, w->shared, w->st_dh, n)) return rc;
+    if (int rc = fourq_encode_batch_dev(c, w->shared, (uint8_t*)w->e32, n)) return rc;
+    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w->e32, m, oprf_make_tail(dst, dst_len), w->st_dh, nullptr, out64, status, (u32)n));
     return FOURQ_OK;
 }
 // host-pointer twins
@@ -2651,22 +2650,16 @@ FQ_API int fourq_oprf_eval_batch(fourq_ctx* c, const uint64_t* key, const uint8_
 // ---- batched DLEQ proofs (include/fourq_amd.h, "oblivious PRF: proofs"): that a batch was evaluated with the key behind pk32 ------------------
 // Every curve operation is one of the calls above -- the grouped sum (M, Z and [s]M + [c]Z), [k]B + [l]P ([s]G + [c]pk), DH_endo and MUL_endo
 // on encodings (Z = DH_endo(k, M), [r]M), the comb with its encoding ([r]G and the public key in one launch) -- and dleq.hip.h's kernels
-// hash, reduce, split and compare in between.  The inner calls carve their own layouts at the start of the work buffer; this call's regions
-// lie behind the largest of them (dleq_layout.h), and the buffer and the projective planes are sized ONCE, here, for everything the inner
-// calls will ask, so that none of them moves the buffer under a value an earlier stage has left.
+// hash, reduce, split and compare in between: a composite layout (dleq_layout.h) by work_layout.h's rule.
 // what every call asks of its context and DST; verify and reserve ask dleq_pair_ok too: verify's sum of two is a grouped sum over 2 x groups rows
 static bool dleq_args_ok(const fourq_ctx* c, const uint8_t* dst, size_t dst_len) { return c && h2c_args_ok(dst, dst_len, FOURQ_H2C_RO); }
 static bool dleq_pair_ok(size_t groups) { return groups <= FOURQ_MAX_BATCH / 2; }
-static int dleq_size(fourq_ctx* c, size_t n, size_t groups) {
-    if (int rc = ensure_proj(c, fq_work::Dleq::plane_rows(groups))) return rc;
-    return ensure_work(c, fq_work::Dleq::bytes(n, groups));
-}
 FQ_API int fourq_dleq_reserve(fourq_ctx* c, size_t groups, size_t group_size) {
     size_t n;
     const int rc = grouped_rows(c && dleq_pair_ok(groups), groups, group_size, &n);
     if (rc || !n) return rc;
     CtxGuard g(c);
-    return dleq_size(c, n, groups);
+    return size_for<fq_work::Dleq>(c, false, n, groups);
 }
 // d, then M32 = sum [d]C and (with_z) Z32 = sum [d]D with their statuses, from the public key's row at pk_dev
 static int dleq_composites_stage(fourq_ctx* c, const fq_work::Dleq& w, const OprfTail& tail, const uint8_t* pk_dev, const uint8_t* blinded32, const uint8_t* evaluated32,
@@ -2683,11 +2676,10 @@ FQ_API int fourq_dleq_composites_dev(fourq_ctx* c, const uint8_t* dst, size_t ds
                           aligned16(m32) && aligned16(z32), groups, group_size, &n);
     if (rc || !n) return rc;
     CtxGuard g(c);
-    if ((rc = dleq_size(c, n, groups))) return rc;
-    const fq_work::Dleq w(c->work, n, groups);
-    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w.pk, 1));
-    if ((rc = dleq_composites_stage(c, w, dleq_make_tail("Composite", dst, dst_len), (const uint8_t*)w.pk, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
-    HIPRC_TRY(c, dleq_launch_composites_merge(c->stream, w.st_m, w.st_z, m32, z32, status, (u32)groups));
+    WORK_SCOPE(w, Dleq, n, groups);
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w->pk, 1));
+    if ((rc = dleq_composites_stage(c, *w, dleq_make_tail("Composite", dst, dst_len), (const uint8_t*)w->pk, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
+    HIPRC_TRY(c, dleq_launch_composites_merge(c->stream, w->st_m, w->st_z, m32, z32, status, (u32)groups));
     return FOURQ_OK;
 }
 FQ_API int fourq_dleq_prove_dev(fourq_ctx* c, const uint64_t* key, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* blinded32, const uint8_t* evaluated32,
@@ -2698,18 +2690,17 @@ FQ_API int fourq_dleq_prove_dev(fourq_ctx* c, const uint64_t* key, const uint64_
     if (rc || !n) return rc;
     CtxGuard g(c);
     if ((rc = stage_comb(c, comb))) return rc;
-    if ((rc = dleq_size(c, n, groups))) return rc;
-    const fq_work::Dleq w(c->work, n, groups);
-    uint8_t *m32 = (uint8_t*)w.m32, *z32 = (uint8_t*)w.z32, *t2 = (uint8_t*)w.t2, *t3 = (uint8_t*)w.t3;
+    WORK_SCOPE(w, Dleq, n, groups);
+    uint8_t *m32 = (uint8_t*)w->m32, *z32 = (uint8_t*)w->z32, *t2 = (uint8_t*)w->t2, *t3 = (uint8_t*)w->t3;
     const uint8_t* pk_dev = t2 + 32 * groups;
     // r mod N on the groups' rows and K behind them: ONE comb launch gives every t2 and the public key
-    HIPRC_TRY(c, dleq_launch_nonces(c->stream, key, nonces, w.sc_a, (u32)groups));
-    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w.sc_b, (u32)groups));
-    if ((rc = comb_encode(c, w.sc_a, w.affine, w.st_t2, t2, groups + 1))) return rc;
-    if ((rc = dleq_composites_stage(c, w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, nullptr, false, groups, group_size))) return rc;
-    if ((rc = dh_bytes_dev(c, ENDO, w.sc_b, m32, nullptr, z32, w.st_z, groups))) return rc;                 // Z = DH_endo(k, M): D is hashed, never decoded
-    if ((rc = mul_bytes_dev(c, ENDO, w.sc_a, m32, t3, w.st_t3, groups))) return rc;                        // t3 = encode([r]M)
-    HIPRC_TRY(c, dleq_launch_prove(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), key, w.sc_a, w.st_m, w.st_z, w.st_t3, proof64, status,
+    HIPRC_TRY(c, dleq_launch_nonces(c->stream, key, nonces, w->sc_a, (u32)groups));
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w->sc_b, (u32)groups));
+    if ((rc = comb_encode(c, w->sc_a, w->affine, w->st_t2, t2, groups + 1))) return rc;
+    if ((rc = dleq_composites_stage(c, *w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, nullptr, false, groups, group_size))) return rc;
+    if ((rc = dh_bytes_dev(c, ENDO, w->sc_b, m32, nullptr, z32, w->st_z, groups))) return rc;                 // Z = DH_endo(k, M): D is hashed, never decoded
+    if ((rc = mul_bytes_dev(c, ENDO, w->sc_a, m32, t3, w->st_t3, groups))) return rc;                        // t3 = encode([r]M)
+    HIPRC_TRY(c, dleq_launch_prove(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), key, w->sc_a, w->st_m, w->st_z, w->st_t3, proof64, status,
                                    (u32)groups));
     return FOURQ_OK;
 }
@@ -2721,16 +2712,15 @@ FQ_API int fourq_dleq_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint64
     if (rc || !n) return rc;
     CtxGuard g(c);
     if ((rc = stage_comb(c, comb))) return rc;
-    if ((rc = dleq_size(c, n, groups))) return rc;
-    const fq_work::Dleq w(c->work, n, groups);
-    uint8_t *m32 = (uint8_t*)w.m32, *z32 = (uint8_t*)w.z32, *t2 = (uint8_t*)w.t2, *t3 = (uint8_t*)w.t3;
-    const uint8_t* pk_dev = (const uint8_t*)w.pk;
-    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w.pk, (u32)groups));             // pk on every group's row: the point of [s]G + [c]pk
-    if ((rc = dleq_composites_stage(c, w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
-    HIPRC_TRY(c, dleq_launch_split(c->stream, proof64, m32, z32, w.sc_a, w.sc_b, w.pair_sc, w.pair_pt, w.st_pre, (u32)groups));
-    if ((rc = double_mul_dev(c, w.sc_a, nullptr, w.sc_b, pk_dev, true, COMBINE_ENCODE, nullptr, t2, w.st_t2, nullptr, groups))) return rc;       // t2' = [s]G + [c]pk
-    if ((rc = msm_dev(c, w.pair_sc, w.pair_pt, true, t3, w.st_t3, groups, 2))) return rc;                                                     // t3' = [s]M + [c]Z
-    HIPRC_TRY(c, dleq_launch_check(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), w.sc_b, w.st_m, w.st_z, w.st_t2, w.st_pre, w.st_t3, ok, status,
+    WORK_SCOPE(w, Dleq, n, groups);
+    uint8_t *m32 = (uint8_t*)w->m32, *z32 = (uint8_t*)w->z32, *t2 = (uint8_t*)w->t2, *t3 = (uint8_t*)w->t3;
+    const uint8_t* pk_dev = (const uint8_t*)w->pk;
+    HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w->pk, (u32)groups));             // pk on every group's row: the point of [s]G + [c]pk
+    if ((rc = dleq_composites_stage(c, *w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
+    HIPRC_TRY(c, dleq_launch_split(c->stream, proof64, m32, z32, w->sc_a, w->sc_b, w->pair_sc, w->pair_pt, w->st_pre, (u32)groups));
+    if ((rc = double_mul_dev(c, w->sc_a, nullptr, w->sc_b, pk_dev, true, COMBINE_ENCODE, nullptr, t2, w->st_t2, nullptr, groups))) return rc;       // t2' = [s]G + [c]pk
+    if ((rc = msm_dev(c, w->pair_sc, w->pair_pt, true, t3, w->st_t3, groups, 2))) return rc;                                                     // t3' = [s]M + [c]Z
+    HIPRC_TRY(c, dleq_launch_check(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), w->sc_b, w->st_m, w->st_z, w->st_t2, w->st_pre, w->st_t3, ok, status,
                                    (u32)groups));
     return FOURQ_OK;
 }
@@ -2773,9 +2763,7 @@ FQ_API int fourq_dleq_verify(fourq_ctx* c, const uint8_t* pk32, const uint64_t* 
 // ---- verifiable random function (include/fourq_amd.h, "verifiable random function"): prove, verify, proof_to_hash under SchnorrQ keys ------
 // Every curve operation is one of the calls above -- the Elligator map, MUL_endo on encodings (Gamma = [x]Hpt, [r]Hpt), the comb with its
 // encoding ([r]G), [k]B + [l]P or its keyed sibling ([s]G + [c]Y), the grouped sum over groups of two ([s]Hpt + [c / 392]W) -- and
-// vrf.hip.h's kernels hash, reduce, clear Gamma's cofactor, split and compare in between.  As the DLEQ proofs: the inner calls carve their own
-// layouts at the start of the work buffer, this call's regions lie behind the largest of them (vrf_layout.h), and the buffer and the
-// projective planes are sized ONCE per call for everything the inner calls will ask.
+// vrf.hip.h's kernels hash, reduce, clear Gamma's cofactor, split and compare in between.  As the DLEQ proofs, a composite layout (vrf_layout.h).
 static bool vrf_args_ok(const fourq_ctx* c, const uint8_t* dst, size_t dst_len) { return c && h2c_args_ok(dst, dst_len, FOURQ_H2C_RO); }
 static bool vrf_pair_ok(size_t n) { return n <= FOURQ_MAX_BATCH / 2; }        // verify's sum of two is a grouped sum over 2 n rows
 FQ_API int fourq_vrf_reserve(fourq_ctx* c, size_t n) {
@@ -2798,15 +2786,14 @@ FQ_API int fourq_vrf_prove_dev(fourq_ctx* c, const uint8_t* sk32, const uint8_t*
     CtxGuard g(c);
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::Vrf>(c, n))) return rc;
-    const fq_work::Vrf w(c->work, n);
-    uint8_t *h32 = (uint8_t*)w.h32, *g32 = (uint8_t*)w.g32, *t_u = (uint8_t*)w.u32, *t_v = (uint8_t*)w.v32;
-    if ((rc = vrf_hash_stage(c, w, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, dst, dst_len, n))) return rc;
-    HIPRC_TRY(c, vrf_launch_scalars(c->stream, sk32, h32, w.sc_a, w.sc_b, (u32)n));                          // x and r
-    if ((rc = comb_encode(c, w.sc_b, w.affine, w.st_u, t_u, n))) return rc;                                // u32 = encode([r]G)
-    if ((rc = mul_bytes_dev(c, ENDO, w.sc_a, h32, g32, w.st_a, n))) return rc;                             // gamma32 = encode([x]Hpt)
-    if ((rc = mul_bytes_dev(c, ENDO, w.sc_b, h32, t_v, w.st_b, n))) return rc;                             // v32 = encode([r]Hpt)
-    HIPRC_TRY(c, vrf_launch_prove(c->stream, pk32, h32, g32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), w.sc_a, w.sc_b, proof96, (u32)n));
+    WORK_SCOPE(w, Vrf, n);
+    uint8_t *h32 = (uint8_t*)w->h32, *g32 = (uint8_t*)w->g32, *t_u = (uint8_t*)w->u32, *t_v = (uint8_t*)w->v32;
+    if ((rc = vrf_hash_stage(c, *w, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, dst, dst_len, n))) return rc;
+    HIPRC_TRY(c, vrf_launch_scalars(c->stream, sk32, h32, w->sc_a, w->sc_b, (u32)n));                          // x and r
+    if ((rc = comb_encode(c, w->sc_b, w->affine, w->st_u, t_u, n))) return rc;                                // u32 = encode([r]G)
+    if ((rc = mul_bytes_dev(c, ENDO, w->sc_a, h32, g32, w->st_a, n))) return rc;                             // gamma32 = encode([x]Hpt)
+    if ((rc = mul_bytes_dev(c, ENDO, w->sc_b, h32, t_v, w->st_b, n))) return rc;                             // v32 = encode([r]Hpt)
+    HIPRC_TRY(c, vrf_launch_prove(c->stream, pk32, h32, g32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), w->sc_a, w->sc_b, proof96, (u32)n));
     return FOURQ_OK;
 }
 // Both verify calls.  key_ids == NULL: the keys are the rows of pk32.  Otherwise the rows' key bytes are gathered by index (the hashes read
@@ -2823,24 +2810,23 @@ static int vrf_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint32_t* key
     if (key_ids && c->keyset_count == 0) return FOURQ_ERR_INVALID;
     int rc = stage_comb(c, comb);
     if (rc) return rc;
-    if ((rc = reserve_for<fq_work::Vrf>(c, n))) return rc;
-    const fq_work::Vrf w(c->work, n);
-    uint8_t *h32 = (uint8_t*)w.h32, *w32 = (uint8_t*)w.g32, *t_u = (uint8_t*)w.u32, *t_v = (uint8_t*)w.v32;
+    WORK_SCOPE(w, Vrf, n);
+    uint8_t *h32 = (uint8_t*)w->h32, *w32 = (uint8_t*)w->g32, *t_u = (uint8_t*)w->u32, *t_v = (uint8_t*)w->v32;
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
     const u32 count = (u32)c->keyset_count;
     if (key_ids) {
-        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, (uint8_t*)w.pk32, (u32)n));
-        pk32 = (const uint8_t*)w.pk32;
+        HIPRC_TRY(c, chain_launch_keyset_gather(c->stream, key_ids, c->keyset_bytes, count, (uint8_t*)w->pk32, (u32)n));
+        pk32 = (const uint8_t*)w->pk32;
     }
-    if ((rc = vrf_hash_stage(c, w, pk32, m, dst, dst_len, n))) return rc;
-    HIPRC_TRY(c, vrf_launch_gamma(c->stream, proof96, h32, w.g32, w.sc_a, w.sc_b, w.pair_sc, w.pair_pt, w.st_a, w.st_pre, (u32)n));
-    if (key_ids && !c->ct) rc = fourq_keyset_double_mul_bytes_dev(c, w.sc_a, nullptr, w.sc_b, key_ids, t_u, w.st_u, n);                  // u32' = [s]G + [c]A_id
-    else rc = double_mul_dev(c, w.sc_a, nullptr, w.sc_b, pk32, true, COMBINE_ENCODE, nullptr, t_u, w.st_u, nullptr, n);                 // u32' = [s]G + [c]Y
+    if ((rc = vrf_hash_stage(c, *w, pk32, m, dst, dst_len, n))) return rc;
+    HIPRC_TRY(c, vrf_launch_gamma(c->stream, proof96, h32, w->g32, w->sc_a, w->sc_b, w->pair_sc, w->pair_pt, w->st_a, w->st_pre, (u32)n));
+    if (key_ids && !c->ct) rc = fourq_keyset_double_mul_bytes_dev(c, w->sc_a, nullptr, w->sc_b, key_ids, t_u, w->st_u, n);                  // u32' = [s]G + [c]A_id
+    else rc = double_mul_dev(c, w->sc_a, nullptr, w->sc_b, pk32, true, COMBINE_ENCODE, nullptr, t_u, w->st_u, nullptr, n);                 // u32' = [s]G + [c]Y
     if (rc) return rc;
-    if ((rc = msm_dev(c, w.pair_sc, w.pair_pt, true, t_v, w.st_v, n, 2))) return rc;                                                   // v32' = [s]Hpt + [c / 392]W
+    if ((rc = msm_dev(c, w->pair_sc, w->pair_pt, true, t_v, w->st_v, n, 2))) return rc;                                                   // v32' = [s]Hpt + [c / 392]W
     const VrfKeys set = { key_ids, c->keyset_status, count };
-    HIPRC_TRY(c, vrf_launch_check(c->stream, pk32, h32, proof96, w32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), dleq_make_tail("VrfOutput", dst, dst_len), w.sc_b, set, m,
-                                  w.st_u, w.st_a, w.st_pre, w.st_v, beta64, ok, status, (u32)n));
+    HIPRC_TRY(c, vrf_launch_check(c->stream, pk32, h32, proof96, w32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), dleq_make_tail("VrfOutput", dst, dst_len), w->sc_b, set, m,
+                                  w->st_u, w->st_a, w->st_pre, w->st_v, beta64, ok, status, (u32)n));
     return FOURQ_OK;
 }
 FQ_API int fourq_vrf_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint64_t* comb, const uint8_t* dst, size_t dst_len, const uint8_t* msgs, size_t stride, const uint32_t* lens,

@@ -86,7 +86,7 @@ struct ShapePlan {
 // than Msm's n / 2 where many groups are short or empty -- and level 2 at most groups + (groups + n / 64) / 64; from level 1 on a pass never
 // makes a level longer, so the later passes alternate between the same two regions.  The ladder's regions hold at least ONE row and one
 // status byte even where n == 0: the lanes of a team whose count is 0 read row 0 of the level below (and discard it), as every idle lane does.
-struct MsmRagged {
+struct MsmRagged : Leaf {
     uint64_t *rows_in, *rows_out;   // as MulRows
     uint8_t* st_decode;
     uint64_t *part_a, *part_b;      // levels 1, 3, ... and 2, 4, ...: rows of 12 words
@@ -102,7 +102,6 @@ struct MsmRagged {
         part_b = w.take<uint64_t>(level2(n, groups) * 12); st_b = w.take_status(level2(n, groups));
         end = w.used;
     }
-    static constexpr bool planes = false;
     static size_t bytes(size_t n, size_t groups) { return MsmRagged(nullptr, n, groups).end; }
 };
 

@@ -1,6 +1,6 @@
 // prints the work-buffer layout of the DLEQ proof calls for n rows in `groups` groups: ./dleq_layout_dump n groups  ->  lines
-// "own.region offset", "inner.layout total" (what each inner call's own layout takes at the size it is called with), "inner_bytes total"
-// and "bytes total"
+// "own.region offset", "inner.layout total" (what each inner call's own layout takes at the size it is called with), "inner_bytes total",
+// "inner_extent value" (the bytes from the buffer's start that the layout admits for its inner calls) and "bytes total"
 #include <cstdio>
 #include <cstdlib>
 #include "dleq_layout.h"
@@ -17,5 +17,6 @@ int main(int argc, char** argv) {
     printf("inner.msm_rows %zu\ninner.msm_pair %zu\ninner.double_mul %zu\ninner.evaluate %zu\ninner.mul_rows %zu\ninner.sig %zu\n", Msm::bytes(n), Msm::bytes(2 * groups),
            DoubleMul::bytes(groups), OprfEvaluate::bytes(groups), MulRows::bytes(groups), Sig::bytes(groups + 1));
     printf("inner_bytes %zu\nbytes %zu\nplane_rows %zu\n", DleqInner::bytes(n, groups), Dleq::bytes(n, groups), Dleq::plane_rows(groups));
+    printf("inner_extent %zu\n", Dleq::inner_extent(n, groups));
     return 0;
 }

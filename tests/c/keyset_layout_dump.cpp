@@ -1,5 +1,6 @@
 // prints the work-buffer layout of the calls over registered keys: ./keyset_layout_dump n  ->  lines "own.region offset", "inner bytes" (what
-// the existing routes carve at the buffer's first byte in constant-time mode) and "bytes total"
+// the existing routes carve at the buffer's first byte in constant-time mode), "bytes total", "inner_extent value" (what the layout admits for
+// its inner calls) and, of the two layouts those calls carve, "sig_verify.bytes", "sig_verify.inner_extent" and "double_mul.lent"
 #include <cstdio>
 #include <cstdlib>
 #include "keyset_layout.h"
@@ -14,5 +15,6 @@ int main(int argc, char** argv) {
     REGION(w, inner); REGION(w, s); REGION(w, h); REGION(w, r32); REGION(w, rows); REGION(w, pk32); REGION(w, pre);
     printf("inner %zu\n", DoubleMul::bytes(n));
     printf("bytes %zu\n", Keyset::bytes(n));
+    printf("inner_extent %zu\nsig_verify.bytes %zu\nsig_verify.inner_extent %zu\ndouble_mul.lent %zu\n", Keyset::inner_extent(n), SigVerify::bytes(n), SigVerify::inner_extent(n), DoubleMul::lent(n));
     return 0;
 }

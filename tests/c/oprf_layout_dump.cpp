@@ -1,5 +1,6 @@
 // prints the work-buffer layouts of the four oblivious-PRF calls for n elements: ./oprf_layout_dump n  ->  lines "layout.region offset",
-// "layout.bytes total" and "sig_verify_bytes total" (the layout that has sized fourq_ctx_reserve so far)
+// "layout.bytes total", "sig_verify_bytes total" (the layout that has sized fourq_ctx_reserve so far) and "layout_inner_extent value" (the
+// bytes from the buffer's start that the layout admits for its inner calls)
 #include <cstdio>
 #include <cstdlib>
 #include "work_layout.h"
@@ -21,5 +22,7 @@ int main(int argc, char** argv) {
     REGION("eval", d, pts); REGION("eval", d, shared); REGION("eval", d, u); REGION("eval", d, keys); REGION("eval", d, e32); REGION("eval", d, st_dh);
     printf("blind.bytes %zu\nevaluate.bytes %zu\nfinalize.bytes %zu\neval.bytes %zu\n", OprfBlind::bytes(n), OprfEvaluate::bytes(n), OprfFinalize::bytes(n), OprfEval::bytes(n));
     printf("dh_bytes_bytes %zu\nsig_verify_bytes %zu\n", DhBytes::bytes(n), SigVerify::bytes(n));
+    printf("blind_inner_extent %zu\nevaluate_inner_extent %zu\nfinalize_inner_extent %zu\neval_inner_extent %zu\n", OprfBlind::inner_extent(n), OprfEvaluate::inner_extent(n),
+           OprfFinalize::inner_extent(n), OprfEval::inner_extent(n));
     return 0;
 }

@@ -1,5 +1,5 @@
 // prints the work-buffer layout of the VRF calls for n rows: ./vrf_layout_dump n  ->  lines "own.region offset", "inner.layout total" (what
-// each inner call's own layout takes at the size it is called with), "inner_bytes total" and "bytes total"
+// each inner call's own layout takes at the size it is called with), "inner_bytes total", "inner_extent value" (the bytes from the buffer's start that the layout admits for its inner calls) and "bytes total"
 #include <cstdio>
 #include <cstdlib>
 #include "vrf_layout.h"
@@ -15,5 +15,6 @@ int main(int argc, char** argv) {
     REGION(w, pair_sc); REGION(w, pair_pt); REGION(w, st_a); REGION(w, st_b); REGION(w, st_u); REGION(w, st_v); REGION(w, st_pre);
     printf("inner.mul_rows %zu\ninner.double_mul %zu\ninner.keyset %zu\ninner.msm_pair %zu\n", MulRows::bytes(n), DoubleMul::bytes(n), Keyset::bytes(n), Msm::bytes(2 * n));
     printf("inner_bytes %zu\nbytes %zu\nplanes %d\n", VrfInner::bytes(n), Vrf::bytes(n), Vrf::planes ? 1 : 0);
+    printf("inner_extent %zu\n", Vrf::inner_extent(n));
     return 0;
 }

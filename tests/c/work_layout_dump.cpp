@@ -1,5 +1,6 @@
 // prints every work-buffer layout for n elements: ./work_layout_dump n  ->  lines "layout region offset" and "layout bytes total", then the
-// list of all layouts as the header has it: "list Struct total" per member and "list max_bytes value"
+// list of all layouts as the header has it: "list Struct total" per member and "list max_bytes value"; then "extent layout value", the bytes
+// from the buffer's start that the layout admits for its inner calls, and "lent layout value", the tail of its total that its caller carves
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,5 +28,9 @@ int main(int argc, char** argv) {
     printf("dh_bytes bytes %zu\nexchange bytes %zu\nmul_rows bytes %zu\ndouble_mul bytes %zu\nsig_verify bytes %zu\nsig bytes %zu\nh2c bytes %zu\n",
            DhBytes::bytes(n), Exchange::bytes(n), MulRows::bytes(n), DoubleMul::bytes(n), SigVerify::bytes(n), Sig::bytes(n), H2c::bytes(n));
     list_all(All(), n);
+    printf("extent dh_bytes %zu\nextent exchange %zu\nextent mul_rows %zu\nextent double_mul %zu\nextent sig_verify %zu\nextent sig %zu\nextent h2c %zu\n",
+           DhBytes::inner_extent(n), Exchange::inner_extent(n), MulRows::inner_extent(n), DoubleMul::inner_extent(n), SigVerify::inner_extent(n), Sig::inner_extent(n), H2c::inner_extent(n));
+    printf("lent dh_bytes %zu\nlent exchange %zu\nlent mul_rows %zu\nlent double_mul %zu\nlent sig_verify %zu\nlent sig %zu\nlent h2c %zu\n",
+           DhBytes::lent(n), Exchange::lent(n), MulRows::lent(n), DoubleMul::lent(n), SigVerify::lent(n), Sig::lent(n), H2c::lent(n));
     return 0;
 }

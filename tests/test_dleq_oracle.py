@@ -213,7 +213,7 @@ def layout(tmp_path_factory):
 def test_dleq_regions_are_aligned_disjoint_behind_the_inner_layouts_and_end_at_the_total(layout, n, one_group):
     groups = 1 if one_group else n
     offs = layout(n, groups)
-    total, inner_bytes, plane_rows = offs.pop("bytes"), offs.pop("inner_bytes"), offs.pop("plane_rows")
+    total, inner_bytes, plane_rows, inner_extent = offs.pop("bytes"), offs.pop("inner_bytes"), offs.pop("plane_rows"), offs.pop("inner_extent")
     inner = {k.split(".")[1]: v for k, v in offs.items() if k.startswith("inner.")}
     own = {k.split(".")[1]: v for k, v in offs.items() if k.startswith("own.")}
     assert own.pop("inner") == 0
@@ -230,3 +230,8 @@ def test_dleq_regions_are_aligned_disjoint_behind_the_inner_layouts_and_end_at_t
         assert end <= off, (name, nxt)
     assert spans[-1][1] == total == inner_bytes + sum(f(n, groups) for f in OWN.values())      # ... and end at bytes()
     assert plane_rows == groups + 1
+    # what the layout admits for its inner calls (work_layout.h, the rule) is the offset of its first own region, and holds every layout an
+    # inner call carves at the size it is called with -- INNER restates who is called with what from fourq_amd.hip: the grouped sum over n
+    # rows and over 2 x groups, [s]G + [c]pk, DH_endo and MUL_endo over `groups` rows, the comb with its encoding over groups + 1
+    assert inner_extent == spans[0][0] == own["d"]
+    assert all(inner_extent >= f(n, groups) for f in INNER.values())

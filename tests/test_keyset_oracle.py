@@ -146,3 +146,9 @@ def test_keyset_regions_are_aligned_disjoint_and_never_shrink(layout):
         assert got["bytes"] >= before
         before = got["bytes"]
         assert layout(n + 1)["bytes"] >= got["bytes"]
+        # what the layout admits for its inner calls (work_layout.h, the rule) is the offset of its first own region.  Restated from
+        # fourq_amd.hip, the constant-time routes call [k]B + [l]P over n rows, and the signature check over n rows, which calls it in turn
+        # within ITS inner extent: the double multiplication's layout without the tail it lends the signature check
+        assert got["inner_extent"] == offs["s"]
+        assert got["inner_extent"] >= got["inner"] and got["inner_extent"] >= got["sig_verify.bytes"]
+        assert got["sig_verify.inner_extent"] >= got["inner"] - got["double_mul.lent"] == 320 * n + 2 * a256(n)

@@ -151,6 +151,10 @@ def test_oprf_regions_are_aligned_disjoint_and_end_at_the_total(layout, n):
     offs = layout(n)
     sig_verify, dh_bytes = offs.pop("sig_verify_bytes"), offs.pop("dh_bytes_bytes")
     assert dh_bytes == NEED["evaluate"]["dh"](n)
+    # what a layout admits for the calls its call makes (work_layout.h, the rule): evaluate calls DH_endo on encodings over n rows (restated
+    # from fourq_amd.hip), which carves DhBytes; the other three make no call with a layout of its own
+    extent = {call: offs.pop(call + "_inner_extent") for call in NEED}
+    assert extent == {"blind": 0, "evaluate": offs["evaluate.keys"], "finalize": 0, "eval": 0} and extent["evaluate"] >= dh_bytes
     for call, need in NEED.items():
         mine = {k.split(".")[1]: v for k, v in offs.items() if k.startswith(call + ".")}
         total = mine.pop("bytes")

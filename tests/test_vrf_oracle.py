@@ -238,7 +238,7 @@ def layout(tmp_path_factory):
 @pytest.mark.parametrize("n", [1, 2, 255, 256, 257, 4095, 65537, 0xffffff00 // 2])
 def test_vrf_regions_are_aligned_disjoint_behind_the_inner_layouts_and_end_at_the_total(layout, n):
     offs = layout(n)
-    total, inner_bytes, planes = offs.pop("bytes"), offs.pop("inner_bytes"), offs.pop("planes")
+    total, inner_bytes, planes, inner_extent = offs.pop("bytes"), offs.pop("inner_bytes"), offs.pop("planes"), offs.pop("inner_extent")
     inner = {k.split(".")[1]: v for k, v in offs.items() if k.startswith("inner.")}
     own = {k.split(".")[1]: v for k, v in offs.items() if k.startswith("own.")}
     assert own.pop("inner") == 0
@@ -255,3 +255,8 @@ def test_vrf_regions_are_aligned_disjoint_behind_the_inner_layouts_and_end_at_th
         assert end <= off, (name, nxt)
     assert spans[-1][1] == total == inner_bytes + sum(f(n) for f in OWN.values())      # ... and end at bytes(), what fourq_vrf_reserve sizes
     assert planes == 1
+    # what the layout admits for its inner calls (work_layout.h, the rule) is the offset of its first own region, and holds every layout an
+    # inner call carves at the size it is called with -- INNER restates who is called with what from fourq_amd.hip: MUL_endo on encodings,
+    # [s]G + [c]Y and its keyed sibling over n rows, the grouped sum over 2 n
+    assert inner_extent == spans[0][0] == own["u"]
+    assert all(inner_extent >= f(n) for f in INNER.values())

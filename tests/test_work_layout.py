@@ -46,14 +46,17 @@ def layouts(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("work_layout") / "work_layout_dump")
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "fourq_amd", "csrc"),
                     os.path.join(ROOT, "tests", "c", "work_layout_dump.cpp"), "-o", exe], check=True)
-    cache = {}
+    cache, shared = {}, {}
 
     def run(n):
         if n not in cache:
             regions, totals, listed = {}, {}, {}
+            shared[n] = {"extent": {}, "lent": {}}
             for line in subprocess.run([exe, str(n)], check=True, capture_output=True, text=True).stdout.splitlines():
                 layout, name, value = line.split()
-                if layout == "list":                  # the header's list of all layouts: struct name -> total, and "max_bytes"
+                if layout in ("extent", "lent"):      # how the layout shares the buffer with the calls its call makes: layout -> bytes
+                    shared[n][layout][name] = int(value)
+                elif layout == "list":                # the header's list of all layouts: struct name -> total, and "max_bytes"
                     listed[name] = int(value)
                 elif name == "bytes":
                     totals[layout] = int(value)
@@ -61,6 +64,7 @@ def layouts(tmp_path_factory):
                     regions.setdefault(layout, {})[name] = int(value)
             cache[n] = (regions, totals, listed)
         return cache[n]
+    run.shared = lambda n: (run(n), shared[n])[1]
     return run
 
 
@@ -92,6 +96,32 @@ def test_totals_are_the_formulas_the_library_allocated_by(layouts, n):
     # two offsets the kernels' callers have always used
     assert regions["mul_rows"]["st_decode"] == 2 * n * 160 + n * 64
     assert regions["sig"]["affine"] == 3 * n * 32
+
+
+# who calls whom with a work layout of its own, restated from fourq_amd.hip: composite -> [(inner layout, the size it is called with)]
+CALLS = {"sig_verify": [("double_mul", lambda n: n)]}
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_the_inner_extent_is_the_first_own_region_and_holds_every_inner_call(layouts, n):
+    """The bytes from the buffer's start that a layout admits for the calls its call makes (work_layout.h, the rule): nothing for a layout
+    whose call makes none, the offset of the first own region for a composite -- here the signature check, whose own regions are the tail
+    -- and at least what every inner call carves at the size it is called with.  The double multiplication's total includes that very tail,
+    which it lends to the signature check and never touches: nested, it has to fit without it, and that is exactly the extent."""
+    regions, totals, _ = layouts(n)
+    extent, lent = layouts.shared(n)["extent"], layouts.shared(n)["lent"]
+    assert set(extent) == set(lent) == set(NEED)
+    for layout in NEED:
+        assert extent[layout] == (regions["sig_verify"]["sig.s"] if layout == "sig_verify" else 0), layout
+        assert lent[layout] == (3 * n * 32 + a(n) if layout == "double_mul" else 0), layout
+    assert lent["double_mul"] == totals["double_mul"] - regions["double_mul"]["tail"] == NEED["double_mul"]["tail"](n)
+    for outer, inner_calls in CALLS.items():
+        for inner, size in inner_calls:
+            m = size(n)
+            inner_regions, inner_totals, _ = layouts(m)
+            assert extent[outer] >= inner_totals[inner] - layouts.shared(m)["lent"][inner], (outer, inner)
+            # ... and nothing the inner call reads or writes lies outside it
+            assert all(off + NEED[inner][name](m) <= extent[outer] for name, off in inner_regions[inner].items() if name != "tail"), (outer, inner)
 
 
 @pytest.mark.parametrize("n", SIZES)
