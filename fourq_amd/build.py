@@ -58,16 +58,15 @@ RESOURCE_POLICY = [
     (r"\bcommit_kernel<", "occupancy", lambda v: v >= 4, "the staged commitment comb runs 1 024-lane blocks (four waves per SIMD), the gather and constant-time ones four 256-lane blocks per CU"),
     (r"\bkeyset_comb_kernel\(", "scratch", lambda v: v == 0, "the keyed comb is the gather commitment comb with two tables under shared doublings: nothing may spill"),
     (r"\bkeyset_comb_kernel\(", "occupancy", lambda v: v >= 4, "the keyed comb hides its gathers behind other waves, as the gather commitment comb: four 256-lane blocks per CU"),
-    (r"\bsig_challenge_keyed_kernel\(", "scratch", lambda v: v == 0, "the keyed challenge is the challenge kernel with its key row fetched by index: a hashing kernel, nothing may spill"),
-    (r"\bsig_challenge_keyed_kernel\(", "occupancy", lambda v: v >= 4, "the keyed challenge is throughput code held to 128 VGPRs, as the other hashing kernels: four waves per SIMD"),
     (r"\bkeyset_order_kernel\(", "scratch", lambda v: v == 0, "the order check is one chain of doublings and additions per key: its point and the key's table entry stay in registers"),
     (r"\b(sha512_kernel|sig_challenge_kernel|sig_nonce_kernel<\w+>|sig_finish_kernel)\(", "scratch", lambda v: v == 0,
-     "the hashing kernels hold 40 live 64-bit values: state, schedule, working variables, prefix -- nothing of it may spill"),
+     "the hashing kernels hold 40 live 64-bit values: state, schedule, working variables, prefix -- nothing of it may spill (the challenge kernel fetches its key row by index for a registered key set)"),
     (r"\b(sha512_kernel|sig_challenge_kernel|sig_nonce_kernel<\w+>|sig_finish_kernel)\(", "occupancy", lambda v: v >= 4,
      "the hashing kernels are throughput code held to 128 VGPRs: four waves per SIMD"),
     (r"\b(h2f_kernel|ell2_kernel)<", "scratch", lambda v: v == 0, "hash to curve: neither the hashing nor the map may spill (DST_prime is read from the kernel arguments, not copied)"),
-    (r"\bh2f_kernel<1>", "occupancy", lambda v: v >= 4, "hash_to_field for one element is a hashing kernel like the signature layer's: four waves per SIMD"),
-    (r"\bh2f_kernel<2>", "occupancy", lambda v: v >= 3, "hash_to_field for two elements keeps b_0 live across b_1: 48 64-bit values, three waves per SIMD"),
+    (r"\bh2f_kernel<1, \w+>", "occupancy", lambda v: v >= 4, "hash_to_field for one element is a hashing kernel like the signature layer's: four waves per SIMD"),
+    (r"\bh2f_kernel<2, \w+>", "occupancy", lambda v: v >= 3,
+     "hash_to_field for two elements keeps b_0 live across b_1: 48 64-bit values, three waves per SIMD, with the VRF's key row in front of the message or without"),
     (r"\bell2_kernel<", "occupancy", lambda v: v >= 2, "the map runs the generated GF(p^2) bodies, whose temporaries are fixed high registers: two waves per SIMD"),
     (r"\boprf_final_kernel\(", "scratch", lambda v: v == 0, "the finalisation hash is a hashing kernel like the signature layer's (the tail is read from the kernel arguments, not copied)"),
     (r"\boprf_final_kernel\(", "occupancy", lambda v: v >= 4, "the finalisation hash is throughput code held to 128 VGPRs: four waves per SIMD"),
@@ -75,10 +74,9 @@ RESOURCE_POLICY = [
      "the proofs' hashing kernels load their rows into the message schedule of the block they belong to: only the state lives across a compression, nothing may spill"),
     (r"\b(dleq_composite_kernel|dleq_prove_kernel|dleq_check_kernel)\(", "occupancy", lambda v: v >= 4,
      "the proofs' hashing kernels are throughput code held to 128 VGPRs, as the finalisation hash: four waves per SIMD"),
-    (r"\b(vrf_scalar_kernel|vrf_prove_kernel|vrf_check_kernel|vrf_h2f_kernel)\(", "scratch", lambda v: v == 0,
+    (r"\b(vrf_scalar_kernel|vrf_prove_kernel|vrf_check_kernel)\(", "scratch", lambda v: v == 0,
      "the VRF's hashing kernels load their rows into the message schedule of the block they belong to, as the proofs': nothing may spill"),
     (r"\b(vrf_scalar_kernel|vrf_prove_kernel|vrf_check_kernel)\(", "occupancy", lambda v: v >= 4, "the VRF's hashing kernels are throughput code held to 128 VGPRs: four waves per SIMD"),
-    (r"\bvrf_h2f_kernel\(", "occupancy", lambda v: v >= 3, "hash_to_field of pk32 || alpha is h2f_kernel<2> with a row in front: three waves per SIMD"),
     (r"\bsc_inv_kernel<", "scratch", lambda v: v == 0, "the inversion modulo N keeps its window table and its K - 1 prefix products in registers across the chain, at every K"),
 ]
 

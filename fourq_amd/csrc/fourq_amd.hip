@@ -2300,7 +2300,7 @@ FQ_API int fourq_sig_verify_batch_dev(fourq_ctx* c, const uint8_t* pk32, const u
     if (rc) return rc;
     WORK_SCOPE(scope, SigVerify, n);
     const fq_work::SigTail& w = scope->sig;
-    HIPRC_TRY(c, sig_launch_challenge(c->stream, pk32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w.s, w.h, w.r32, w.pre, (u32)n));
+    HIPRC_TRY(c, sig_launch_challenge(c->stream, KeyRows{ nullptr, pk32, nullptr, 0 }, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w.s, w.h, w.r32, w.pre, (u32)n));
     if ((rc = double_mul_dev(c, w.s, nullptr, w.h, pk32, true, COMBINE_VERIFY, (const uint8_t*)w.r32, nullptr, status, ok, n))) return rc;
     HIPRC_TRY(c, sig_launch_merge(c->stream, w.pre, ok, status, (u32)n));
     return FOURQ_OK;
@@ -2438,8 +2438,8 @@ FQ_API int fourq_keyset_sig_verify_dev(fourq_ctx* c, const uint32_t* key_ids, co
         HIPRC_TRY(c, chain_launch_keyset_fix(c->stream, key_ids, c->keyset_status, count, nullptr, ok, status, (u32)n));
         return FOURQ_OK;
     }
-    HIPRC_TRY(c, sig_launch_challenge_keyed(c->stream, key_ids, c->keyset_bytes, c->keyset_status, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w->s, w->h, w->r32,
-                                            w->pre, (u32)n));
+    HIPRC_TRY(c, sig_launch_challenge(c->stream, KeyRows{ key_ids, c->keyset_bytes, c->keyset_status, count }, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sig64, w->s, w->h, w->r32,
+                                      w->pre, (u32)n));
     HIPRC_TRY(c, chain_launch_keyset_comb(c->stream, w->s, w->h, key_ids, c->comb_limbs, c->keyset_combs, c->keyset_status, count, w->rows, nullptr, (u32)n));
     HIPRC_TRY(c, chain_launch_keyset_lower(c->stream, true, w->rows, w->pre, w->r32, nullptr, ok, status, (u32)n));
     return FOURQ_OK;
@@ -2479,7 +2479,7 @@ FQ_API int fourq_hash_to_field_batch_dev(fourq_ctx* c, const uint8_t* dst, size_
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
     const int count = mode == FOURQ_H2C_RO ? 2 : 1;
-    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), out_u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, nullptr, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), out_u, (u32)n));
     return FOURQ_OK;
 }
 FQ_API int fourq_map_to_curve_batch_dev(fourq_ctx* c, const uint64_t* u, uint64_t* out_affine, size_t n) {
@@ -2496,7 +2496,7 @@ static int hash_to_curve_dev(fourq_ctx* c, const uint8_t* dst, size_t dst_len, i
     CtxGuard g(c);
     WORK_SCOPE(w, H2c, n);
     const int count = mode == FOURQ_H2C_RO ? 2 : 1;
-    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), w->u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, count, nullptr, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, h2c_make_dst(dst, dst_len, count), w->u, (u32)n));
     HIPRC_TRY(c, h2c_launch_ell2(c->stream, count, out_kind, w->u, (uint64_t*)out, (u32)n));
     return FOURQ_OK;
 }
@@ -2564,7 +2564,7 @@ FQ_API int fourq_oprf_blind_batch_dev(fourq_ctx* c, const uint8_t* dst, size_t d
     CtxGuard g(c);
     WORK_SCOPE(w, OprfBlind, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
-    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w->u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, nullptr, m, h2c_make_dst(dst, dst_len, 2), w->u, (u32)n));
     HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w->u, w->pts, (u32)n));
     HIP_TRY(c, hipMemsetAsync(w->st_decode, 0, n, c->stream));              // the lowering reads a decode code per row: these points were never decoded
     u32 row_words;
@@ -2592,7 +2592,7 @@ FQ_API int fourq_oprf_finalize_batch_dev(fourq_ctx* c, const uint8_t* dst, size_
     u32 row_words;
     if (int rc = mul_rows_dev(c, ENDO, w->inv, evaluated32, true, w->rows_in, w->rows_out, w->st_decode, n, &row_words)) return rc;
     if (int rc = launch_lower(c, true, w->rows_out, row_words, w->st_decode, w->e32, w->st_lower, n)) return rc;
-    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w->e32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, oprf_make_tail(dst, dst_len), w->st_lower, w->st_zero,
+    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w->e32, SigMsgs{ msgs, stride, lens, (uint32_t)msg_len }, sha_make_tail("Finalize", 8, dst, dst_len), w->st_lower, w->st_zero,
                                    out64, status, (u32)n));
     return FOURQ_OK;
 }
@@ -2604,12 +2604,12 @@ FQ_API int fourq_oprf_eval_batch_dev(fourq_ctx* c, const uint64_t* key, const ui
     CtxGuard g(c);
     WORK_SCOPE(w, OprfEval, n);
     const SigMsgs m{ msgs, stride, lens, (uint32_t)msg_len };
-    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, m, h2c_make_dst(dst, dst_len, 2), w->u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, nullptr, m, h2c_make_dst(dst, dst_len, 2), w->u, (u32)n));
     HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_AFFINE, w->u, w->pts, (u32)n));
     HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w->keys, (u32)n));
     if (int rc = dh_dev(c, ENDO, w->keys, w->pts, nullptr, w->shared, w->st_dh, n)) return rc;
     if (int rc = fourq_encode_batch_dev(c, w->shared, (uint8_t*)w->e32, n)) return rc;
-    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w->e32, m, oprf_make_tail(dst, dst_len), w->st_dh, nullptr, out64, status, (u32)n));
+    HIPRC_TRY(c, oprf_launch_final(c->stream, (const uint8_t*)w->e32, m, sha_make_tail("Finalize", 8, dst, dst_len), w->st_dh, nullptr, out64, status, (u32)n));
     return FOURQ_OK;
 }
 // host-pointer twins
@@ -2662,7 +2662,7 @@ FQ_API int fourq_dleq_reserve(fourq_ctx* c, size_t groups, size_t group_size) {
     return size_for<fq_work::Dleq>(c, false, n, groups);
 }
 // d, then M32 = sum [d]C and (with_z) Z32 = sum [d]D with their statuses, from the public key's row at pk_dev
-static int dleq_composites_stage(fourq_ctx* c, const fq_work::Dleq& w, const OprfTail& tail, const uint8_t* pk_dev, const uint8_t* blinded32, const uint8_t* evaluated32,
+static int dleq_composites_stage(fourq_ctx* c, const fq_work::Dleq& w, const ShaTail& tail, const uint8_t* pk_dev, const uint8_t* blinded32, const uint8_t* evaluated32,
                                  uint8_t* m32, uint8_t* z32, bool with_z, size_t groups, size_t group_size) {
     const size_t n = groups * group_size;
     HIPRC_TRY(c, dleq_launch_composite(c->stream, pk_dev, blinded32, evaluated32, tail, w.d, (u32)group_size, (u32)n));
@@ -2678,7 +2678,7 @@ FQ_API int fourq_dleq_composites_dev(fourq_ctx* c, const uint8_t* dst, size_t ds
     CtxGuard g(c);
     WORK_SCOPE(w, Dleq, n, groups);
     HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w->pk, 1));
-    if ((rc = dleq_composites_stage(c, *w, dleq_make_tail("Composite", dst, dst_len), (const uint8_t*)w->pk, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
+    if ((rc = dleq_composites_stage(c, *w, sha_make_tail("Composite", DLEQ_LABEL, dst, dst_len), (const uint8_t*)w->pk, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
     HIPRC_TRY(c, dleq_launch_composites_merge(c->stream, w->st_m, w->st_z, m32, z32, status, (u32)groups));
     return FOURQ_OK;
 }
@@ -2697,10 +2697,10 @@ FQ_API int fourq_dleq_prove_dev(fourq_ctx* c, const uint64_t* key, const uint64_
     HIPRC_TRY(c, dleq_launch_nonces(c->stream, key, nonces, w->sc_a, (u32)groups));
     HIPRC_TRY(c, oprf_launch_fill_key(c->stream, key, w->sc_b, (u32)groups));
     if ((rc = comb_encode(c, w->sc_a, w->affine, w->st_t2, t2, groups + 1))) return rc;
-    if ((rc = dleq_composites_stage(c, *w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, nullptr, false, groups, group_size))) return rc;
+    if ((rc = dleq_composites_stage(c, *w, sha_make_tail("Composite", DLEQ_LABEL, dst, dst_len), pk_dev, blinded32, evaluated32, m32, nullptr, false, groups, group_size))) return rc;
     if ((rc = dh_bytes_dev(c, ENDO, w->sc_b, m32, nullptr, z32, w->st_z, groups))) return rc;                 // Z = DH_endo(k, M): D is hashed, never decoded
     if ((rc = mul_bytes_dev(c, ENDO, w->sc_a, m32, t3, w->st_t3, groups))) return rc;                        // t3 = encode([r]M)
-    HIPRC_TRY(c, dleq_launch_prove(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), key, w->sc_a, w->st_m, w->st_z, w->st_t3, proof64, status,
+    HIPRC_TRY(c, dleq_launch_prove(c->stream, pk_dev, m32, z32, t2, t3, sha_make_tail("Challenge", DLEQ_LABEL, dst, dst_len), key, w->sc_a, w->st_m, w->st_z, w->st_t3, proof64, status,
                                    (u32)groups));
     return FOURQ_OK;
 }
@@ -2716,11 +2716,11 @@ FQ_API int fourq_dleq_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint64
     uint8_t *m32 = (uint8_t*)w->m32, *z32 = (uint8_t*)w->z32, *t2 = (uint8_t*)w->t2, *t3 = (uint8_t*)w->t3;
     const uint8_t* pk_dev = (const uint8_t*)w->pk;
     HIPRC_TRY(c, oprf_launch_fill_key(c->stream, dleq_scalar_arg(pk32).w, w->pk, (u32)groups));             // pk on every group's row: the point of [s]G + [c]pk
-    if ((rc = dleq_composites_stage(c, *w, dleq_make_tail("Composite", dst, dst_len), pk_dev, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
+    if ((rc = dleq_composites_stage(c, *w, sha_make_tail("Composite", DLEQ_LABEL, dst, dst_len), pk_dev, blinded32, evaluated32, m32, z32, true, groups, group_size))) return rc;
     HIPRC_TRY(c, dleq_launch_split(c->stream, proof64, m32, z32, w->sc_a, w->sc_b, w->pair_sc, w->pair_pt, w->st_pre, (u32)groups));
     if ((rc = double_mul_dev(c, w->sc_a, nullptr, w->sc_b, pk_dev, true, COMBINE_ENCODE, nullptr, t2, w->st_t2, nullptr, groups))) return rc;       // t2' = [s]G + [c]pk
     if ((rc = msm_dev(c, w->pair_sc, w->pair_pt, true, t3, w->st_t3, groups, 2))) return rc;                                                     // t3' = [s]M + [c]Z
-    HIPRC_TRY(c, dleq_launch_check(c->stream, pk_dev, m32, z32, t2, t3, dleq_make_tail("Challenge", dst, dst_len), w->sc_b, w->st_m, w->st_z, w->st_t2, w->st_pre, w->st_t3, ok, status,
+    HIPRC_TRY(c, dleq_launch_check(c->stream, pk_dev, m32, z32, t2, t3, sha_make_tail("Challenge", DLEQ_LABEL, dst, dst_len), w->sc_b, w->st_m, w->st_z, w->st_t2, w->st_pre, w->st_t3, ok, status,
                                    (u32)groups));
     return FOURQ_OK;
 }
@@ -2774,7 +2774,7 @@ FQ_API int fourq_vrf_reserve(fourq_ctx* c, size_t n) {
 }
 // h32 = encode(hash to curve, RO, of pk32 || alpha): pk32 is a register prefix of the message loop, nothing is concatenated
 static int vrf_hash_stage(fourq_ctx* c, const fq_work::Vrf& w, const uint8_t* pk32, const SigMsgs& m, const uint8_t* dst, size_t dst_len, size_t n) {
-    HIPRC_TRY(c, vrf_launch_h2f(c->stream, pk32, m, h2c_make_dst(dst, dst_len, 2), w.u, (u32)n));
+    HIPRC_TRY(c, h2c_launch_h2f(c->stream, 2, pk32, m, h2c_make_dst(dst, dst_len, 2), w.u, (u32)n));
     HIPRC_TRY(c, h2c_launch_ell2(c->stream, 2, H2C_OUT_BYTES, w.u, w.h32, (u32)n));
     return FOURQ_OK;
 }
@@ -2793,7 +2793,7 @@ FQ_API int fourq_vrf_prove_dev(fourq_ctx* c, const uint8_t* sk32, const uint8_t*
     if ((rc = comb_encode(c, w->sc_b, w->affine, w->st_u, t_u, n))) return rc;                                // u32 = encode([r]G)
     if ((rc = mul_bytes_dev(c, ENDO, w->sc_a, h32, g32, w->st_a, n))) return rc;                             // gamma32 = encode([x]Hpt)
     if ((rc = mul_bytes_dev(c, ENDO, w->sc_b, h32, t_v, w->st_b, n))) return rc;                             // v32 = encode([r]Hpt)
-    HIPRC_TRY(c, vrf_launch_prove(c->stream, pk32, h32, g32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), w->sc_a, w->sc_b, proof96, (u32)n));
+    HIPRC_TRY(c, vrf_launch_prove(c->stream, pk32, h32, g32, t_u, t_v, sha_make_tail("VrfVerify", DLEQ_LABEL, dst, dst_len), w->sc_a, w->sc_b, proof96, (u32)n));
     return FOURQ_OK;
 }
 // Both verify calls.  key_ids == NULL: the keys are the rows of pk32.  Otherwise the rows' key bytes are gathered by index (the hashes read
@@ -2824,8 +2824,8 @@ static int vrf_verify_dev(fourq_ctx* c, const uint8_t* pk32, const uint32_t* key
     else rc = double_mul_dev(c, w->sc_a, nullptr, w->sc_b, pk32, true, COMBINE_ENCODE, nullptr, t_u, w->st_u, nullptr, n);                 // u32' = [s]G + [c]Y
     if (rc) return rc;
     if ((rc = msm_dev(c, w->pair_sc, w->pair_pt, true, t_v, w->st_v, n, 2))) return rc;                                                   // v32' = [s]Hpt + [c / 392]W
-    const VrfKeys set = { key_ids, c->keyset_status, count };
-    HIPRC_TRY(c, vrf_launch_check(c->stream, pk32, h32, proof96, w32, t_u, t_v, dleq_make_tail("VrfVerify", dst, dst_len), dleq_make_tail("VrfOutput", dst, dst_len), w->sc_b, set, m,
+    const KeyRows set = { key_ids, c->keyset_bytes, c->keyset_status, count };
+    HIPRC_TRY(c, vrf_launch_check(c->stream, pk32, h32, proof96, w32, t_u, t_v, sha_make_tail("VrfVerify", DLEQ_LABEL, dst, dst_len), sha_make_tail("VrfOutput", DLEQ_LABEL, dst, dst_len), w->sc_b, set, m,
                                   w->st_u, w->st_a, w->st_pre, w->st_v, beta64, ok, status, (u32)n));
     return FOURQ_OK;
 }
@@ -2842,7 +2842,7 @@ FQ_API int fourq_vrf_proof_to_hash_dev(fourq_ctx* c, const uint8_t* dst, size_t 
     if (!vrf_args_ok(c, dst, dst_len) || !proof96 || !beta64 || !status || n > FOURQ_MAX_BATCH || !aligned16(proof96) || !aligned16(beta64)) return FOURQ_ERR_INVALID;
     if (n == 0) return FOURQ_OK;
     CtxGuard g(c);
-    HIPRC_TRY(c, vrf_launch_proof_to_hash(c->stream, proof96, dleq_make_tail("VrfOutput", dst, dst_len), beta64, status, (u32)n));
+    HIPRC_TRY(c, vrf_launch_proof_to_hash(c->stream, proof96, sha_make_tail("VrfOutput", DLEQ_LABEL, dst, dst_len), beta64, status, (u32)n));
     return FOURQ_OK;
 }
 // host-pointer twins: copy in, the _dev call, copy out, through the pipeline's chunks; the comb is staged once, before the arrays

@@ -4,13 +4,13 @@
 //
 // Hashing (h2f_kernel).  b_0 = H(Z_pad || msg || I2OSP(len_in_bytes, 2) || 0x00 || DST_prime), b_1 = H(b_0 || 0x01 || DST_prime),
 // b_2 = H((b_0 xor b_1) || 0x02 || DST_prime).  Everything but msg and the digests is the same for every lane and travels BY VALUE in
-// the kernel arguments (H2cDst: nothing is staged, so the _dev calls stay capturable), already laid out as big-endian words with the
-// 0x80 marker, the zero fill and -- where the whole string is wave-uniform -- the bit length in place:
-//   tail0   what follows a row in b_0's string; a lane reads it at the byte offset its row's length gives (lengths are public)
-//   tail1   whole padded blocks of b_1's string behind the 64 digest bytes; b_2's differ in the counter byte alone
+// the kernel arguments (H2cDst), already laid out as big-endian words:
+//   tail0   what follows a row in b_0's string: a ShaTail (sha512.hip.h), which sha512_fill reads behind the row with `before` = 128
+//   tail1   whole padded blocks of b_1's string behind the 64 digest bytes, the bit length in place; b_2's differ in the counter byte alone
 // The state behind the all-zero Z_pad block is a constant (SHA512_ZPAD_MID, constants.inc).  One lane runs its blocks of all three
 // strings through ONE copy of the compression function (as sig_nonce_kernel does); only the number of blocks differs between lanes.
-// The row rules of sig.hip.h hold: no byte at or past a row's length is read, any stride, vector loads only where alignment allows.
+// The PREFIXED flavour hashes a 32-byte row (the VRF's pk32) in front of msg without a concatenated copy: the row is sha512_fill's
+// register prefix, loaded in the step that uses it, and msg follows at string offset 32, so an aligned row keeps its vector loads.
 //
 // Field and map (ell2_kernel).  Every decision is a mask: no branch and no address depends on u or on a message byte (the message may
 // be a password), so the same code serves both table-selection modes of the library.  Per map three GF(p) exponentiations --
@@ -24,12 +24,10 @@
 
 namespace fq {
 
-constexpr int H2C_TAIL0_WORDS = 34;      // 3 + 255 + 1 bytes, the marker, and one zero word behind what a shifted read can reach
 constexpr int H2C_TAIL1_WORDS = 40;      // 3 blocks - 64 bytes: 0x01 || DST_prime (257 bytes at most) || padding || bit length
 struct H2cDst {
-    u64 tail0[H2C_TAIL0_WORDS];
+    ShaTail tail0;                       // I2OSP(len_in_bytes, 2) || 0x00 || DST_prime
     u64 tail1[H2C_TAIL1_WORDS];
-    u32 tail0_len;                       // 3 + |DST| + 1
     u32 blocks1;                         // blocks of b_0 || 0x01 || DST_prime: 1..3
 };
 enum H2cOut { H2C_OUT_MAP = 0, H2C_OUT_AFFINE = 1, H2C_OUT_BYTES = 2 };     // map + rational map only | + x392, affine words | + x392, 32 bytes
@@ -38,82 +36,34 @@ enum H2cOut { H2C_OUT_MAP = 0, H2C_OUT_AFFINE = 1, H2C_OUT_BYTES = 2 };     // m
 inline H2cDst h2c_make_dst(const uint8_t* dst, size_t dst_len, int count) {
     H2cDst d;
     memset(&d, 0, sizeof d);
-    uint8_t t0[8 * H2C_TAIL0_WORDS] = { 0 }, t1[8 * H2C_TAIL1_WORDS] = { 0 };
     const size_t len_in_bytes = 64 * (size_t)count;
-    t0[0] = (uint8_t)(len_in_bytes >> 8); t0[1] = (uint8_t)len_in_bytes; t0[2] = 0;
-    memcpy(t0 + 3, dst, dst_len);
-    t0[3 + dst_len] = (uint8_t)dst_len;
-    d.tail0_len = (u32)(3 + dst_len + 1);
-    t0[d.tail0_len] = 0x80;
-    t1[0] = 0x01;
-    memcpy(t1 + 1, dst, dst_len);
-    t1[1 + dst_len] = (uint8_t)dst_len;
-    t1[2 + dst_len] = 0x80;
-    const size_t total = 64 + 1 + dst_len + 1;
-    d.blocks1 = (u32)((total + 17 + 127) / 128);
-    const uint64_t bits = 8 * (uint64_t)total;
-    for (int k = 0; k < 8; k++) t1[128 * d.blocks1 - 64 - 1 - k] = (uint8_t)(bits >> (8 * k));
-    for (int w = 0; w < H2C_TAIL0_WORDS; w++) for (int k = 0; k < 8; k++) d.tail0[w] = (d.tail0[w] << 8) | t0[8 * w + k];
-    for (int w = 0; w < H2C_TAIL1_WORDS; w++) for (int k = 0; k < 8; k++) d.tail1[w] = (d.tail1[w] << 8) | t1[8 * w + k];
+    const uint8_t head0[3] = { (uint8_t)(len_in_bytes >> 8), (uint8_t)len_in_bytes, 0 }, head1[1] = { 0x01 };
+    d.tail0 = sha_make_tail(head0, sizeof head0, dst, dst_len);
+    const ShaTail t1 = sha_make_tail(head1, sizeof head1, dst, dst_len);
+    static_assert(SHA_TAIL_WORDS <= H2C_TAIL1_WORDS, "tail1 starts as a ShaTail's words");
+    for (int w = 0; w < SHA_TAIL_WORDS; w++) d.tail1[w] = t1.w[w];
+    d.blocks1 = sha512_blocks(64 + t1.len);
+    d.tail1[16 * d.blocks1 - 8 - 1] = 8 * (uint64_t)(64 + t1.len);      // the bit length ends the last block
     return d;
 }
 
 namespace {
 
 // ---- hashing ----------------------------------------------------------------------------------------------------------------------
-// big-endian word of tail0 at byte offset `at` (marker and zeros included; zero behind the array)
-FQ_DEV u64 h2c_tail_word(const H2cDst& d, u32 at) {
-    const u32 q = at >> 3, r = 8 * (at & 7);
-    const u32 qa = q < (u32)H2C_TAIL0_WORDS - 1 ? q : (u32)H2C_TAIL0_WORDS - 1;          // the last word is zero
-    const u32 qb = q + 1 < (u32)H2C_TAIL0_WORDS - 1 ? q + 1 : (u32)H2C_TAIL0_WORDS - 1;
-    const u64 a = d.tail0[qa], b = d.tail0[qb];
-    return r ? (a << r) | (b >> (64 - r)) : a;
-}
-// big-endian word at offset m (a multiple of 8) of row[0..len) ++ tail0: data, the word that straddles the row's end, tail
-FQ_DEV u64 h2c_word(const uint8_t* row, u32 len, const H2cDst& d, u32 m, int mode) {
-    if (m + 8 <= len) {
-        if (mode != SHA_LOAD_BYTES) return __builtin_bswap64(*reinterpret_cast<const u64*>(row + m));
-        u64 v = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) v |= (u64)row[m + k] << (56 - 8 * k);
-        return v;
-    }
-    if (m >= len) return h2c_tail_word(d, m - len);
-    const u32 rem = len - m;                        // 1..7 bytes of data, then the tail's first bytes
-    u64 v = d.tail0[0] >> (8 * rem);
-#pragma unroll 1
-    for (u32 k = 0; k < rem; k++) v |= (u64)row[m + k] << (56 - 8 * k);
-    return v;
-}
-// sha512_fill's sibling: block b of the padded string row[0..len) ++ tail0 -- a row of per-lane length with a wave-uniform tail behind
-// it -- that FOLLOWS one block already hashed (Z_pad: the caller starts from SHA512_ZPAD_MID), into w[0..15]
-FQ_DEV void sha512_fill_tail(u64 w[16], const uint8_t* row, u32 len, const H2cDst& d, u32 b, u32 blocks, int mode) {
-#pragma unroll
-    for (int j = 0; j < 16; j += 2) {
-        const u32 m = 128 * b + 8 * j;
-        if (mode == SHA_LOAD_16 && m + 16 <= len) {
-            const uint4 q = *reinterpret_cast<const uint4*>(row + m);
-            w[j] = __builtin_bswap64(((u64)q.y << 32) | q.x);
-            w[j + 1] = __builtin_bswap64(((u64)q.w << 32) | q.z);
-        } else {
-            w[j] = h2c_word(row, len, d, m, mode);
-            w[j + 1] = h2c_word(row, len, d, m + 8, mode);
-        }
-    }
-    if (b + 1 == blocks) w[15] = (u64)(128 + len + d.tail0_len) * 8;      // the bit length, Z_pad included
-}
 // OS2IP(32 bytes) mod p for the big-endian words (a, b, c, e), a first: 2^128 = 2 (mod 2^127 - 1), so the value is 2 (a : b) + (c : e)
 FQ_DEV Fe<3> h2c_reduce256(u64 a, u64 b, u64 c, u64 e) { return fe_add(fe_dbl(fe_unpack(b, a)), fe_unpack(e, c)); }
 
 // out_u: n x COUNT x 4 canonical words.  b_0 stays live across b_1 for COUNT = 2: eight more 64-bit values than the 40 of the signature
-// layer's hashing kernels, which do not fit 128 VGPRs (4 spilled) -- that flavour is held to three waves per SIMD instead of four
-template <int COUNT>
-__global__ __launch_bounds__(SIG_BLOCK, COUNT == 2 ? SIG_WAVES - 1 : SIG_WAVES) void h2f_kernel(SigMsgs m, H2cDst d, u64* out_u, u32 n) {
+// layer's hashing kernels, which do not fit 128 VGPRs (4 spilled) -- that flavour is held to three waves per SIMD instead of four.
+// PREFIXED: the string is pk32[i] || msg_i (pk32: n rows of 32 bytes, 16-byte aligned; not read otherwise)
+template <int COUNT, bool PREFIXED>
+__global__ __launch_bounds__(SIG_BLOCK, COUNT == 2 ? SIG_WAVES - 1 : SIG_WAVES) void h2f_kernel(const uint8_t* pk32, SigMsgs m, H2cDst d, u64* out_u, u32 n) {
+    constexpr int PW = PREFIXED ? 4 : 0;
     const u32 i = blockIdx.x * SIG_BLOCK + threadIdx.x;
     if (i >= n) return;
     const LaneMsg l = lane_msg(m, i);
     const int mode = sha_load_mode(m.rows, m.stride);
-    const u32 blocks0 = sha512_blocks(l.len + d.tail0_len), blocks1 = d.blocks1, steps = blocks0 + COUNT * blocks1;
+    const u32 blocks0 = sha512_blocks(8 * PW + l.len + d.tail0.len), blocks1 = d.blocks1, steps = blocks0 + COUNT * blocks1;
     u64 h[8], b0[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) { h[k] = SHA512_ZPAD_MID[k]; b0[k] = 0; }
@@ -125,7 +75,9 @@ __global__ __launch_bounds__(SIG_BLOCK, COUNT == 2 ? SIG_WAVES - 1 : SIG_WAVES) 
         const u32 r = (COUNT == 2 && !msg_phase && s1 >= blocks1) ? 1u : 0u;    // which of b_1, b_2
         const u32 bb = s1 - r * blocks1;                                      // its block
         if (msg_phase) {
-            sha512_fill_tail(w, l.row, l.len, d, step, blocks0, mode);
+            u64 pre[4];
+            if (PREFIXED && step == 0) dleq_row_words(pk32 + 32 * (size_t)i, pre);
+            sha512_fill<PW>(w, pre, l.row, l.len, d.tail0, 128, step, blocks0, mode);      // behind Z_pad
         } else if (bb == 0) {
             // h is b_0 (r == 0) or b_1 (r == 1): the string starts with b_0, or with b_0 xor b_1
 #pragma unroll
@@ -268,9 +220,11 @@ __global__ __launch_bounds__(BLOCK) void ell2_kernel(const u64* u, u64* out, u32
 }
 
 // ---- launchers: each returns the hipError_t of its launch ---------------------------------------------------------------------------
-int h2c_launch_h2f(hipStream_t stream, int count, SigMsgs m, const H2cDst& d, uint64_t* out_u, uint32_t n) {
-    if (count == 2) hipLaunchKernelGGL(h2f_kernel<2>, sig_grid(n), dim3(SIG_BLOCK), 0, stream, m, d, (u64*)out_u, n);
-    else hipLaunchKernelGGL(h2f_kernel<1>, sig_grid(n), dim3(SIG_BLOCK), 0, stream, m, d, (u64*)out_u, n);
+// pk32 != NULL: the 32-byte row hashed in front of every message (two elements only)
+int h2c_launch_h2f(hipStream_t stream, int count, const uint8_t* pk32, SigMsgs m, const H2cDst& d, uint64_t* out_u, uint32_t n) {
+    if (pk32) hipLaunchKernelGGL((h2f_kernel<2, true>), sig_grid(n), dim3(SIG_BLOCK), 0, stream, pk32, m, d, (u64*)out_u, n);
+    else if (count == 2) hipLaunchKernelGGL((h2f_kernel<2, false>), sig_grid(n), dim3(SIG_BLOCK), 0, stream, pk32, m, d, (u64*)out_u, n);
+    else hipLaunchKernelGGL((h2f_kernel<1, false>), sig_grid(n), dim3(SIG_BLOCK), 0, stream, pk32, m, d, (u64*)out_u, n);
     return (int)hipGetLastError();
 }
 int h2c_launch_ell2(hipStream_t stream, int count, int out_kind, const uint64_t* u, uint64_t* out, uint32_t n) {

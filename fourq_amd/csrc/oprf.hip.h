@@ -9,34 +9,14 @@
 // the elements are loaded and reduced again on the way back.  A lane's slots past the end of the batch redo its first element and store
 // nothing.  Everything is masks and straight-line code on whole words: no branch and no address depends on a value.
 //
-// Finalisation (oprf_final_kernel).  F(E, msg) = SHA-512(E || msg || tail), tail = "Finalize" || DST || I2OSP(len(DST), 1): the 32 bytes
-// of E are a register prefix (sha512_fill's PW = 4), the row follows at string offset 32 -- a multiple of 16, so an aligned row keeps its
-// vector loads -- and the tail is the same for every lane and travels BY VALUE in the kernel arguments like H2cDst::tail0 (OprfTail:
-// big-endian words with the 0x80 marker and the zero fill in place; a lane reads it at the byte offset its row's length gives).  The row
-// rules of sig.hip.h hold: no byte at or past a row's length is read, any stride.
+// Finalisation (oprf_final_kernel).  F(E, msg) = SHA-512(E || msg || tail), tail = "Finalize" || DST || I2OSP(len(DST), 1): sha512_hash
+// (sha512.hip.h) with the 32 bytes of E as its register prefix (PW = 4) -- the row follows at string offset 32, a multiple of 16, so an
+// aligned row keeps its vector loads -- and the tail as a ShaTail by value in the kernel arguments.
 #pragma once
 #include "h2c.hip.h"        // sig.hip.h: SigMsgs, lane_msg, load32 / store32, SIG_BLOCK; scalar_n.hip.h
 
 namespace fq {
 
-constexpr int OPRF_TAIL_WORDS = 35;      // 8 + 255 + 1 bytes, the marker, and one zero word behind what a shifted read can reach
-struct OprfTail {
-    u64 tail[OPRF_TAIL_WORDS];
-    u32 tail_len;                        // 8 + |DST| + 1
-};
-// dst: 1..255 bytes (checked by the caller)
-inline OprfTail oprf_make_tail(const uint8_t* dst, size_t dst_len) {
-    OprfTail d;
-    memset(&d, 0, sizeof d);
-    uint8_t t[8 * OPRF_TAIL_WORDS] = { 0 };
-    memcpy(t, "Finalize", 8);
-    memcpy(t + 8, dst, dst_len);
-    t[8 + dst_len] = (uint8_t)dst_len;
-    d.tail_len = (u32)(8 + dst_len + 1);
-    t[d.tail_len] = 0x80;
-    for (int w = 0; w < OPRF_TAIL_WORDS; w++) for (int k = 0; k < 8; k++) d.tail[w] = (d.tail[w] << 8) | t[8 * w + k];
-    return d;
-}
 struct ScalarArg { u64 w[4]; };
 
 namespace {
@@ -103,51 +83,9 @@ __global__ __launch_bounds__(SIG_BLOCK) void oprf_blind_merge_kernel(const u64* 
 }
 
 // ---- the finalisation hash ---------------------------------------------------------------------------------------------------------------
-// big-endian word of the tail at byte offset `at` (marker and zeros included; zero behind the array)
-FQ_DEV u64 oprf_tail_word(const OprfTail& d, u32 at) {
-    const u32 q = at >> 3, r = 8 * (at & 7);
-    const u32 qa = q < (u32)OPRF_TAIL_WORDS - 1 ? q : (u32)OPRF_TAIL_WORDS - 1;          // the last word is zero
-    const u32 qb = q + 1 < (u32)OPRF_TAIL_WORDS - 1 ? q + 1 : (u32)OPRF_TAIL_WORDS - 1;
-    const u64 a = d.tail[qa], b = d.tail[qb];
-    return r ? (a << r) | (b >> (64 - r)) : a;
-}
-// big-endian word at offset m (a multiple of 8) of row[0..len) ++ tail: data, the word that straddles the row's end, tail
-FQ_DEV u64 oprf_word(const uint8_t* row, u32 len, const OprfTail& d, u32 m, int mode) {
-    if (m + 8 <= len) {
-        if (mode != SHA_LOAD_BYTES) return __builtin_bswap64(*reinterpret_cast<const u64*>(row + m));
-        u64 v = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) v |= (u64)row[m + k] << (56 - 8 * k);
-        return v;
-    }
-    if (m >= len) return oprf_tail_word(d, m - len);
-    const u32 rem = len - m;                        // 1..7 bytes of data, then the tail's first bytes
-    u64 v = d.tail[0] >> (8 * rem);
-#pragma unroll 1
-    for (u32 k = 0; k < rem; k++) v |= (u64)row[m + k] << (56 - 8 * k);
-    return v;
-}
-// sha512_fill_tail's sibling: block b of the padded string pre[0..4) ++ row[0..len) ++ tail, nothing hashed in front of it
-FQ_DEV void oprf_fill(u64 w[16], const u64 pre[4], const uint8_t* row, u32 len, const OprfTail& d, u32 b, u32 blocks, int mode) {
-#pragma unroll
-    for (int j = 0; j < 16; j += 2) {
-        const u32 m = 128 * b + 8 * j - 32;         // offset into row ++ tail (wraps for a prefix word: not used then)
-        if (j < 4 && b == 0) {
-            w[j] = pre[j]; w[j + 1] = pre[j + 1];
-        } else if (mode == SHA_LOAD_16 && m + 16 <= len) {
-            const uint4 q = *reinterpret_cast<const uint4*>(row + m);
-            w[j] = __builtin_bswap64(((u64)q.y << 32) | q.x);
-            w[j + 1] = __builtin_bswap64(((u64)q.w << 32) | q.z);
-        } else {
-            w[j] = oprf_word(row, len, d, m, mode);
-            w[j + 1] = oprf_word(row, len, d, m + 8, mode);
-        }
-    }
-    if (b + 1 == blocks) w[15] = (u64)(32 + len + d.tail_len) * 8;       // the bit length; w[14] is the zero fill already there
-}
 // out64[i] = F(e32[i], msg_i); status[i] = st_in[i] (a decode or DH code of the stages in front), else st_zero[i] (optional: the blind was
 // 0 mod N), else FOURQ_SIG_MSG_CLAMPED for a clamped row; the row is all zero unless 0
-__global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void oprf_final_kernel(const uint8_t* e32, SigMsgs m, OprfTail d, const uint8_t* st_in, const uint8_t* st_zero,
+__global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void oprf_final_kernel(const uint8_t* e32, SigMsgs m, ShaTail d, const uint8_t* st_in, const uint8_t* st_zero,
                                                                          uint8_t* out64, uint8_t* status, u32 n) {
     const u32 i = blockIdx.x * SIG_BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -160,14 +98,7 @@ __global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void oprf_final_kernel(const 
     uint8_t st = st_in[i];
     if (st == 0 && st_zero) st = st_zero[i];
     if (st == 0 && l.clamped) st = (uint8_t)FOURQ_SIG_MSG_CLAMPED;
-    const u32 blocks = sha512_blocks(32 + l.len + d.tail_len);
-    sha512_init(h);
-#pragma unroll 1
-    for (u32 b = 0; b < blocks; b++) {
-        u64 w[16];
-        oprf_fill(w, pre, l.row, l.len, d, b, blocks, mode);
-        sha512_compress(h, w);
-    }
+    sha512_hash<4>(h, pre, l.row, l.len, d, mode);
     sha512_digest_le(h, x);
 #pragma unroll
     for (int k = 0; k < 8; k++) x[k] = st ? 0 : x[k];
@@ -196,7 +127,7 @@ int oprf_launch_blind_merge(hipStream_t stream, const uint64_t* blinds, SigMsgs 
     hipLaunchKernelGGL(oprf_blind_merge_kernel, sig_grid(n), dim3(SIG_BLOCK), 0, stream, (const u64*)blinds, m, (u64*)out32, status, n);
     return (int)hipGetLastError();
 }
-int oprf_launch_final(hipStream_t stream, const uint8_t* e32, SigMsgs m, const OprfTail& d, const uint8_t* st_in, const uint8_t* st_zero, uint8_t* out64,
+int oprf_launch_final(hipStream_t stream, const uint8_t* e32, SigMsgs m, const ShaTail& d, const uint8_t* st_in, const uint8_t* st_zero, uint8_t* out64,
                       uint8_t* status, uint32_t n) {
     hipLaunchKernelGGL(oprf_final_kernel, sig_grid(n), dim3(SIG_BLOCK), 0, stream, e32, m, d, st_in, st_zero, out64, status, n);
     return (int)hipGetLastError();

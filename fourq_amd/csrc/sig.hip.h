@@ -4,6 +4,8 @@
 //   keygen   k = H(sk), pk = encode([LE(k[0:32])]G)
 //   sign     r = LE(H(k[32:64] || msg)) mod N, R = encode([r]G), h = LE(H(R || pk || msg)) mod N, s = (r - LE(k[0:32]) h) mod N
 //   verify   s < N, h as above, encode([s]G + [h]decode(pk)) == R
+// Every hashed string is sha512.hip.h's: prefix words in registers (k[32:64], or R || pk), the message row, padding only (ShaPad).  ONE
+// challenge kernel serves sig_verify and its keyed sibling: KeyRows says whether the key row is row i or a slot of the registered set.
 // Throughput kernels: ~2 600 instructions of code, 40 live 64-bit values, no LDS, no scratch memory.  Every launcher returns the
 // hipError_t of its launch.
 #pragma once
@@ -22,9 +24,16 @@ struct SigMsgs {
     const uint32_t* lens;
     uint32_t msg_len;
 };
+// whose public key a row is checked against: row i of `bytes` (ids == NULL; no key status), or slot ids[i] of a registered key set of `count`
+// keys (fourq_keyset_set) with the slots' 32-byte rows in `bytes` and their statuses in `status`
+struct KeyRows {
+    const uint32_t* ids;
+    const uint8_t* bytes;
+    const uint8_t* status;
+    uint32_t count;
+};
 
 namespace {
-
 
 constexpr int SIG_BLOCK = 256;
 constexpr int SIG_WAVES = 4;      // waves per SIMD the hashing kernels are held to (128 VGPRs): 40 live 64-bit values fit with room to spare
@@ -48,12 +57,25 @@ FQ_DEV void store32(uint8_t* p, const u64 w[4]) {
     reinterpret_cast<uint4*>(p)[0] = make_uint4((u32)w[0], (u32)(w[0] >> 32), (u32)w[1], (u32)(w[1] >> 32));
     reinterpret_cast<uint4*>(p)[1] = make_uint4((u32)w[2], (u32)(w[2] >> 32), (u32)w[3], (u32)(w[3] >> 32));
 }
+// a 32-byte row as the four big-endian words of a hashed string
+FQ_DEV void dleq_row_words(const uint8_t* row, u64 w[4]) {
+    sha_load16(row, w[0], w[1]);
+    sha_load16(row + 16, w[2], w[3]);
+}
+// the key row of lane i (`at`) and the key's status: an index outside the set is clamped BEFORE it becomes an address
+FQ_DEV uint8_t key_row(const KeyRows& keys, u32 i, u32& at) {
+    at = i;
+    if (!keys.ids) return 0;
+    const u32 id = keys.ids[i];
+    at = id < keys.count ? id : keys.count - 1;
+    return id < keys.count ? keys.status[at] : (uint8_t)FOURQ_KEYSET_ID_RANGE;
+}
 // the challenge h = LE(SHA-512(R || pk || msg)) mod N; R, pk as little-endian words of their 32 bytes
 FQ_DEV void challenge(const u64 R[4], const u64 pk[4], const LaneMsg& l, int mode, u64 h[4]) {
     u64 pre[8], d[8], x[8];
 #pragma unroll
     for (int k = 0; k < 4; k++) { pre[k] = __builtin_bswap64(R[k]); pre[4 + k] = __builtin_bswap64(pk[k]); }
-    sha512_hash<8>(d, pre, l.row, l.len, mode);
+    sha512_hash<8>(d, pre, l.row, l.len, ShaPad{}, mode);
     sha512_digest_le(d, x);
     sc_reduce512(x, h);
 }
@@ -63,44 +85,27 @@ __global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void sha512_kernel(SigMsgs m,
     if (i >= n) return;
     const LaneMsg l = lane_msg(m, i);
     u64 d[8], x[8];
-    sha512_hash<0>(d, nullptr, l.row, l.len, sha_load_mode(m.rows, m.stride));
+    sha512_hash<0>(d, nullptr, l.row, l.len, ShaPad{}, sha_load_mode(m.rows, m.stride));
     sha512_digest_le(d, x);
     store32(out64 + 64 * (size_t)i, x);
     store32(out64 + 64 * (size_t)i + 32, x + 4);
 }
 
-__global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void sig_challenge_kernel(const uint8_t* pk32, SigMsgs m, const uint8_t* sig64, u64* s_out, u64* h_out, u64* r_out,
-                                                                  uint8_t* pre_status, u32 n) {
+// the pre-status carries the whole precedence: the key's (key_row), a clamped message, s >= N
+__global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void sig_challenge_kernel(KeyRows keys, SigMsgs m, const uint8_t* sig64, u64* s_out, u64* h_out, u64* r_out,
+                                                                            uint8_t* pre_status, u32 n) {
     const u32 i = blockIdx.x * SIG_BLOCK + threadIdx.x;
     if (i >= n) return;
     const LaneMsg l = lane_msg(m, i);
+    u32 at;
+    const uint8_t key = key_row(keys, i, at);
     u64 R[4], s[4], pk[4], h[4];
     load32(sig64 + 64 * (size_t)i, R);
     load32(sig64 + 64 * (size_t)i + 32, s);
-    load32(pk32 + 32 * (size_t)i, pk);
-    // s, R and the range byte leave before the hash: nothing of them stays live across it
+    load32(keys.bytes + 32 * (size_t)at, pk);
+    // s, R and the status byte leave before the hash: nothing of them stays live across it
     store32(reinterpret_cast<uint8_t*>(s_out + 4 * (size_t)i), s);
     store32(reinterpret_cast<uint8_t*>(r_out + 4 * (size_t)i), R);
-    pre_status[i] = l.clamped ? (uint8_t)FOURQ_SIG_MSG_CLAMPED : sc_lt_n(s) ? (uint8_t)0 : (uint8_t)FOURQ_SIG_S_RANGE;
-    challenge(R, pk, l, sha_load_mode(m.rows, m.stride), h);
-    store32(reinterpret_cast<uint8_t*>(h_out + 4 * (size_t)i), h);
-}
-
-// sig_challenge_kernel over a registered key set (fourq_keyset_set): the key row is key_bytes[id_i], and the pre-status carries the whole
-// precedence -- an index outside the set (clamped before it becomes an address), the key's own status, a clamped message, s >= N
-__global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void sig_challenge_keyed_kernel(const u32* key_ids, const uint8_t* key_bytes, const uint8_t* key_status, u32 count, SigMsgs m,
-                                                                                   const uint8_t* sig64, u64* s_out, u64* h_out, u64* r_out, uint8_t* pre_status, u32 n) {
-    const u32 i = blockIdx.x * SIG_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const LaneMsg l = lane_msg(m, i);
-    const u32 id = key_ids[i], at = id < count ? id : count - 1;
-    u64 R[4], s[4], pk[4], h[4];
-    load32(sig64 + 64 * (size_t)i, R);
-    load32(sig64 + 64 * (size_t)i + 32, s);
-    load32(key_bytes + 32 * (size_t)at, pk);
-    store32(reinterpret_cast<uint8_t*>(s_out + 4 * (size_t)i), s);
-    store32(reinterpret_cast<uint8_t*>(r_out + 4 * (size_t)i), R);
-    const uint8_t key = id < count ? key_status[at] : (uint8_t)FOURQ_KEYSET_ID_RANGE;
     pre_status[i] = key ? key : l.clamped ? (uint8_t)FOURQ_SIG_MSG_CLAMPED : sc_lt_n(s) ? (uint8_t)0 : (uint8_t)FOURQ_SIG_S_RANGE;
     challenge(R, pk, l, sha_load_mode(m.rows, m.stride), h);
     store32(reinterpret_cast<uint8_t*>(h_out + 4 * (size_t)i), h);
@@ -133,7 +138,7 @@ __global__ __launch_bounds__(SIG_BLOCK, SIG_WAVES) void sig_nonce_kernel(const u
         }
         // step 0: the string is the prefix alone (sk, one block); afterwards block step - 1 of k[32:64] || msg
         const bool first = step == 0;
-        sha512_fill<4>(w, pre, l.row, first ? 0 : l.len, first ? 0 : step - 1, first ? 1 : blocks, mode);
+        sha512_fill<4>(w, pre, l.row, first ? 0 : l.len, ShaPad{}, 0, first ? 0 : step - 1, first ? 1 : blocks, mode);
         sha512_compress(h, w);
     }
     if (NONCE) {
@@ -203,15 +208,9 @@ int sig_launch_sha512(hipStream_t stream, SigMsgs m, uint8_t* out64, uint32_t n)
     return (int)hipGetLastError();
 }
 // h = SHA-512(R || pk || msg) mod N from sig64 = R || s; writes s, h, R as 32-byte rows and the pre-status byte the merge reads
-int sig_launch_challenge(hipStream_t stream, const uint8_t* pk32, SigMsgs m, const uint8_t* sig64, uint64_t* s_out, uint64_t* h_out, uint64_t* r_out,
-                         uint8_t* pre_status, uint32_t n) {
-    hipLaunchKernelGGL(sig_challenge_kernel, sig_grid(n), dim3(SIG_BLOCK), 0, stream, pk32, m, sig64, (u64*)s_out, (u64*)h_out, (u64*)r_out, pre_status, n);
-    return (int)hipGetLastError();
-}
-int sig_launch_challenge_keyed(hipStream_t stream, const uint32_t* key_ids, const uint8_t* key_bytes, const uint8_t* key_status, uint32_t count, SigMsgs m, const uint8_t* sig64,
-                               uint64_t* s_out, uint64_t* h_out, uint64_t* r_out, uint8_t* pre_status, uint32_t n) {
-    hipLaunchKernelGGL(sig_challenge_keyed_kernel, sig_grid(n), dim3(SIG_BLOCK), 0, stream, key_ids, key_bytes, key_status, count, m, sig64, (u64*)s_out, (u64*)h_out, (u64*)r_out,
-                       pre_status, n);
+int sig_launch_challenge(hipStream_t stream, const KeyRows& keys, SigMsgs m, const uint8_t* sig64, uint64_t* s_out, uint64_t* h_out, uint64_t* r_out, uint8_t* pre_status,
+                         uint32_t n) {
+    hipLaunchKernelGGL(sig_challenge_kernel, sig_grid(n), dim3(SIG_BLOCK), 0, stream, keys, m, sig64, (u64*)s_out, (u64*)h_out, (u64*)r_out, pre_status, n);
     return (int)hipGetLastError();
 }
 // k = SHA-512(sk): a = LE(k[0:32]) (not reduced) into a_out; with `nonce`, r = SHA-512(k[32:64] || msg) mod N into r_out
