@@ -38,9 +38,7 @@ FQ_DEV Fe2<1> fe2_zero() {
 FQ_DEV void store_xyz(u64* dst_row, const Fe2<1>& X, const Fe2<1>& Y, const Fe2<1>& Z) {
     u64 w[12];
     store_fe2(w, X); store_fe2(w + 4, Y); store_fe2(w + 8, Z);
-    uint4* dst = reinterpret_cast<uint4*>(dst_row);
-#pragma clang loop unroll(full)
-    for (int k = 0; k < 6; k++) dst[k] = make_uint4((u32)w[2 * k], (u32)(w[2 * k] >> 32), (u32)w[2 * k + 1], (u32)(w[2 * k + 1] >> 32));
+    put_words<12>(dst_row, w);
 }
 
 // ---- 1. digits: v[i] = decompose(k_i); group_code[g] = the largest raw decode code among the group's elements (st_decode NULL: affine flavour)
@@ -50,9 +48,7 @@ __global__ __launch_bounds__(BLOCK) void bucket_digits_kernel(const u64* scalars
     u64 m[4], v[4];
     load_scalar(scalars + 4 * i, m);
     decompose(m, v);
-    uint4* dst = reinterpret_cast<uint4*>(v_out + 4 * i);
-    dst[0] = make_uint4((u32)v[0], (u32)(v[0] >> 32), (u32)v[1], (u32)(v[1] >> 32));
-    dst[1] = make_uint4((u32)v[2], (u32)(v[2] >> 32), (u32)v[3], (u32)(v[3] >> 32));
+    put_words<4>(v_out + 4 * i, v);
     if (st_decode) {
         const u32 s = st_decode[i];
         if (s) atomicMax(group_code + i / group_size, s);

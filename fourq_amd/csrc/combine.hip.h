@@ -16,12 +16,9 @@
 // the same projective point.  11 products + 1 square in GF(p^2); every operand's limb bound is in its type and every product's
 // column bound is static_asserted by fe2_mul (fp127.hip.h), the widest being Z3 = F' G' with bounds 4 and 3.
 //
-// R1toAffine behind it as lower_kernel does it (fourq_amd.hip): lane t owns elements t, t + T, ..., t + (K-1) T with T = ceil(n / K)
-// and inverts the product of their norms |Z3|^2 ONCE (Montgomery's trick; GFp2.inv = conj / norm, fields.py:193-199).  Z3 != 0 for any
-// two points of the curve; pairs of field elements that are not on it (MUL_* checks nothing, and a key that fails to decode is lifted
-// as the all-zero pair) can give Z3 = 0: such an element contributes a 1 to the lane's product, so it cannot touch the other K - 1
-// elements of its lane, and gets conj(0) * (...) = (0, 0) itself.  The sums of the lane's K elements stay in registers between the two
-// passes (30 limbs each): K = 2 takes 157 VGPRs and no scratch memory; K = 4 would fill all 256 of a two-wave kernel and spill.
+// R1toAffine behind it by the shared inversion of lower.hip.h.  Z3 != 0 for any two points of the curve; pairs of field elements that are not on it
+// can give Z3 = 0 and are masked (K > 1).  The sums of the lane's K elements stay in registers between the two passes (30 limbs each): K = 2
+// takes 157 VGPRs and no scratch memory; K = 4 would fill all 256 of a two-wave kernel and spill.
 #pragma once
 #include "kernels.hip.h"
 
@@ -53,61 +50,35 @@ FQ_DEV XYZ add_projective(const Fe2<1>& X1, const Fe2<1>& Y1, const Fe2<1>& Z1, 
 template <int K, int OUT>
 __global__ __launch_bounds__(BLOCK, 2) void combine_kernel(const uint4* proj, u32 proj_stride, const u64* rows, u32 row_stride, const uint8_t* st_decode,
                                                            const u64* expect, u64* out, uint8_t* status, uint8_t* ok, u32 n) {
-    const u32 T = (n + K - 1) / K;
-    const u32 t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= T) return;
-    Fe<1> one;
-    one.l[0] = 1; one.l[1] = one.l[2] = one.l[3] = one.l[4] = 0;
-    XYZ s[K];
-    Fe<1> nz[K], pre[K];
+    LaneSlots<K> s(n);
+    if (!s.lane(blockIdx.x * BLOCK + threadIdx.x)) return;
+    XYZ sum[K];
+    SharedInverse<K, FeOps<false>> si;
 #pragma clang loop unroll(full)
-    for (int j = 0; j < K; j++) {                     // a lane's slots past the end of the batch redo its first element and store nothing
-        const u32 id = t + (u32)j * T, at = id < n ? id : t;
+    for (int j = 0; j < K; j++) {
+        const u32 at = s.at(j);
         Fe2<1> X1, Y1;
         load_proj_xy(proj, proj_stride, at, X1, Y1);
         const Fe2<1> Z1 = load_proj_z(proj, proj_stride, at);
         const u64* row = rows + row_stride * (size_t)at;
-        s[j] = add_projective(X1, Y1, Z1, load_fe2(row), load_fe2(row + 4), load_fe2(row + 8));
-        const Fe<1> norm = fe_carry(fe_add(fe_sqr(s[j].Z.re), fe_sqr(s[j].Z.im)));
-        nz[j] = (K > 1) ? fe_select(fe_is_zero(norm) ? 0u : ~0u, norm, one) : norm;
-        if (j == 0) pre[0] = nz[0]; else pre[j] = fe_mul(pre[j - 1], nz[j]);
+        sum[j] = add_projective(X1, Y1, Z1, load_fe2(row), load_fe2(row + 4), load_fe2(row + 8));
+        const Fe<1> norm = z_norm(sum[j].Z);
+        if constexpr (K > 1) si.take(j, norm, !fe_is_zero(norm)); else si.take(j, norm);
         __builtin_amdgcn_sched_barrier(0);            // one addition after the other: interleaved, their temporaries would not fit the lane's registers
     }
-    Fe<1> inv = fe_inv(pre[K - 1]);
+    si.invert();
 #pragma clang loop unroll(full)
     for (int j = K - 1; j >= 0; j--) {
-        const u32 id = t + (u32)j * T;
-        Fe<1> ninv = inv;                                              // 1 / |Z_j|^2
-        if (j > 0) { ninv = fe_mul(inv, pre[j - 1]); inv = fe_mul(inv, nz[j]); }
-        Fe2<1> zi;
-        zi.re = fe_mul(ninv, s[j].Z.re);                               // conj(Z) / |Z|^2     fields.py:193-199
-        zi.im = fe_mul(ninv, fe_neg(s[j].Z.im));
-        const Fe2<1> ax = fe2_mul(s[j].X, zi), ay = fe2_mul(s[j].Y, zi);
-        if (id >= n) continue;
+        const Fe2<1> zi = z_inverse(sum[j].Z, si.peel(j));
+        const Fe2<1> ax = fe2_mul(sum[j].X, zi), ay = fe2_mul(sum[j].Y, zi);
+        if (!s.live(j)) continue;
+        const u32 id = s.id(j);
         if constexpr (OUT == COMBINE_AFFINE) {
-            u64 o[8];
-            store_fe2(o, ax); store_fe2(o + 4, ay);
-            uint4* dst = reinterpret_cast<uint4*>(out + 8 * (size_t)id);
-#pragma clang loop unroll(full)
-            for (int k = 0; k < 4; k++) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
+            put_affine(out, id, ax, ay);
         } else {
-            const uint8_t sd = st_decode ? st_decode[id] : (uint8_t)0;
-            const uint8_t st = sd ? (uint8_t)(FOURQ_BYTES_DECODE_BASE + sd) : (uint8_t)0;
-            u64 w[4];
-            point_encode(ax, ay, w);
-            if constexpr (OUT == COMBINE_ENCODE) {
-                if (st) w[0] = w[1] = w[2] = w[3] = 0;
-                uint4* dst = reinterpret_cast<uint4*>(out + 4 * (size_t)id);
-                dst[0] = make_uint4((u32)w[0], (u32)(w[0] >> 32), (u32)w[1], (u32)(w[1] >> 32));
-                dst[1] = make_uint4((u32)w[2], (u32)(w[2] >> 32), (u32)w[3], (u32)(w[3] >> 32));
-            } else {
-                const uint4* e = reinterpret_cast<const uint4*>(expect + 4 * (size_t)id);
-                const uint4 e0 = e[0], e1 = e[1];
-                const bool same = e0.x == (u32)w[0] && e0.y == (u32)(w[0] >> 32) && e0.z == (u32)w[1] && e0.w == (u32)(w[1] >> 32) &&
-                                  e1.x == (u32)w[2] && e1.y == (u32)(w[2] >> 32) && e1.z == (u32)w[3] && e1.w == (u32)(w[3] >> 32);
-                ok[id] = (same && !st) ? (uint8_t)1 : (uint8_t)0;
-            }
-            status[id] = st;
+            const uint8_t st = bytes_decode_status(st_decode ? st_decode[id] : (uint8_t)0);
+            if constexpr (OUT == COMBINE_ENCODE) put_encoded(out, status, id, ax, ay, st);
+            else put_verdict(expect, ok, status, id, ax, ay, st);
         }
     }
 }

@@ -58,9 +58,7 @@ template <bool CT> FQ_DEV void commit_row(const u64* scalars, const u32* table, 
     u64 w[12];
     store_fe2(w, fe2_carry(fe2_cneg(Q.X, c.negate)));           // even scalar: [k]B = -[N - k]B, -(x, y) = (-x, y)
     store_fe2(w + 4, Q.Y); store_fe2(w + 8, Q.Z);
-    uint4* dst = reinterpret_cast<uint4*>(rows + 12 * row);
-#pragma clang loop unroll(full)
-    for (int k = 0; k < 6; k++) dst[k] = make_uint4((u32)w[2 * k], (u32)(w[2 * k] >> 32), (u32)w[2 * k + 1], (u32)(w[2 * k + 1] >> 32));
+    put_words<12>(rows + 12 * row, w);
 }
 
 enum CommitRoute { COMMIT_STAGED = 1, COMMIT_GATHER = 2 };

@@ -180,9 +180,7 @@ __global__ __launch_bounds__(BLOCK) void encode_status_kernel(const u64* affine,
     u64 w[4];
     point_encode(load_fe2(affine + 8 * (size_t)i), load_fe2(affine + 8 * (size_t)i + 4), w);
     if (st) w[0] = w[1] = w[2] = w[3] = 0;
-    uint4* dst = reinterpret_cast<uint4*>(out + 4 * (size_t)i);
-    dst[0] = make_uint4((u32)w[0], (u32)(w[0] >> 32), (u32)w[1], (u32)(w[1] >> 32));
-    dst[1] = make_uint4((u32)w[2], (u32)(w[2] >> 32), (u32)w[3], (u32)(w[3] >> 32));
+    put_words<4>(out + 4 * (size_t)i, w);
     status[i] = st;
 }
 // one affine point replicated n times (the public base of a batch of exchanges); the point travels as a kernel argument,
@@ -191,9 +189,7 @@ struct AffineArg { u64 w[FOURQ_AFFINE_WORDS]; };
 __global__ __launch_bounds__(BLOCK) void broadcast_point_kernel(AffineArg point, u64* out, u32 n) {
     u32 i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    uint4* dst = reinterpret_cast<uint4*>(out + 8 * (size_t)i);
-#pragma unroll
-    for (int k = 0; k < 4; k++) dst[k] = make_uint4((u32)point.w[2 * k], (u32)(point.w[2 * k] >> 32), (u32)point.w[2 * k + 1], (u32)(point.w[2 * k + 1] >> 32));
+    put_words<8>(out + 8 * (size_t)i, point.w);
 }
 // MUL_* with affine I/O ("affine-only I/O variant"): AffineToR1 in front (curve4q.py:100-101), R1toAffine behind
 // (curve4q.py:103-106, one GFp2.inv per element: ~2 % of a MUL_endo's multiply-adds).  The R1 rows in between stay on the device.
@@ -207,63 +203,34 @@ __global__ __launch_bounds__(BLOCK) void lift_affine_kernel(const u64* affine, u
     dst[4] = make_uint4(1, 0, 0, 0); dst[5] = make_uint4(0, 0, 0, 0);                   // Z = 1
     dst[6] = x0; dst[7] = x1; dst[8] = y0; dst[9] = y1;                                  // Ta = X, Tb = Y
 }
-// R1toAffine (curve4q.py:103-106) behind a MUL_*, K elements per lane with ONE GFp.inv (Montgomery's trick inside a lane, as normalize_kernel
-// does for DH batches; fields.py:66-106, :193-199): lane t owns elements t, t + T, ..., t + (K-1) T with T = ceil(n / K).  Z != 0 for every
-// point of the curve (the addition law is complete) -- but MUL_* accepts any pair of field elements (curve4q.py never checks), and the
-// all-zero point a failed decode is lifted to DOES come out with Z = 0: an element whose norm is zero contributes a 1 to the lane's product,
-// so it cannot touch its neighbours, and gets (0, 0) itself -- what conj(0) * 0^(p-2) gives the reference (fields.py:193-199).  A lane's
-// slots past the end of the batch redo its first element and store nothing.  K = 1 for chunks within two generations (one wave per SIMD: the chain's latency is the time either
-// way), K = 4 beyond (throughput: 0.29 -> 0.12 ms per 2^20 elements).  ENC: the result leaves as a 32-byte encoding + status byte
-// (curve4q.py:41-47; 16 + decode status where the input did not decode) instead of 64 bytes of affine words.
+// R1toAffine behind a MUL_*, K elements per lane with one GFp.inv (lower.hip.h; ~2 % of a MUL_endo's multiply-adds at K = 1).  Source: rows of
+// `stride` words, 20 (R1) or 12 ((X, Y, Z)).  Masked: a zero norm, when K > 1 -- MUL_* accepts any pair of field elements (curve4q.py never checks),
+// and the all-zero point a failed decode is lifted to DOES come out with Z = 0.  K = 1 for chunks within two generations (one wave per SIMD: the
+// chain's latency is the time either way), K = 4 beyond (throughput: 0.29 -> 0.12 ms per 2^20 elements).  ENC: the result leaves as a 32-byte
+// encoding + status byte instead of 64 bytes of affine words.
 template <int K, bool ENC>
-__global__ __launch_bounds__(BLOCK) void lower_kernel(const u64* r1, u32 stride, const uint8_t* st_decode, u64* out, uint8_t* status, u32 n) {   // stride: 20 (R1 rows) or 12 ((X, Y, Z) rows)
-    const u32 T = (n + K - 1) / K;
-    const u32 t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= T) return;
+__global__ __launch_bounds__(BLOCK) void lower_kernel(const u64* r1, u32 stride, const uint8_t* st_decode, u64* out, uint8_t* status, u32 n) {
+    LaneSlots<K> s(n);
+    if (!s.lane(blockIdx.x * BLOCK + threadIdx.x)) return;
     Fe2<1> z[K];
-    Fe<1> nz[K], pre[K];
+#pragma clang loop unroll(full)
+    for (int j = 0; j < K; j++) z[j] = load_fe2(r1 + stride * (size_t)s.at(j) + 8);
+    SharedInverse<K, FeOps<false>> si;
 #pragma clang loop unroll(full)
     for (int j = 0; j < K; j++) {
-        const u32 id = t + (u32)j * T, at = id < n ? id : t;
-        z[j] = load_fe2(r1 + stride * (size_t)at + 8);
+        const Fe<1> norm = z_norm(z[j]);
+        if constexpr (K > 1) si.take(j, norm, !fe_is_zero(norm)); else si.take(j, norm);
     }
-    Fe<1> one;
-    one.l[0] = 1; one.l[1] = one.l[2] = one.l[3] = one.l[4] = 0;
-#pragma clang loop unroll(full)
-    for (int j = 0; j < K; j++) {
-        const Fe<1> norm = fe_carry(fe_add(fe_sqr(z[j].re), fe_sqr(z[j].im)));
-        nz[j] = (K > 1) ? fe_select(fe_is_zero(norm) ? 0u : ~0u, norm, one) : norm;
-        if (j == 0) pre[0] = nz[0]; else pre[j] = fe_mul(pre[j - 1], nz[j]);
-    }
-    Fe<1> inv = fe_inv(pre[K - 1]);
+    si.invert();
 #pragma clang loop unroll(full)
     for (int j = K - 1; j >= 0; j--) {
-        const u32 id = t + (u32)j * T, at = id < n ? id : t;
-        const Fe2<1> X = load_fe2(r1 + stride * (size_t)at), Y = load_fe2(r1 + stride * (size_t)at + 4);
-        Fe<1> ninv = inv;                                              // 1 / |Z_j|^2
-        if (j > 0) { ninv = fe_mul(inv, pre[j - 1]); inv = fe_mul(inv, nz[j]); }
-        Fe2<1> zi;
-        zi.re = fe_mul(ninv, z[j].re);                                 // conj(Z) / |Z|^2     fields.py:193-199
-        zi.im = fe_mul(ninv, fe_neg(z[j].im));
+        const u64* row = r1 + stride * (size_t)s.at(j);
+        const Fe2<1> X = load_fe2(row), Y = load_fe2(row + 4);
+        const Fe2<1> zi = z_inverse(z[j], si.peel(j));
         const Fe2<1> ax = fe2_mul(X, zi), ay = fe2_mul(Y, zi);
-        if (id >= n) continue;
-        if constexpr (ENC) {
-            const uint8_t sd = st_decode[id];
-            const uint8_t st = sd ? (uint8_t)(16 + sd) : (uint8_t)0;
-            u64 w[4];
-            point_encode(ax, ay, w);
-            if (st) w[0] = w[1] = w[2] = w[3] = 0;
-            uint4* dst = reinterpret_cast<uint4*>(out + 4 * (size_t)id);
-            dst[0] = make_uint4((u32)w[0], (u32)(w[0] >> 32), (u32)w[1], (u32)(w[1] >> 32));
-            dst[1] = make_uint4((u32)w[2], (u32)(w[2] >> 32), (u32)w[3], (u32)(w[3] >> 32));
-            status[id] = st;
-        } else {
-            u64 o[8];
-            store_fe2(o, ax); store_fe2(o + 4, ay);
-            uint4* dst = reinterpret_cast<uint4*>(out + 8 * (size_t)id);
-#pragma clang loop unroll(full)
-            for (int k = 0; k < 4; k++) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
-        }
+        if (!s.live(j)) continue;
+        if constexpr (ENC) put_encoded(out, status, s.id(j), ax, ay, bytes_decode_status(st_decode[s.id(j)]));
+        else put_affine(out, s.id(j), ax, ay);
     }
 }
 // The 32-byte I/O flavour of MUL_* as THREE kernels per chunk instead of five (round 5): decode + AffineToR1 in one (the decoded point

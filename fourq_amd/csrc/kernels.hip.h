@@ -16,6 +16,7 @@
 
 #include "../../include/fourq_amd.h"
 #include "curve.hip.h"
+#include "lower.hip.h"
 #include "ladder_asm.hip.h"
 #include "recode.hip.h"
 #include "pair.hip.h"
@@ -449,12 +450,6 @@ FQ_DEV void load_scalar(const u64* p, u64 m[4]) {
     m[2] = (u64)b.x | ((u64)b.y << 32); m[3] = (u64)b.z | ((u64)b.w << 32);
 }
 
-// an R1 row of twenty canonical words as ten 16-byte stores
-FQ_DEV void store_row(u64* row, const u64 o[20]) {
-    uint4* dst = reinterpret_cast<uint4*>(row);
-#pragma unroll
-    for (int k = 0; k < 10; k++) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
-}
 // the fused constant-time ladders' source: N, D of the lane's eight entries from its slot into registers, E, F where they are
 template <typename L, typename EF> FQ_DEV ScanSplit<EF> scan_split(const u32* slot, const EF& ef) {
     ScanSplit<EF> regs;
@@ -568,10 +563,10 @@ __global__ __launch_bounds__(BLOCK, ladder_waves(SRC)) void ladder_kernel(Ladder
             if constexpr (ALGO == ENDO && SRC == FUSED && !CT) store_r1_signed(o, Q);
             else store_r1(o, Q);
             const bool xyz = SRC == FUSED && (a.io & LADDER_IO_XYZ_OUT);
-            uint4* dst = reinterpret_cast<uint4*>(a.out + (xyz ? 12 : 20) * (size_t)id);
+            u64* dst = a.out + (xyz ? 12 : 20) * (size_t)id;
 #pragma unroll
             for (int k = 0; k < 10; k++)
-                if (k < 6 || !xyz) dst[k] = make_uint4((u32)o[2 * k], (u32)(o[2 * k] >> 32), (u32)o[2 * k + 1], (u32)(o[2 * k + 1] >> 32));
+                if (k < 6 || !xyz) put_words<2>(dst + 2 * k, o + 2 * k);
         }
     }
 }
@@ -749,7 +744,7 @@ __global__ __launch_bounds__(BLOCK, 1) void mixed_queue_kernel(LadderArgs a, con
         if (live) {
             u64 o[20];
             store_r1(o, Q);
-            store_row(a.out + 20 * (size_t)id, o);
+            put_words<20>(a.out + 20 * (size_t)id, o);
         }
     }
 }
@@ -809,7 +804,7 @@ __global__ __launch_bounds__(BLOCK, 2) void mixed_ct_tail_kernel(LadderArgs a, c
         if (live) {
             u64 o[20];
             store_r1(o, Q);
-            store_row(a.out + 20 * (size_t)id, o);
+            put_words<20>(a.out + 20 * (size_t)id, o);
         }
     }
 }
@@ -1001,60 +996,44 @@ __global__ __launch_bounds__(CT ? BLOCK : COMB_BLOCK_MAX, CT ? 4 : 1) void comb_
     }
 }
 
-// R1toAffine for a whole batch with one GF(p) inversion per K elements (Montgomery's trick; SURVEY 8f row 4,
-// curve4q.py:103-106, fields.py:66-106, :193-199).  Lane t owns elements t, t + T, ..., t + (K-1)T with
-// T = ceil(n / K): it multiplies up the norms |Z|^2, inverts the product once and peels the individual inverses
-// off on the way back.  Elements already rejected (status != 0) and the ragged tail contribute a 1.  The affine
-// result is canonical, hence identical to the per-element inversion.  Z != 0 for every point of the curve (the
-// addition law is complete), so a product is zero only for rejected elements, which are masked.
+// R1toAffine for a whole DH batch with one GF(p) inversion per K elements (lower.hip.h).  Source: the planes of store_proj.
+// Masked: elements already rejected (status != 0), at every K -- a point of the curve has Z != 0, so a product is zero only for those.
+// The chain is inlined (fe_inv_inline): around a call the lane's live values spill.  The affine result is canonical, hence identical to
+// the per-element inversion.
 template <int K>
 __global__ __launch_bounds__(BLOCK) void normalize_kernel(const uint4* proj, u32 stride, u64* out, uint8_t* status, u32 n) {
-    const u32 T = (n + K - 1) / K;
-    const u32 t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= T) return;
-    // every loop over the K elements is unrolled in full: left to its size heuristics the compiler keeps z[], nz[] and pre[] in
-    // scratch memory and walks them by a run-time index (656 bytes per lane at K = 8), a memory round trip per use in a kernel
-    // that is nothing but one dependent chain per lane
-    Fe<1> one;
-    one.l[0] = 1; one.l[1] = one.l[2] = one.l[3] = one.l[4] = 0;
+    LaneSlots<K> s(n);
+    if (!s.lane(blockIdx.x * BLOCK + threadIdx.x)) return;
     Fe2<1> z[K];
     uint8_t st[K];
 #pragma clang loop unroll(full)
     for (int j = 0; j < K; j++) {                     // all loads first: the lane's K elements are K separate cache lines
-        const u32 id = t + (u32)j * T, at = id < n ? id : t;
+        const u32 at = s.at(j);
         z[j] = load_proj_z(proj, stride, at);
-        st[j] = id < n ? status[at] : (uint8_t)FOURQ_DH_NOT_ON_CURVE;
+        st[j] = s.live(j) ? status[at] : (uint8_t)FOURQ_DH_NOT_ON_CURVE;
     }
-    Fe<1> nz[K], pre[K];
+    SharedInverse<K, FeOps<true>> si;
 #pragma clang loop unroll(full)
-    for (int j = 0; j < K; j++) {
-        Fe<1> norm = fe_carry(fe_add(fe_sqr(z[j].re), fe_sqr(z[j].im)));
-        nz[j] = fe_select(st[j] == FOURQ_DH_OK ? ~0u : 0u, norm, one);
-        if (j == 0) pre[0] = nz[0]; else pre[j] = fe_mul(pre[j - 1], nz[j]);
-    }
-    Fe<1> inv = fe_inv_inline(pre[K - 1]);
+    for (int j = 0; j < K; j++) si.take(j, z_norm(z[j]), st[j] == FOURQ_DH_OK);
+    si.invert();
 #pragma clang loop unroll(full)
     for (int j = K - 1; j >= 0; j--) {
-        const u32 id = t + (u32)j * T, at = id < n ? id : t;
-        Fe2<1> X, Y, zi;
-        load_proj_xy(proj, stride, at, X, Y);
-        Fe<1> ninv = inv;                                              // 1 / |Z_j|^2
-        if (j > 0) { ninv = fe_mul(inv, pre[j - 1]); inv = fe_mul(inv, nz[j]); }
-        zi.re = fe_mul(ninv, z[j].re);                                 // conj(Z) / |Z|^2     fields.py:193-199
-        zi.im = fe_mul(ninv, fe_neg(z[j].im));
+        Fe2<1> X, Y;
+        load_proj_xy(proj, stride, s.at(j), X, Y);
+        const Fe2<1> zi = z_inverse(z[j], si.peel(j));
         u64 o[8];
         store_fe2(o, fe2_mul(X, zi));
         store_fe2(o + 4, fe2_mul(Y, zi));
-        uint8_t s = st[j];
-        if (s == FOURQ_DH_OK && (o[0] | o[1] | o[2] | o[3] | o[5] | o[6] | o[7]) == 0 && o[4] == 1) s = FOURQ_DH_NEUTRAL;   // curve4q.py:459-460
-        if (id < n) {
-            uint4* dst = reinterpret_cast<uint4*>(out + 8 * (size_t)id);
+        uint8_t st_j = st[j];
+        if (st_j == FOURQ_DH_OK && (o[0] | o[1] | o[2] | o[3] | o[5] | o[6] | o[7]) == 0 && o[4] == 1) st_j = FOURQ_DH_NEUTRAL;   // curve4q.py:459-460
+        if (s.live(j)) {
+            uint4* dst = reinterpret_cast<uint4*>(out + 8 * (size_t)s.id(j));
 #pragma clang loop unroll(full)
             for (int k = 0; k < 4; k++) {
-                u64 lo = s ? 0 : o[2 * k], hi = s ? 0 : o[2 * k + 1];
+                u64 lo = st_j ? 0 : o[2 * k], hi = st_j ? 0 : o[2 * k + 1];
                 dst[k] = make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
             }
-            status[id] = s;
+            status[s.id(j)] = st_j;
         }
     }
 }

@@ -156,38 +156,23 @@ __global__ __launch_bounds__(BLOCK, 4) void keyset_comb_kernel(const u64* k, con
     if (row >= n) return;
     u64 w[12];
     store_fe2(w, Q.X); store_fe2(w + 4, Q.Y); store_fe2(w + 8, Q.Z);
-    uint4* dst = reinterpret_cast<uint4*>(rows + 12 * (size_t)row);
-#pragma clang loop unroll(full)
-    for (int q = 0; q < 6; q++) dst[q] = make_uint4((u32)w[2 * q], (u32)(w[2 * q] >> 32), (u32)w[2 * q + 1], (u32)(w[2 * q + 1] >> 32));
+    put_words<12>(rows + 12 * (size_t)row, w);
 }
 
 // One inversion per row (the lowering is a hundredth of the comb in front of it).  pre[i] != 0: ok = 0 or a zero row, and status = pre[i].
 template <bool VERIFY>
 __global__ __launch_bounds__(BLOCK) void keyset_lower_kernel(const u64* rows, const uint8_t* pre, const u64* expect, u64* out, uint8_t* ok, uint8_t* status, u32 n) {
-    const u32 i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
+    LaneSlots<1> s(n);
+    if (!s.lane(blockIdx.x * BLOCK + threadIdx.x)) return;
+    const u32 i = s.id(0);
     const u64* row = rows + 12 * (size_t)i;
     const Fe2<1> X = load_fe2(row), Y = load_fe2(row + 4), Z = load_fe2(row + 8);
-    const Fe<1> ninv = fe_inv(fe_carry(fe_add(fe_sqr(Z.re), fe_sqr(Z.im))));
-    Fe2<1> zi;
-    zi.re = fe_mul(ninv, Z.re);                                    // conj(Z) / |Z|^2     fields.py:193-199
-    zi.im = fe_mul(ninv, fe_neg(Z.im));
-    u64 w[4];
-    point_encode(fe2_mul(X, zi), fe2_mul(Y, zi), w);
-    const uint8_t st = pre[i];
-    if constexpr (VERIFY) {
-        const uint4* e = reinterpret_cast<const uint4*>(expect + 4 * (size_t)i);
-        const uint4 e0 = e[0], e1 = e[1];
-        const bool same = e0.x == (u32)w[0] && e0.y == (u32)(w[0] >> 32) && e0.z == (u32)w[1] && e0.w == (u32)(w[1] >> 32) &&
-                          e1.x == (u32)w[2] && e1.y == (u32)(w[2] >> 32) && e1.z == (u32)w[3] && e1.w == (u32)(w[3] >> 32);
-        ok[i] = (same && !st) ? (uint8_t)1 : (uint8_t)0;
-    } else {
-        if (st) w[0] = w[1] = w[2] = w[3] = 0;
-        uint4* dst = reinterpret_cast<uint4*>(out + 4 * (size_t)i);
-        dst[0] = make_uint4((u32)w[0], (u32)(w[0] >> 32), (u32)w[1], (u32)(w[1] >> 32));
-        dst[1] = make_uint4((u32)w[2], (u32)(w[2] >> 32), (u32)w[3], (u32)(w[3] >> 32));
-    }
-    status[i] = st;
+    SharedInverse<1, FeOps<false>> si;
+    si.take(0, z_norm(Z));                                         // nobody is masked
+    si.invert();
+    const Fe2<1> zi = z_inverse(Z, si.peel(0));
+    if constexpr (VERIFY) put_verdict(expect, ok, status, i, fe2_mul(X, zi), fe2_mul(Y, zi), pre[i]);
+    else put_encoded(out, status, i, fe2_mul(X, zi), fe2_mul(Y, zi), pre[i]);
 }
 
 // pk32[i] = the registered bytes of key id_i (of the last key for an index outside the set)

@@ -65,9 +65,7 @@ __global__ __launch_bounds__(BLOCK, 2) void msm_fold_kernel(const u64* rows, u32
     if (!live || j != 0) return;
     u64 w[12];
     store_fe2(w, acc.X); store_fe2(w + 4, acc.Y); store_fe2(w + 8, acc.Z);
-    uint4* dst = reinterpret_cast<uint4*>(rows_out + 12 * team);
-#pragma clang loop unroll(full)
-    for (int k = 0; k < 6; k++) dst[k] = make_uint4((u32)w[2 * k], (u32)(w[2 * k] >> 32), (u32)w[2 * k + 1], (u32)(w[2 * k + 1] >> 32));
+    put_words<12>(rows_out + 12 * team, w);
     if (st_in) st_out[team] = (uint8_t)st;
 }
 
@@ -116,9 +114,7 @@ __global__ __launch_bounds__(BLOCK, 2) void msm_fold_desc_kernel(const u64* rows
     if (!live || j != 0) return;
     u64 w[12];
     store_fe2(w, acc.X); store_fe2(w + 4, acc.Y); store_fe2(w + 8, acc.Z);
-    uint4* dst = reinterpret_cast<uint4*>(rows_out + 12 * team);
-#pragma clang loop unroll(full)
-    for (int k = 0; k < 6; k++) dst[k] = make_uint4((u32)w[2 * k], (u32)(w[2 * k] >> 32), (u32)w[2 * k + 1], (u32)(w[2 * k + 1] >> 32));
+    put_words<12>(rows_out + 12 * team, w);
     if (st_in) st_out[team] = (uint8_t)st;
 }
 

@@ -10,6 +10,7 @@
 // hipError_t of its launch.
 #pragma once
 #include "curve.hip.h"      // constants.inc: ORDER_N, SC_MU, SHA512_IV, SHA512_K
+#include "lower.hip.h"      // put_words
 #include "sha512.hip.h"
 #include "scalar_n.hip.h"
 #include "../../include/fourq_amd.h"
@@ -54,8 +55,7 @@ FQ_DEV void load32(const uint8_t* p, u64 w[4]) {
     w[2] = ((u64)hi.y << 32) | hi.x; w[3] = ((u64)hi.w << 32) | hi.z;
 }
 FQ_DEV void store32(uint8_t* p, const u64 w[4]) {
-    reinterpret_cast<uint4*>(p)[0] = make_uint4((u32)w[0], (u32)(w[0] >> 32), (u32)w[1], (u32)(w[1] >> 32));
-    reinterpret_cast<uint4*>(p)[1] = make_uint4((u32)w[2], (u32)(w[2] >> 32), (u32)w[3], (u32)(w[3] >> 32));
+    put_words<4>(reinterpret_cast<u64*>(p), w);
 }
 // a 32-byte row as the four big-endian words of a hashed string
 FQ_DEV void dleq_row_words(const uint8_t* row, u64 w[4]) {

@@ -60,7 +60,7 @@ template <int VARIANT> __global__ __launch_bounds__(256, 1) void k(const u64* sc
     uint64_t t4 = stamp();
     u64 o[20];
     store_r1(o, Q);
-    store_row(out + 20 * (size_t)id, o);
+    put_words<20>(out + 20 * (size_t)id, o);
     uint64_t t5 = stamp();
     if ((threadIdx.x & 63) == 0) {
         uint64_t* w = stamps + 8 * (size_t)(id >> 6);

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Throughput probe for kernel experiments (GPU box): mults/s by kernel-event time for several
-modes and batch sizes.   python tools/perf_probe.py [--modes endo_var,endo_fixed,...] [--sizes 16,18,20]"""
+modes and batch sizes.   python tools/perf_probe.py [--modes endo_var,endo_fixed,...] [--sizes 16,18,20]
+The calls that end in a lowering kernel (mul_affine, mul_bytes, double_mul, double_mul_bytes, verify_bytes, keyset_double_mul_bytes,
+sig_verify_keyed) are modes too; every line gives the best and the median of --reps event-timed calls after one warm-up call."""
 import argparse
 import os
+import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,7 +46,32 @@ for n in ([int(x) for x in args.ns.split(",")] if args.ns else [1 << int(x) for 
     comb = eng.comb_table(g392)
     t392 = eng.table_endo(g392)
     gaff = torch.from_numpy(np.repeat(codec.pack_point((constants.Gx, constants.Gy)).reshape(1, 8), n, 0).view(np.int64)).to(dev)
+    lowering = {"mul_affine", "mul_bytes", "double_mul", "double_mul_bytes", "verify_bytes", "keyset_double_mul_bytes", "sig_verify_keyed"} & set(args.modes.split(","))
+    if lowering:
+        rng = np.random.default_rng(7700)
+        u8 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        eng.comb_stage(eng.comb_table(g1))
+        eng.reserve(n)
+        enc = u8(eng.encode(aff.cpu().numpy().view(np.uint64)))
+        out32, expect = torch.empty((n, 32), dtype=torch.uint8, device=dev), torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        ok = torch.empty(n, dtype=torch.uint8, device=dev)
+        eng.double_mul_bytes_dev(s, k, enc, expect, st, n)
+        keys = eng.sig_keygen(rng.integers(0, 256, size=(64, 32), dtype=np.uint8))
+        assert not eng.keyset_set(keys).any()
+        eng.keyset_reserve(n)
+        ids = torch.from_numpy(rng.integers(0, 64, size=n).astype(np.uint32).view(np.int32)).to(dev)
+        sig = rng.integers(0, 256, size=(n, 64), dtype=np.uint8)
+        sig[:, 62:] = 0                                              # s < N: no row is refused for its range
+        sig, msg = u8(sig), u8(rng.integers(0, 256, size=(n, 32), dtype=np.uint8))
+        torch.cuda.synchronize()
     fns = {
+        "mul_affine": lambda: eng.mul_affine_dev(s, aff, aff_out, n),
+        "mul_bytes": lambda: eng.mul_bytes_dev(s, enc, out32, st, n),
+        "double_mul": lambda: eng.double_mul_dev(s, k, aff, aff_out, n),
+        "double_mul_bytes": lambda: eng.double_mul_bytes_dev(s, k, enc, out32, st, n),
+        "verify_bytes": lambda: eng.verify_bytes_dev(s, k, enc, expect, ok, st, n),
+        "keyset_double_mul_bytes": lambda: eng.keyset_double_mul_bytes_dev(s, k, ids, out32, st, n),
+        "sig_verify_keyed": lambda: eng.sig_verify_keyed_dev(ids, msg, 32, None, 32, sig, ok, st, n),
         "comb": lambda: eng.comb_mul_dev(s, comb, aff_out, st, n),
         "dh_fixed": lambda: eng.dh_endo_dev(s, gaff, t392, aff_out, st, n),
         "endo_var": lambda: eng.mul_endo_dev(s, pts, out, n),
@@ -55,9 +83,10 @@ for n in ([int(x) for x in args.ns.split(",")] if args.ns else [1 << int(x) for 
     for mode in args.modes.split(","):
         fn = fns[mode]
         fn(); torch.cuda.synchronize()
-        best = 1e9
+        ms = []
         for _ in range(args.reps):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record(stream); fn(); b.record(stream); torch.cuda.synchronize()
-            best = min(best, a.elapsed_time(b))
-        print("n=%-8d (2^%d+%d) %-10s %8.3f ms  %8.2f Mmults/s" % (n, lg, n - (1 << lg), mode, best, n / best / 1e3), flush=True)
+            ms.append(a.elapsed_time(b))
+        best = min(ms)
+        print("n=%-8d (2^%d+%d) %-10s %8.3f ms  %8.2f Mmults/s  median %8.4f ms" % (n, lg, n - (1 << lg), mode, best, n / best / 1e3, statistics.median(ms)), flush=True)
