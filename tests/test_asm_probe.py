@@ -11,12 +11,12 @@ from conftest import ROOT
 PROBE_SRC = os.path.join(ROOT, "tests", "hip", "asm_body_probe.hip")
 
 
-def build_probe(out_dir):
-    """compile the probe like a library unit and link it into a shared object; returns its path"""
+def build_probe(out_dir, src=PROBE_SRC, name="asm_body_probe", extra_flags=()):
+    """compile a probe like a library unit (plus `extra_flags`) and link it into a shared object; returns its path"""
     from fourq_amd import build as fb
-    obj = os.path.join(out_dir, "asm_body_probe.o")
-    fb.compile_unit(PROBE_SRC, obj, fb.HIPCC_FLAGS + ["-I" + fb.SRC_DIR])
-    so = os.path.join(out_dir, "libasm_body_probe.so")
+    obj = os.path.join(out_dir, name + ".o")
+    fb.compile_unit(src, obj, fb.HIPCC_FLAGS + ["-I" + fb.SRC_DIR] + list(extra_flags))
+    so = os.path.join(out_dir, "lib%s.so" % name)
     proc = subprocess.run([fb._hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj], capture_output=True, text=True)
     assert proc.returncode == 0, proc.stdout + proc.stderr
     return so

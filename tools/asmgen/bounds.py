@@ -684,6 +684,24 @@ def corner_vectors(contract_name, rng, count):
     return vecs
 
 
+def pattern_vectors(free, rng, extra, sample=64):
+    """corner inputs for operands that are no contract of a generated body (tests/field_model.py): `free` maps an operand to its limb
+    intervals, a multiple of five of them, and every five are a component.  (pattern, {operand: limbs}) for: all components at max, at
+    min, the two alternating patterns; every combination of components at max / min (a seeded sample of `sample` when there are more
+    than that); then `extra` vectors of random extremes, top limbs and random limbs per component.  corner_vectors is not built on
+    this: its vectors seed the existing tests and stay as they are."""
+    comps = [(name, h) for name in free for h in range(len(free[name]) // 5)]
+    pats = [(p, {c: p for c in comps}) for p in ("max", "min", "alt", "alt2")]
+    n = len(comps)
+    combos = range(1 << n) if (1 << n) <= sample else rng.sample(range(1 << n), sample)
+    for bits in combos:
+        pats.append(("combo%x" % bits, {c: ("max" if bits >> k & 1 else "min") for k, c in enumerate(comps)}))
+    for _ in range(extra):
+        pats.append(("mixed", {c: rng.choice(("ext", "ext", "top", "rand")) for c in comps}))
+    return [(label, {name: [x for h in range(len(free[name]) // 5) for x in _component(free[name][5 * h:5 * h + 5], pat[(name, h)], rng)]
+                     for name in free}) for label, pat in pats]
+
+
 def registers(contract_name, vec, neg=0):
     """sim.py registers of an input vector (limbs mod 2^32), the limb mask and the neg mask included"""
     regs = {}
