@@ -31,6 +31,7 @@ OPRF_BLIND_ZERO = 48                                          # FOURQ_OPRF_BLIND
 DLEQ_NONCE_ZERO = 80                                          # FOURQ_DLEQ_NONCE_ZERO
 KEYSET_MAX_KEYS, KEYSET_NOT_ORDER_N, KEYSET_ID_RANGE = 4096, 96, 112   # FOURQ_KEYSET_*
 VRF_GAMMA_NEUTRAL = 128                                       # FOURQ_VRF_GAMMA_NEUTRAL
+SHAMIR_MAX_T, SHAMIR_ID_ZERO, SHAMIR_ID_REPEATED = 4096, 144, 160   # FOURQ_SHAMIR_*
 
 
 class HostStats(ctypes.Structure):
@@ -190,6 +191,19 @@ PROTOTYPES = {
     "fourq_vrf_verify_keyed_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_vrf_proof_to_hash": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_vrf_proof_to_hash_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "fourq_shamir_reserve": (c_int, [c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_shares": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t]),
+    "fourq_shamir_shares_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t]),
+    "fourq_shamir_lagrange": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_lagrange_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_combine_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_combine_points": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_combine_points_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_public_shares": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_public_shares_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
+    "fourq_shamir_verify_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t]),
     "fourq_encode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_decode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fourq_encode_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),

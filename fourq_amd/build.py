@@ -24,7 +24,7 @@ RESOURCES_PATH = os.path.join(HERE, "kernel_resources.json")
 PLACEMENT_PATH = os.path.join(HERE, "code_placement.json")
 # four translation units: FQ_CHAIN=0 / 1 (kernels.hip.h), and the constant-time-selection builds of both flavours
 SOURCES = ["fourq_amd.hip", "fourq_chain.hip", "fourq_ct_fused.hip", "fourq_ct_chain.hip"]
-HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "lower.hip.h", "kernels.hip.h", "combine.hip.h", "msm.hip.h", "msm_shape.h", "bucket.hip.h", "bucket_layout.h", "commit.hip.h", "commit_layout.h", "keyset.hip.h", "keyset_layout.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "work_layout.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", "h2c.hip.h", "oprf.hip.h", "dleq_layout.h", "dleq.hip.h", "vrf_layout.h", "vrf.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
+HEADERS = ["fp127.hip.h", "curve.hip.h", "recode.hip.h", "lower.hip.h", "kernels.hip.h", "combine.hip.h", "msm.hip.h", "msm_shape.h", "bucket.hip.h", "bucket_layout.h", "commit.hip.h", "commit_layout.h", "keyset.hip.h", "keyset_layout.h", "pair.hip.h", "ladder_asm.hip.h", "ladder_asm_gfx950.inc", "constants.inc", "pipeline_plan.h", "work_layout.h", "sha512.hip.h", "scalar_n.hip.h", "sig.hip.h", "h2c.hip.h", "oprf.hip.h", "dleq_layout.h", "dleq.hip.h", "vrf_layout.h", "vrf.hip.h", "shamir_layout.h", "shamir.hip.h", os.path.join("..", "..", "include", "fourq_amd.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Rpass-analysis=kernel-resource-usage"]
 # Code placement (tools/asmgen/place_asm.py, profiles/r04_ladder_step.txt): the device code of every translation unit goes through
 # assembly text, where every 8-byte instruction is put on an 8-byte boundary (an _e32 instruction in front of it re-encoded as _e64),
@@ -77,6 +77,10 @@ RESOURCE_POLICY = [
     (r"\b(vrf_scalar_kernel|vrf_prove_kernel|vrf_check_kernel)\(", "scratch", lambda v: v == 0,
      "the VRF's hashing kernels load their rows into the message schedule of the block they belong to, as the proofs': nothing may spill"),
     (r"\b(vrf_scalar_kernel|vrf_prove_kernel|vrf_check_kernel)\(", "occupancy", lambda v: v >= 4, "the VRF's hashing kernels are throughput code held to 128 VGPRs: four waves per SIMD"),
+    (r"\b(shamir_shares_kernel|shamir_combine_kernel)\(", "scratch", lambda v: v == 0,
+     "threshold sharing's secret-handling kernels keep an accumulator and one operand row in registers: nothing of a share may spill to memory"),
+    (r"\b(shamir_shares_kernel|shamir_powers_kernel|shamir_combine_kernel)\(", "occupancy", lambda v: v >= 4,
+     "Horner steps and dot products are one dependent chain per lane behind strided loads: four waves per SIMD, as the hashing kernels"),
     (r"\bsc_inv_kernel<", "scratch", lambda v: v == 0, "the inversion modulo N keeps its window table and its K - 1 prefix products in registers across the chain, at every K"),
 ]
 

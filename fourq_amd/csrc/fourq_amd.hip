@@ -48,6 +48,8 @@
 #include "dleq.hip.h"
 #include "vrf_layout.h"
 #include "vrf.hip.h"
+#include "shamir_layout.h"
+#include "shamir.hip.h"
 
 using namespace fq;
 
@@ -2849,6 +2851,173 @@ FQ_API int fourq_vrf_proof_to_hash(fourq_ctx* c, const uint8_t* dst, size_t dst_
     const HostCall d = { { { proof96, 96 } }, { { beta64, 64 }, { status, 1 } }, { PR_VRF_HASH, 0, KT_DECODE + KT_LIFT_LOWER + KT_SHA_BLOCK * (double)((32 + dst_len + 27 + 127) / 128) },
                          unit_w4, nullptr, nullptr, h2c_args_ok(dst, dst_len, FOURQ_H2C_RO) };
     return host_call(c, n, d, [&](const Chunk& k) { return fourq_vrf_proof_to_hash_dev(c, dst, dst_len, k.in<uint8_t>(0), k.out<uint8_t>(0), k.out<uint8_t>(1), k.m); });
+}
+
+// ---- threshold sharing (include/fourq_amd.h, "threshold sharing"): deal, verify, Lagrange, combine -------------------------------------------
+// The curve work is the calls above -- the grouped sum on encodings over groups of t, the comb with its encoding -- and shamir.hip.h's
+// kernels evaluate, multiply and lay the operands out in between.  As the VRF, a composite layout (shamir_layout.h).
+// The argument contract of every call: grouped_rows over (rows, t) -- the call's predicates, then rows == 0 is FOURQ_OK, then t == 0 or a
+// product above FOURQ_MAX_BATCH is FOURQ_ERR_INVALID -- and t above FOURQ_SHAMIR_MAX_T refused with them.
+static int shamir_rows(bool args_ok, size_t rows, size_t t, size_t* n) {
+    const int rc = grouped_rows(args_ok, rows, t, n);
+    if (rc == FOURQ_OK && *n && t > FOURQ_SHAMIR_MAX_T) { *n = 0; return FOURQ_ERR_INVALID; }
+    return rc;
+}
+FQ_API int fourq_shamir_reserve(fourq_ctx* c, size_t rows, size_t t) {
+    size_t n;
+    const int rc = shamir_rows(c != nullptr, rows, t, &n);
+    if (rc || !n) return rc;
+    CtxGuard g(c);
+    return size_for<fq_work::Shamir>(c, false, rows, t);
+}
+FQ_API int fourq_shamir_shares_dev(fourq_ctx* c, const uint64_t* coeffs, const uint32_t* ids, uint64_t* shares, uint8_t* status, size_t n, size_t t, size_t m) {
+    if (!c || !coeffs || !ids || !shares || !status || !aligned16(coeffs) || !aligned16(ids) || !aligned16(shares)) return FOURQ_ERR_INVALID;
+    if (n == 0 || m == 0) return FOURQ_OK;
+    size_t items, lanes;
+    if (int rc = shamir_rows(true, n, t, &items)) return rc;
+    if (int rc = grouped_rows(true, m, n, &lanes)) return rc;
+    CtxGuard g(c);
+    HIPRC_TRY(c, shamir_launch_shares(c->stream, coeffs, ids, shares, status, (u32)n, (u32)t, (u32)m));
+    return FOURQ_OK;
+}
+FQ_API int fourq_shamir_lagrange_dev(fourq_ctx* c, const uint32_t* ids, uint64_t* lambda, uint8_t* status, size_t sets, size_t t) {
+    size_t n;
+    const int rc = shamir_rows(c && ids && lambda && status && aligned16(ids) && aligned16(lambda), sets, t, &n);
+    if (rc || !n) return rc;
+    CtxGuard g(c);
+    WORK_SCOPE(w, Shamir, sets, t);
+    HIPRC_TRY(c, shamir_launch_lagrange(c->stream, ids, lambda, w->flags, status, (u32)sets, (u32)t));
+    return FOURQ_OK;
+}
+FQ_API int fourq_shamir_combine_dev(fourq_ctx* c, const uint32_t* ids, const uint64_t* shares, uint64_t* out, uint8_t* status, size_t n, size_t t) {
+    size_t items;
+    const int rc = shamir_rows(c && ids && shares && out && status && aligned16(ids) && aligned16(shares) && aligned16(out), n, t, &items);
+    if (rc || !items) return rc;
+    CtxGuard g(c);
+    WORK_SCOPE(w, Shamir, n, t);
+    HIPRC_TRY(c, shamir_launch_lagrange(c->stream, ids, w->lambda, w->flags, w->st_set, 1, (u32)t));
+    HIPRC_TRY(c, shamir_launch_combine(c->stream, w->lambda, shares, w->st_set, out, status, (u32)n, (u32)t));
+    return FOURQ_OK;
+}
+FQ_API int fourq_shamir_combine_points_dev(fourq_ctx* c, const uint32_t* ids, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n, size_t t) {
+    size_t items;
+    int rc = shamir_rows(c && ids && points32 && out32 && status && aligned16(ids) && aligned16(points32) && aligned16(out32), n, t, &items);
+    if (rc || !items) return rc;
+    CtxGuard g(c);
+    WORK_SCOPE(w, Shamir, n, t);
+    HIPRC_TRY(c, shamir_launch_lagrange(c->stream, ids, w->lambda, w->flags, w->st_set, 1, (u32)t));
+    HIPRC_TRY(c, shamir_launch_fill(c->stream, w->lambda, points32, w->sc, w->pt, (u32)n, (u32)t));
+    if ((rc = msm_dev(c, w->sc, w->pt, true, out32, status, n, t))) return rc;
+    HIPRC_TRY(c, shamir_launch_set_merge(c->stream, w->st_set, out32, status, (u32)n));
+    return FOURQ_OK;
+}
+// the verification shares of `groups` polynomials into out32 / status, the id 0 not yet merged: the powers, then the grouped sum over commits32 in place
+static int shamir_public_stage(fourq_ctx* c, const fq_work::Shamir& w, const uint8_t* commits32, const uint32_t* ids, uint8_t* out32, uint8_t* status, size_t groups, size_t t) {
+    HIPRC_TRY(c, shamir_launch_powers(c->stream, ids, w.sc, (u32)groups, (u32)t));
+    return msm_dev(c, w.sc, commits32, true, out32, status, groups, t);
+}
+FQ_API int fourq_shamir_public_shares_dev(fourq_ctx* c, const uint8_t* commits32, const uint32_t* ids, uint8_t* out32, uint8_t* status, size_t groups, size_t t) {
+    size_t n;
+    int rc = shamir_rows(c && commits32 && ids && out32 && status && aligned16(commits32) && aligned16(ids) && aligned16(out32), groups, t, &n);
+    if (rc || !n) return rc;
+    CtxGuard g(c);
+    WORK_SCOPE(w, Shamir, groups, t);
+    if ((rc = shamir_public_stage(c, *w, commits32, ids, out32, status, groups, t))) return rc;
+    HIPRC_TRY(c, shamir_launch_id_merge(c->stream, ids, out32, status, (u32)groups));
+    return FOURQ_OK;
+}
+FQ_API int fourq_shamir_verify_dev(fourq_ctx* c, const uint64_t* comb, const uint8_t* commits32, const uint32_t* ids, const uint64_t* shares, uint8_t* ok, uint8_t* status,
+                                   size_t groups, size_t t) {
+    size_t n;
+    int rc = shamir_rows(c && commits32 && ids && shares && ok && status && aligned16(commits32) && aligned16(ids) && aligned16(shares), groups, t, &n);
+    if (rc || !n) return rc;
+    CtxGuard g(c);
+    if ((rc = stage_comb(c, comb))) return rc;
+    WORK_SCOPE(w, Shamir, groups, t);
+    if ((rc = shamir_public_stage(c, *w, commits32, ids, (uint8_t*)w->pub32, w->st_pub, groups, t))) return rc;
+    if ((rc = comb_encode(c, shares, w->affine, w->st_comb, (uint8_t*)w->g32, groups))) return rc;          // encode([share]G)
+    HIPRC_TRY(c, shamir_launch_compare(c->stream, ids, w->pub32, w->g32, shares, w->st_pub, w->st_comb, ok, status, (u32)groups));
+    return FOURQ_OK;
+}
+// Host arrays: copy in through the staging buffer, the _dev call, copy out, synchronise, in one piece (as grouped_host, whose arrays have one
+// row per element or per group; these have their own extents).  `call` gets the device arrays in listed order, each 16-byte aligned.
+struct ShamirArray { const void* in; void* out; size_t bytes; };
+static int shamir_host(fourq_ctx* c, const ShamirArray* arrays, size_t count, const std::function<int(char* const*)>& call) {
+    if (count > GROUPED_MAX_ARRAYS) return FOURQ_ERR_INVALID;
+    CtxGuard g(c);
+    size_t total = 0;
+    for (size_t k = 0; k < count; k++) total += fq_work::align256(arrays[k].bytes);
+    if (int rc = ensure_stage(c, total)) return rc;
+    const fq_work::Hold stage_parent = c->stage_hold;
+    c->stage_hold = stage_parent.opened("shamir_host's arrays", c->stage_bytes, c->stage_bytes);
+    char* dev[GROUPED_MAX_ARRAYS] = {};
+    auto staged = [&]() -> int {
+        size_t used = 0;
+        for (size_t k = 0; k < count; k++) {
+            dev[k] = c->stage + used;
+            if (arrays[k].in) HIP_TRY(c, hipMemcpyAsync(dev[k], arrays[k].in, arrays[k].bytes, hipMemcpyHostToDevice, c->stream));
+            used += fq_work::align256(arrays[k].bytes);
+        }
+        if (int rc = call(dev)) return rc;
+        for (size_t k = 0; k < count; k++)
+            if (arrays[k].out) HIP_TRY(c, hipMemcpyAsync(arrays[k].out, dev[k], arrays[k].bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return FOURQ_OK;
+    };
+    const int rc = staged();
+    c->stage_hold = stage_parent;
+    if (rc != FOURQ_OK) (void)hipStreamSynchronize(c->stream);    // as grouped_host: nothing of this call may still read or write the caller's arrays
+    return rc;
+}
+FQ_API int fourq_shamir_shares(fourq_ctx* c, const uint64_t* coeffs, const uint32_t* ids, uint64_t* shares, uint8_t* status, size_t n, size_t t, size_t m) {
+    if (!c || !coeffs || !ids || !shares || !status) return FOURQ_ERR_INVALID;
+    if (n == 0 || m == 0) return FOURQ_OK;
+    size_t items, lanes;
+    if (int rc = shamir_rows(true, n, t, &items)) return rc;
+    if (int rc = grouped_rows(true, m, n, &lanes)) return rc;
+    const ShamirArray arrays[] = { { coeffs, nullptr, items * 32 }, { ids, nullptr, m * 4 }, { nullptr, shares, lanes * 32 }, { nullptr, status, m } };
+    return shamir_host(c, arrays, 4, [&](char* const* d) { return fourq_shamir_shares_dev(c, (uint64_t*)d[0], (uint32_t*)d[1], (uint64_t*)d[2], (uint8_t*)d[3], n, t, m); });
+}
+FQ_API int fourq_shamir_lagrange(fourq_ctx* c, const uint32_t* ids, uint64_t* lambda, uint8_t* status, size_t sets, size_t t) {
+    size_t n;
+    const int rc = shamir_rows(c && ids && lambda && status, sets, t, &n);
+    if (rc || !n) return rc;
+    const ShamirArray arrays[] = { { ids, nullptr, n * 4 }, { nullptr, lambda, n * 32 }, { nullptr, status, sets } };
+    return shamir_host(c, arrays, 3, [&](char* const* d) { return fourq_shamir_lagrange_dev(c, (uint32_t*)d[0], (uint64_t*)d[1], (uint8_t*)d[2], sets, t); });
+}
+FQ_API int fourq_shamir_combine(fourq_ctx* c, const uint32_t* ids, const uint64_t* shares, uint64_t* out, uint8_t* status, size_t n, size_t t) {
+    size_t items;
+    const int rc = shamir_rows(c && ids && shares && out && status, n, t, &items);
+    if (rc || !items) return rc;
+    const ShamirArray arrays[] = { { ids, nullptr, t * 4 }, { shares, nullptr, items * 32 }, { nullptr, out, n * 32 }, { nullptr, status, 1 } };
+    return shamir_host(c, arrays, 4, [&](char* const* d) { return fourq_shamir_combine_dev(c, (uint32_t*)d[0], (uint64_t*)d[1], (uint64_t*)d[2], (uint8_t*)d[3], n, t); });
+}
+FQ_API int fourq_shamir_combine_points(fourq_ctx* c, const uint32_t* ids, const uint8_t* points32, uint8_t* out32, uint8_t* status, size_t n, size_t t) {
+    size_t items;
+    const int rc = shamir_rows(c && ids && points32 && out32 && status, n, t, &items);
+    if (rc || !items) return rc;
+    const ShamirArray arrays[] = { { ids, nullptr, t * 4 }, { points32, nullptr, items * 32 }, { nullptr, out32, n * 32 }, { nullptr, status, n } };
+    return shamir_host(c, arrays, 4, [&](char* const* d) { return fourq_shamir_combine_points_dev(c, (uint32_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], n, t); });
+}
+FQ_API int fourq_shamir_public_shares(fourq_ctx* c, const uint8_t* commits32, const uint32_t* ids, uint8_t* out32, uint8_t* status, size_t groups, size_t t) {
+    size_t n;
+    const int rc = shamir_rows(c && commits32 && ids && out32 && status, groups, t, &n);
+    if (rc || !n) return rc;
+    const ShamirArray arrays[] = { { commits32, nullptr, n * 32 }, { ids, nullptr, groups * 4 }, { nullptr, out32, groups * 32 }, { nullptr, status, groups } };
+    return shamir_host(c, arrays, 4, [&](char* const* d) { return fourq_shamir_public_shares_dev(c, (uint8_t*)d[0], (uint32_t*)d[1], (uint8_t*)d[2], (uint8_t*)d[3], groups, t); });
+}
+// the comb is staged BEFORE the arrays, and the _dev call gets comb == NULL (as fourq_dleq_verify)
+FQ_API int fourq_shamir_verify(fourq_ctx* c, const uint64_t* comb, const uint8_t* commits32, const uint32_t* ids, const uint64_t* shares, uint8_t* ok, uint8_t* status, size_t groups,
+                               size_t t) {
+    size_t n;
+    int rc = shamir_rows(c && commits32 && ids && shares && ok && status, groups, t, &n);
+    if (rc || !n) return rc;
+    CtxGuard g(c);
+    if ((rc = stage_comb(c, comb))) return rc;
+    const ShamirArray arrays[] = { { commits32, nullptr, n * 32 }, { ids, nullptr, groups * 4 }, { shares, nullptr, groups * 32 }, { nullptr, ok, groups }, { nullptr, status, groups } };
+    return shamir_host(c, arrays, 5, [&](char* const* d) {
+        return fourq_shamir_verify_dev(c, nullptr, (uint8_t*)d[0], (uint32_t*)d[1], (uint64_t*)d[2], (uint8_t*)d[3], (uint8_t*)d[4], groups, t);
+    });
 }
 
 // ---- pinned host memory and transfer statistics of the host-pointer calls ---------------------------------------

@@ -970,6 +970,124 @@ class Engine:
         buf, dst_len, _ = self._h2c(dst, "ro")
         self._ck(self._lib.fourq_vrf_proof_to_hash_dev(self._ctx, buf, dst_len, _ptr(proof96), _ptr(beta64), _ptr(status), n))
 
+    # ---- threshold sharing (fourq_shamir_*; include/fourq_amd.h, "threshold sharing"): Shamir shares modulo N, Feldman commitments and
+    # their check, Lagrange coefficients at 0, combination of scalars and of points.  ids are uint32, never 0.  Party-major: item (i, r) of
+    # an array with one item per (party, row) is [i][r].  MultiEngine does not shard these calls ---------------------------------------
+    @staticmethod
+    def _ids(ids):
+        return np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+
+    @staticmethod
+    def _poly(coeffs):
+        a = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("coefficients are (n, t, 4) words: row r's t coefficients together")
+        return a
+
+    def shamir_reserve(self, rows, t):
+        """Size the context's buffers for `shamir_*_dev` calls of up to rows x t items (fourq_shamir_reserve; reserve() is not enough for
+        them): such calls then only enqueue and, with the comb staged, can be captured."""
+        self._ck(self._lib.fourq_shamir_reserve(self._ctx, int(rows), int(t)))
+
+    def shamir_shares(self, coeffs, ids, out=None, status=None):
+        """shares[p][r] = sum_j coeffs[r][j] ids[p]^j mod N: ((m, n, 4) words party-major, status (m,)).  coeffs: (n, t, 4) words, any
+        values below 2^256, coeffs[r][0] the secret.  status[p]: SHAMIR_ID_ZERO where ids[p] == 0 (block p is zero)."""
+        a, x = self._poly(coeffs), self._ids(ids)
+        n, t, m = a.shape[0], a.shape[1], len(x)
+        out, status = _out(None if out is None else out.reshape(m * n, 4), m * n, 4), _out(status, m, None, np.uint8)
+        self._ck(self._lib.fourq_shamir_shares(self._ctx, _ptr(a), _ptr(x), _ptr(out), _ptr(status), n, t, m))
+        return out.reshape(m, n, 4), status
+
+    def shamir_commitments(self, coeffs, comb=None):
+        """The Feldman commitments encode([coeffs[r][j]]G) as (n, t, 32) uint8: the comb over the n x t coefficients, then encode.
+        comb: the generator's table, None = the staged one.  No new C entry: comb_mul and encode composed."""
+        a = self._poly(coeffs)
+        n, t = a.shape[0], a.shape[1]
+        affine, st = np.empty((n * t, 8), dtype=np.uint64), np.empty(n * t, dtype=np.uint8)
+        self._ck(self._lib.fourq_comb_mul_batch(self._ctx, _ptr(a), _ptr(self._comb_arg(comb)), _ptr(affine), _ptr(st), n * t))
+        out = self.encode(affine)
+        out[st == _lib.DH_NEUTRAL] = np.array([1] + [0] * 31, dtype=np.uint8)       # the comb reports [0]G by its status and a zero row: 01 00 .. 00 is its encoding
+        return out.reshape(n, t, 32)
+
+    def shamir_lagrange(self, ids, out=None, status=None):
+        """lambda[set][i] = prod_(j != i) x_j / (x_j - x_i) mod N for ids (sets, t): ((sets, t, 4) words, status (sets,)).  status:
+        SHAMIR_ID_ZERO, SHAMIR_ID_REPEATED (the set's rows are all zero then), 0."""
+        x = np.ascontiguousarray(ids, dtype=np.uint32)
+        if x.ndim != 2:
+            raise ValueError("ids are (sets, t)")
+        sets, t = x.shape
+        out, status = _out(None if out is None else out.reshape(sets * t, 4), sets * t, 4), _out(status, sets, None, np.uint8)
+        self._ck(self._lib.fourq_shamir_lagrange(self._ctx, _ptr(x), _ptr(out), _ptr(status), sets, t))
+        return out.reshape(sets, t, 4), status
+
+    def shamir_combine(self, ids, shares, out=None):
+        """out[r] = sum_i lambda_i shares[i][r] mod N for ONE set of t ids: ((n, 4) words, status).  shares: (t, n, 4) party-major, any
+        values below 2^256.  status: one int, shamir_lagrange's codes; non-zero: every row is zero."""
+        x, s = self._ids(ids), np.ascontiguousarray(shares, dtype=np.uint64)
+        if s.ndim != 3 or s.shape[0] != len(x) or s.shape[2] != 4:
+            raise ValueError("shares are (t, n, 4) words, one block per id")
+        t, n = s.shape[0], s.shape[1]
+        out, status = _out(out, n, 4), np.zeros(1, dtype=np.uint8)
+        self._ck(self._lib.fourq_shamir_combine(self._ctx, _ptr(x), _ptr(s), _ptr(out), _ptr(status), n, t))
+        return out, int(status[0])
+
+    def shamir_combine_points(self, ids, points32, out=None, status=None):
+        """out32[r] = encode(sum_i [lambda_i]decode(points32[i][r])) for ONE set of t ids: ((n, 32) uint8, status (n,)), byte for byte
+        msm_bytes over lambda tiled and the points transposed.  points32: (t, n, 32) party-major -- server i's replies are block i."""
+        x, p = self._ids(ids), np.ascontiguousarray(points32, dtype=np.uint8)
+        if p.ndim != 3 or p.shape[0] != len(x) or p.shape[2] != 32:
+            raise ValueError("points are (t, n, 32) bytes, one block per id")
+        t, n = p.shape[0], p.shape[1]
+        out, status = _out(out, n, 32, np.uint8), _out(status, n, None, np.uint8)
+        self._ck(self._lib.fourq_shamir_combine_points(self._ctx, _ptr(x), _ptr(p), _ptr(out), _ptr(status), n, t))
+        return out, status
+
+    @staticmethod
+    def _commits(commits32, ids):
+        c, x = np.ascontiguousarray(commits32, dtype=np.uint8), np.ascontiguousarray(ids, dtype=np.uint32).ravel()
+        if c.ndim != 3 or c.shape[0] != len(x) or c.shape[2] != 32:
+            raise ValueError("commitments are (groups, t, 32) bytes, with one id per group")
+        return c, x
+
+    def shamir_public_shares(self, commits32, ids, out=None, status=None):
+        """out32[g] = encode(sum_j [ids[g]^j]decode(commits32[g][j])), party ids[g]'s verification share: ((groups, 32) uint8, status).
+        status: msm_bytes's per group, or SHAMIR_ID_ZERO (first; the row is zero)."""
+        c, x = self._commits(commits32, ids)
+        groups, t = c.shape[0], c.shape[1]
+        out, status = _out(out, groups, 32, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_shamir_public_shares(self._ctx, _ptr(c), _ptr(x), _ptr(out), _ptr(status), groups, t))
+        return out, status
+
+    def shamir_verify(self, commits32, ids, shares, comb=None, ok=None, status=None):
+        """(ok, status) per group: ok[g] = 1 iff shares[g] (4 words) is the value at ids[g] of the polynomial behind commits32[g].
+        status: shamir_public_shares's, else SIG_S_RANGE where shares[g] >= N."""
+        c, x = self._commits(commits32, ids)
+        s = _host(shares, 4)
+        groups, t = c.shape[0], c.shape[1]
+        if len(s) != groups:
+            raise ValueError("one share per group")
+        ok, status = _out(ok, groups, None, np.uint8), _out(status, groups, None, np.uint8)
+        self._ck(self._lib.fourq_shamir_verify(self._ctx, _ptr(self._comb_arg(comb)), _ptr(c), _ptr(x), _ptr(s), _ptr(ok), _ptr(status), groups, t))
+        return ok, status
+
+    def shamir_shares_dev(self, coeffs, ids, shares, status, n, t, m):
+        self._ck(self._lib.fourq_shamir_shares_dev(self._ctx, _ptr(coeffs), _ptr(ids), _ptr(shares), _ptr(status), n, t, m))
+
+    def shamir_lagrange_dev(self, ids, lam, status, sets, t):
+        self._ck(self._lib.fourq_shamir_lagrange_dev(self._ctx, _ptr(ids), _ptr(lam), _ptr(status), sets, t))
+
+    def shamir_combine_dev(self, ids, shares, out, status, n, t):
+        self._ck(self._lib.fourq_shamir_combine_dev(self._ctx, _ptr(ids), _ptr(shares), _ptr(out), _ptr(status), n, t))
+
+    def shamir_combine_points_dev(self, ids, points32, out32, status, n, t):
+        self._ck(self._lib.fourq_shamir_combine_points_dev(self._ctx, _ptr(ids), _ptr(points32), _ptr(out32), _ptr(status), n, t))
+
+    def shamir_public_shares_dev(self, commits32, ids, out32, status, groups, t):
+        self._ck(self._lib.fourq_shamir_public_shares_dev(self._ctx, _ptr(commits32), _ptr(ids), _ptr(out32), _ptr(status), groups, t))
+
+    def shamir_verify_dev(self, commits32, ids, shares, ok, status, groups, t, comb_host=None):
+        self._ck(self._lib.fourq_shamir_verify_dev(self._ctx, _ptr(self._comb_arg(comb_host)), _ptr(commits32), _ptr(ids), _ptr(shares), _ptr(ok), _ptr(status), groups, t))
+
     def dh_exchange_dev(self, a_scalars, b_scalars, base_affine_host, table392_host, out_affine, status, n):
         base = _host(base_affine_host, None).ravel()
         t = None if table392_host is None else _host(table392_host, None).ravel()

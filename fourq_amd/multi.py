@@ -7,6 +7,8 @@ shard g owns rows [g*n/G, (g+1)*n/G) (`dist.shard_bounds`, the same cut the one-
 GIL for the duration of a library call, so the per-device pipelines (H2D, kernels, D2H) really
 overlap.  The reference's API is a plain function call (curve4q.py:188, :405, :464-468); this is the same call with
 the node's GPUs behind it.  Fixed-base tables and comb tables are replicated (1 KiB / 13 KiB per device).
+Threshold sharing (`Engine.shamir_*`) is NOT sharded: its arrays are party-major, so a contiguous cut of the rows is not a
+contiguous cut of the arrays, and its batches are small beside the ladders'; call it on `engines[0]` or on an `Engine`.
 
     with MultiEngine() as eng:                 # every visible MI355X; MultiEngine([0, 0]) = two contexts on GPU 0
         out = eng.mul_endo(scalars, points)    # same arrays, same results as Engine.mul_endo

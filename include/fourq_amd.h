@@ -855,6 +855,66 @@ int fourq_vrf_verify_keyed_dev(fourq_ctx *ctx, const uint32_t *key_ids, const ui
 int fourq_vrf_proof_to_hash(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *proof96, uint8_t *beta64, uint8_t *status, size_t n);
 int fourq_vrf_proof_to_hash_dev(fourq_ctx *ctx, const uint8_t *dst, size_t dst_len, const uint8_t *proof96, uint8_t *beta64, uint8_t *status, size_t n);
 
+/* ---- threshold sharing: Shamir shares modulo N, Feldman commitments and their check, Lagrange coefficients, combination ----------------------
+ * For a key that is split t-of-n across machines.  N is the group order; scalars are 4 little-endian words.  A party's identifier is a
+ * uint32_t id, the evaluation point x = id; ids are public.  The id 0 is refused: f(0) is the secret.  A polynomial is t coefficients
+ * a_0 .. a_(t-1), each ANY value in [0, 2^256), read modulo N; a_0 is the secret; 1 <= t <= FOURQ_SHAMIR_MAX_T.
+ * Party-major layout: wherever an array holds one 32-byte item per (party, row), block i holds party i's n rows contiguously, item (i, r)
+ * at index i * n + r -- what a dealer sends to party i, what a client receives from server i.  No call asks the caller to interleave.
+ *   shares          shares[p][r] = sum_j a_rj ids[p]^j mod N, canonical.  coeffs: n x t x 4 words, row r's coefficients together; ids: m;
+ *                   shares: party-major m x n x 4 words.  status[p]: FOURQ_SHAMIR_ID_ZERO where ids[p] == 0 (block p is all zero), else 0.
+ *                   Repeated ids are no error here: equal blocks.  One (party, row) per lane, Horner's rule from a_(t-1) down.
+ *   lagrange        lambda[set][i] = prod_(j != i) x_j / (x_j - x_i) mod N, canonical: the coefficients at 0.  ids: sets x t.  status[set]:
+ *                   FOURQ_SHAMIR_ID_ZERO if any id of the set is 0, else FOURQ_SHAMIR_ID_REPEATED if two are equal, else 0.  A set with
+ *                   a status has ALL its rows zero; other sets are unaffected.  t = 1 gives lambda = 1.
+ *   combine         out[r] = sum_i lambda_i shares[i][r] mod N for ONE set of t ids; shares: party-major t x n x 4 words, each any value
+ *                   in [0, 2^256).  status: ONE byte, lagrange's codes; non-zero: every out row is zero.
+ *   combine_points  out32[r] = encode(sum_i [lambda_i]decode(points32[i][r])) for ONE set of t ids; points32: party-major t x n x 32 bytes;
+ *                   status: n bytes.  out32 and status are byte for byte what fourq_msm_bytes_batch returns for groups = n, group_size = t,
+ *                   scalar row (r, i) = lambda_i and point row (r, i) = points32[i][r]: 16 + the largest FOURQ_DECODE_* of a group with its
+ *                   zero row, the neutral point as an ordinary result.  A bad id set marks EVERY row with its code and zeroes it, ahead
+ *                   of the decode codes.  "In the exponent": with points32[i] = server i's fourq_oprf_evaluate_batch reply under its
+ *                   share, out32 is the reply under the undivided key, byte for byte.
+ *   public_shares   out32[g] = encode(sum_j [ids[g]^j mod N]decode(C_gj)): party ids[g]'s verification share from the Feldman
+ *                   commitments C_g0 .. C_g,t-1 of polynomial g (commits32: groups x t x 32 bytes; C_gj = encode([a_gj]G): the comb over
+ *                   the coefficients, then fourq_encode_batch).  status: fourq_msm_bytes_batch's per group, or FOURQ_SHAMIR_ID_ZERO,
+ *                   which comes first and zeroes the row.  A coefficient that is 0 mod N has the commitment 01 00 .. 00, the neutral
+ *                   point's encoding, which the reference's decode refuses: as in fourq_msm_bytes_batch that group reports
+ *                   16 + FOURQ_DECODE_REF_ATTRIBUTE_ERROR.  A dealer draws its coefficients from [1, N).
+ *   verify          ok[g] = (public_share_g == encode([shares[g]]G)); shares: groups x 4 words; the right side through the generator's comb
+ *                   (`comb`, or NULL = the staged one, as fourq_sig_*) and encode.  status: that of public_shares, else
+ *                   FOURQ_SIG_S_RANGE where shares[g] >= N; ok is 0 wherever the status is not.  Both sides may be the neutral point
+ *                   (f(x) = 0 mod N): that compares equal, with status 0.
+ * Secrets.  Coefficients, shares and combine's out never steer a branch or an address: straight-line code on whole words (shamir.hip.h,
+ * scalar_n.hip.h).  Ids, lambda, commitments and verification shares are public.  The library has no random numbers: coefficients come
+ * from the caller.
+ * Arguments.  groups, n, sets or m == 0: FOURQ_OK, nothing touched.  t == 0 with work to do, t > FOURQ_SHAMIR_MAX_T, a NULL array, a
+ * misaligned _dev pointer, or n x t (shares: also m x n) above FOURQ_MAX_BATCH: FOURQ_ERR_INVALID before anything is staged.  Every _dev
+ * array is 16-byte aligned except ok and status.
+ * Work buffer.  combine_points, public_shares and verify run fourq_msm_bytes_batch_dev (and verify the comb) as inner calls; their own
+ * regions lie behind the largest inner layout (shamir_layout.h).  fourq_shamir_reserve(ctx, rows, t) sizes the buffers for any call of
+ * this section with at most rows x t items (shares needs none); after it, with the comb staged, a _dev call allocates nothing,
+ * synchronises nothing and can be captured.  The host flavours copy in, run the twin and copy out, in one piece.
+ * Names: no _batch, as the VRF's.  Cost: tools/shamir_timing.py (profiles/shamir_timing.txt); nothing of it is quoted here. */
+#define FOURQ_SHAMIR_MAX_T 4096
+#define FOURQ_SHAMIR_ID_ZERO 144      /* status: the id is 0 (f(0) is the secret) */
+#define FOURQ_SHAMIR_ID_REPEATED 160  /* status of lagrange and the combines: two ids of the set are equal */
+int fourq_shamir_reserve(fourq_ctx *ctx, size_t rows, size_t t);
+int fourq_shamir_shares(fourq_ctx *ctx, const uint64_t *coeffs, const uint32_t *ids, uint64_t *shares, uint8_t *status, size_t n, size_t t, size_t m);
+int fourq_shamir_shares_dev(fourq_ctx *ctx, const uint64_t *coeffs, const uint32_t *ids, uint64_t *shares, uint8_t *status, size_t n, size_t t, size_t m);
+int fourq_shamir_lagrange(fourq_ctx *ctx, const uint32_t *ids, uint64_t *lambda, uint8_t *status, size_t sets, size_t t);
+int fourq_shamir_lagrange_dev(fourq_ctx *ctx, const uint32_t *ids, uint64_t *lambda, uint8_t *status, size_t sets, size_t t);
+int fourq_shamir_combine(fourq_ctx *ctx, const uint32_t *ids, const uint64_t *shares, uint64_t *out, uint8_t *status, size_t n, size_t t);
+int fourq_shamir_combine_dev(fourq_ctx *ctx, const uint32_t *ids, const uint64_t *shares, uint64_t *out, uint8_t *status, size_t n, size_t t);
+int fourq_shamir_combine_points(fourq_ctx *ctx, const uint32_t *ids, const uint8_t *points32, uint8_t *out32, uint8_t *status, size_t n, size_t t);
+int fourq_shamir_combine_points_dev(fourq_ctx *ctx, const uint32_t *ids, const uint8_t *points32, uint8_t *out32, uint8_t *status, size_t n, size_t t);
+int fourq_shamir_public_shares(fourq_ctx *ctx, const uint8_t *commits32, const uint32_t *ids, uint8_t *out32, uint8_t *status, size_t groups, size_t t);
+int fourq_shamir_public_shares_dev(fourq_ctx *ctx, const uint8_t *commits32, const uint32_t *ids, uint8_t *out32, uint8_t *status, size_t groups, size_t t);
+int fourq_shamir_verify(fourq_ctx *ctx, const uint64_t *comb, const uint8_t *commits32, const uint32_t *ids, const uint64_t *shares,
+                        uint8_t *ok, uint8_t *status, size_t groups, size_t t);
+int fourq_shamir_verify_dev(fourq_ctx *ctx, const uint64_t *comb, const uint8_t *commits32, const uint32_t *ids, const uint64_t *shares,
+                            uint8_t *ok, uint8_t *status, size_t groups, size_t t);
+
 /* ---- primitives (one reference function per op, batched) --------------------------------------
  * Used by the Python mirror of the reference's helper API (GFp.*, GFp2.*, DBL, ADD, phi, ...) and by
  * the parity tests to check every layer of the path on the GPU.  in/out are HOST pointers;
